@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: vanilla NeRF (BASELINE.json configs[1]) on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one training step of the hot path (reference run.py:312-338) on one batch of synthetic
@@ -11,10 +11,14 @@ draws, rays, composited targets and depths in one kernel) -> fused bf16-MFMA dec
 -> composite + MSE + backward (one kernel) -> dgrad chain -> wgrad (bf16 MFMA) -> (RCCL all-reduce) -> Adam ->
 weight repack, inputs resident in HBM.  ``value`` / ``ms_per_step`` / ``dtype`` are THIS step: every MFMA in it
 contracts bf16 operands (BASELINE configs[1]).  The same step on 8-bit training images (library option stash_fp8:
-e4m3 x e5m2 weight-gradient operands, narrower than the config's precision) is timed afterwards and reported
-beside it as ``value_fp8_images`` -- a labelled secondary figure, never the headline.  Rays shard across ranks (weak scaling: every rank owns its own
-4096-ray batch; one gradient all-reduce per step).  ``value`` = rays/s summed over ranks.  The same run
-also reports: the 800x800, 128-samples/ray render (``render_fps``); every phase of the step timed INSIDE
+e4m3 x e5m2 weight-gradient operands, narrower than the config's precision) is timed afterwards (``--full``) and
+reported beside it as ``value_fp8_images`` -- a labelled secondary figure, never the headline.  Rays shard across ranks (weak scaling: every rank owns its own
+4096-ray batch; one gradient all-reduce per step).  ``value`` = rays/s summed over ranks.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (``value``, ``ms_per_step``, ...);
+``--dump-outputs DIR`` also writes what the last timed step handed back (loss, updated weights, gradients, Adam
+moments) as float32 DIR/<name>.npy.  With ``--full`` the same run goes on to report the 8-bit-image step, the
+800x800, 128-samples/ray render (``render_fps``); every phase of the step timed INSIDE
 the step with HIP events on the launch stream (``kernels_in_step``, what rocprofv3's per-kernel averages
 in profiles/ show) and each kernel launched back to back on its own (``kernels``); the roofline of the
 dominant kernel from its in-step time; the step against the MFMA roof SURVEY 8(d) binds configs[1] to
@@ -72,6 +76,17 @@ def pmc_summary(name):
     if meta.get("kernel_sources_sha16") != src["kernel_sources_sha16_now"]:
         return {}, dict(src, stale="the kernels' sources have changed since the counters were collected: traffic withheld")
     return data, dict(src, stale=False)
+
+
+def dump_outputs(out_dir, arrays, limit_bytes=64 << 20):
+    """--dump-outputs: one float32 DIR/<name>.npy per array the timed path handed back in its last step"""
+    import numpy as np
+    host = {name: t.detach().float().cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    assert total <= limit_bytes, f"outputs of {total} bytes exceed the {limit_bytes}-byte dump limit"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def synth_rays(n, seed, device):
@@ -475,14 +490,21 @@ def main():
     ap.add_argument("--render-samples", type=int, default=128)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-render", action="store_true")
-    ap.add_argument("--no-instant", action="store_true", help="skip the shortened Instant-NGP block of the default run")
+    ap.add_argument("--no-instant", action="store_true", help="skip the shortened Instant-NGP block of the --full run")
     ap.add_argument("--render-frames", type=int, default=10)
     ap.add_argument("--frames", type=int, default=100, help="GPU-resident 800x800 training frames the batches are drawn from")
-    ap.add_argument("--no-part4", action="store_true", help="skip the Part 4 block of the default run")
+    ap.add_argument("--no-part4", action="store_true", help="skip the Part 4 block of the --full run")
     ap.add_argument("--workload", choices=["vanilla", "instant", "part4"], default="vanilla",
                     help="vanilla = BASELINE.json configs[1] (default, the judged line); instant = configs[2] / configs[3]; "
                          "part4 = configs[4] on one GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also measure everything else: in-step phase times, the 8-bit-image step, "
+                         "per-kernel times and rooflines, render FPS, the CPU baseline, the Instant-NGP and Part 4 blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, weights, gradients, Adam moments) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.workload != "vanilla":
+        raise SystemExit("--dump-outputs writes the outputs of the vanilla workload's timed step only")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -577,10 +599,19 @@ def main():
                    "parallelism": f"ray-dp{world}", "weights": "random init (seed 0)",
                    "frames": f"{args.frames} x 800x800 RGBA resident in HBM (uniform noise)",
                    "training_images": "bf16 (layer inputs and pre-activation gradients); forward, dgrad and wgrad all on "
-                                      "v_mfma_f32_32x32x16_bf16, fp32 accumulate everywhere",
-                   "render": f"800x800 x {args.render_samples} samples/ray"},
+                                      "v_mfma_f32_32x32x16_bf16, fp32 accumulate everywhere"},
         "final_loss": float(loss.item()),
     }
+    if rank == 0 and args.dump_outputs is not None:
+        # the parameters are replicated after the all-reduce: rank 0's copy is every rank's
+        dump_outputs(args.dump_outputs, {"loss": loss, "params": eng.params, "grads": eng.grads,
+                                         "adam_exp_avg": eng.exp_avg, "adam_exp_avg_sq": eng.exp_avg_sq})
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- every phase timed INSIDE the step: a HIP event on the launch stream after each phase.  EVERY rank runs
     # these steps (they contain the gradient all-reduce: a rank-0-only loop would wait for its peers for ever)
@@ -703,6 +734,7 @@ def main():
 
     # ---- render: 800x800 rays, 128 samples, rays split into row bands across ranks ----
     if not args.no_render:
+        out["config"]["render"] = f"800x800 x {args.render_samples} samples/ray"
         H = W = 800
         rows = H // world
         ro, rd, _ = synth_rays(rows * W, 7 + rank, device)

@@ -185,7 +185,7 @@ def test_bench_two_rank_control_flow_on_one_device(workload, tmp_path):
     port = 29650 + (0 if workload == "vanilla" else 1)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--frames", "6",
-           "--no-cpu-baseline", "--render-frames", "1"]
+           "--full", "--no-cpu-baseline", "--render-frames", "1"]
     if workload == "instant":
         cmd += ["--workload", "instant"]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, env=env, timeout=420)

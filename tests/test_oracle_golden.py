@@ -1,7 +1,8 @@
 """Pin the CPU oracle to the reference's own outputs (tests/golden/*.npz).
 
 Bit-exact for sampling / voxel indices / masks; tight fp tolerance elsewhere
-(the oracle uses the same torch ops in the same order, so most are bit-exact too).
+(the oracle uses the same torch ops in the same order, so most are bit-exact too on the CPU the vectors
+were recorded on; the last bits of sin / exp depend on the CPU's vector code paths).
 """
 import numpy as np
 import pytest
@@ -19,7 +20,7 @@ def test_fourier(dim, L):
     g = golden(f"g1_fourier_d{dim}_L{L}")
     y = O.fourier_encode(T(g["x"]), L)
     assert y.shape == g["y"].shape
-    assert np.array_equal(y.numpy(), g["y"])
+    np.testing.assert_allclose(y.numpy(), g["y"], rtol=1e-6, atol=1e-7)
 
 
 @pytest.mark.parametrize("S", [64, 128])
@@ -70,12 +71,16 @@ def test_composite_forward_backward(S, tag):
     rgb = T(g["rgb"]).requires_grad_(True)
     sig = T(g["sigma"]).requires_grad_(True)
     c, dep, acc = O.composite(rgb, sig, T(g["z"]), T(g["rays_d"]), bg)
-    assert np.array_equal(c.detach().numpy(), g["out_rgb"])
-    assert np.array_equal(dep.detach().numpy(), g["out_depth"])
-    assert np.array_equal(acc.detach().numpy(), g["out_acc"])
+    np.testing.assert_allclose(c.detach().numpy(), g["out_rgb"], rtol=1e-6, atol=1e-9)
+    np.testing.assert_allclose(dep.detach().numpy(), g["out_depth"], rtol=1e-6, atol=1e-9)
+    np.testing.assert_allclose(acc.detach().numpy(), g["out_acc"], rtol=1e-6, atol=1e-9)
     ((c * T(g["g_rgb_map"])).sum() + (dep * T(g["g_depth"])).sum() + (acc * T(g["g_acc"])).sum()).backward()
-    np.testing.assert_allclose(sig.grad.numpy(), g["d_sigma"], rtol=1e-6, atol=1e-9)
-    np.testing.assert_allclose(rgb.grad.numpy(), g["d_rgb"], rtol=1e-6, atol=1e-9)
+    # the forward's last-bit differences between CPUs pass through the transmittance scan.  The absolute floor is about
+    # 2 ulp at the scale of d_rgb (|d_rgb| <= ~1) and binds only there and on the small d_sigma entries: the large ones
+    # (|d_sigma| reaches ~1e10 where the last interval is 1e10 long) stay under rtol (largest difference seen between two
+    # CPUs: 6e-8)
+    np.testing.assert_allclose(sig.grad.numpy(), g["d_sigma"], rtol=1e-6, atol=2e-7)
+    np.testing.assert_allclose(rgb.grad.numpy(), g["d_rgb"], rtol=1e-6, atol=2e-7)
 
 
 def test_render_rays_plain_jitter_and_grads():
@@ -128,7 +133,7 @@ def _blob(x, d):
 def test_density_grid_static(res):
     g = golden(f"g7_grid_static_res{res}")
     grid, binary, ratio = O.density_grid_update(_blob, 1.5, res, 0.12)
-    assert np.array_equal(grid.numpy(), g["grid"])
+    np.testing.assert_allclose(grid.numpy(), g["grid"], rtol=1e-6, atol=0)
     assert np.array_equal(binary.numpy(), g["binary"])
     assert ratio == pytest.approx(float(g["ratio"]), abs=1e-9)
 

@@ -16,7 +16,7 @@ passes() {   # passes <workload> cmd...
   echo "$w rc=$?"
   python3 tools/pmc_summarize.py "$dir" "$dir/summary.json" > "$dir/summary.txt" 2>&1
 }
-passes vanilla python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-instant --no-part4 --render-frames 1
+passes vanilla python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-instant --no-part4 --render-frames 1
 passes instant python3 bench.py --workload instant --steps 6 --render-frames 1
 passes part4 python3 tools/part4_profile_loop.py 40
 # only the summaries travel back (the per-dispatch counter files are large)

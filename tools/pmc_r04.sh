@@ -19,7 +19,7 @@ passes() {   # passes <workload> cmd...
 WL=${*:-vanilla instant part4}
 for w in $WL; do
   case $w in
-    vanilla) passes vanilla python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-instant --no-part4 --render-frames 1 ;;
+    vanilla) passes vanilla python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-instant --no-part4 --render-frames 1 ;;
     instant) python3 tools/instant_profile_loop.py train /tmp/instant_state.pt > gpurun_out/pmc_r04_instant_train.log 2>&1 \
              && passes instant python3 tools/instant_profile_loop.py loop /tmp/instant_state.pt 24 ;;
     part4) passes part4 python3 tools/part4_profile_loop.py 40 ;;
