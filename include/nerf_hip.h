@@ -680,6 +680,27 @@ int nerf_p4_canon_bwd(const void* packed, void* workspace, const float* rgb, con
 int nerf_p4_deform_bwd(const void* packed, const float* params_f32, void* workspace, const float* d_delta_x, int64_t n,
                        float* grads_f32, void* amax_bits, void* grad_lm, nerf_stream_t stream);
 
+/* ---- Part 3 deformation MLP (csrc/p3deform.hip) ------------------------------------------------------------------
+ * Replaces DeformationNetwork (reference src/decoders.py:165-195) with its Fourier codes (src/embeddings.py:22-32) and
+ * x_c = x + delta_x (src/core.py:262-270):
+ *   [Fourier_10(x') (63) | Fourier_10(t') (21)] -> 128 -> 128 -> 128 -> 3, ReLU between, biases on every layer.
+ * params_f32 [nerf_p3_deform_param_count()] = deform_net.net.{0,2,4,6}.{weight,bias} concatenated ([out,in] row-major):
+ *   W1 [128,84] b1 [128] W2 [128,128] b2 [128] W3 [128,128] b3 [128] W4 [3,128] b4 [3].
+ * Forward on fp16 operands, backward and training images bf16, fp32 accumulation.  The workspace (nerf_p3_deform_workspace_bytes(n),
+ * 256-byte aligned) holds the training images and the weight-gradient partial tiles; inference (train 0) may pass NULL.
+ * x_code [n,3] (x', the code's input; NULL: pts), pts [n,3] (x_c = pts + delta_x), t_deform [n]. */
+int64_t nerf_p3_deform_param_count(void);
+size_t nerf_p3_deform_packed_bytes(void);
+size_t nerf_p3_deform_workspace_bytes(int64_t n);
+int nerf_p3_deform_pack(const float* params_f32, void* packed, nerf_stream_t stream);
+int nerf_p3_deform_fwd(const void* packed, void* workspace, const float* x_code, const float* pts, const float* t_deform,
+                       int64_t n, float* delta_x, float* x_canonical, int train, nerf_stream_t stream);
+/* from d loss / d delta_x [n,3] of the last training forward on this workspace: the weight and bias gradients of the four
+ * layers ACCUMULATED into grads_f32 [nerf_p3_deform_param_count()].  The sum over samples is taken by chunk-partial tiles and
+ * one reduction in chunk order (no float atomics): the same bits on every run, with or without option "deterministic". */
+int nerf_p3_deform_bwd(const void* packed, void* workspace, const float* d_delta_x, int64_t n, float* grads_f32,
+                       nerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

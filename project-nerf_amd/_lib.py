@@ -118,6 +118,12 @@ PROTOTYPES = {
     "nerf_p4_canon_fwd": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, i64, c_ptr, c_ptr, i32, c_ptr]),
     "nerf_p4_canon_bwd": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, i64, c_ptr, c_ptr, c_ptr, c_ptr]),
     "nerf_p4_deform_bwd": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, i64, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "nerf_p3_deform_param_count": (i64, []),
+    "nerf_p3_deform_packed_bytes": (size_t, []),
+    "nerf_p3_deform_workspace_bytes": (size_t, [i64]),
+    "nerf_p3_deform_pack": (i32, [c_ptr, c_ptr, c_ptr]),
+    "nerf_p3_deform_fwd": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, i64, c_ptr, c_ptr, i32, c_ptr]),
+    "nerf_p3_deform_bwd": (i32, [c_ptr, c_ptr, c_ptr, i64, c_ptr, c_ptr]),
     "nerf_tv_codes_bytes": (size_t, [i64]),
     "nerf_tv_normsq_codes": (i32, [c_ptr, c_ptr, i64, i32, f32, f32, c_ptr, i32, c_ptr, c_ptr]),
     "nerf_clip_adamw_small": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, i64, i32, f32, f32, f32, f32, f32, f32, f32, c_ptr, i32, c_ptr]),

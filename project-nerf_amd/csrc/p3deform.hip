@@ -1,0 +1,454 @@
+// Part 3 deformation MLP (reference src/decoders.py:165-195, applied at src/core.py:262-270) as a fused register chain:
+//
+//   xcode = Fourier_10(x')   63 columns [x | sin(2^0 pi x) | cos(2^0 pi x) | ...]   (src/embeddings.py:22-32)
+//   tcode = Fourier_10(t')   21 columns
+//   h1 = relu(W1 [xcode | tcode] + b1)    84 -> 128
+//   h2 = relu(W2 h1 + b2)                 128 -> 128
+//   h3 = relu(W3 h2 + b3)                 128 -> 128
+//   dx = W4 h3 + b4                       128 -> 3
+//   x_c = x + dx                          x, NOT the noised x' (core.py:268-270)
+//
+// Same register chain as p4mlp.hip: 32 samples per wave on the MFMA column, accumulator tiles -> 16-bit B fragments of the
+// next layer, every weight fragment of one direction resident in LDS (forward 96 KiB fp16 + 1 KiB of biases, backward 68 KiB
+// bf16: one workgroup of 8 waves per CU).  The forward contracts fp16 operands (v_mfma_f32_32x32x16_f16) for the reason
+// p4mlp.hip gives: dx moves x_c inside a canonical hash grid whose finest cells are ~4.3e-4 wide.  The backward and the
+// training images are bf16.  b1 rides on a constant-1 column (84) of the layer-1 operand, b2 / b3 initialise the accumulators,
+// b4 is added to the output.
+//
+// Training images are row-major [n_pad][width] bf16 (code 96, h1..h3 128; the relu masks are h > 0 of the stored values,
+// which bf16 rounding cannot flip).  The backward runs the transposed chain on the stored masks (no input gradient: x', t'
+// are not learned) and writes dz1..dz3; the weight gradients are then summed by chunk-partial tiles in a slab and ONE
+// reduction in chunk order: no float atomics anywhere, the same bits on every run.
+//
+// Parameter vector (fp32, the module's state dict concatenated, [out, in] row-major):
+//   W1 [128,84] b1 [128] W2 [128,128] b2 [128] W3 [128,128] b3 [128] W4 [3,128] b4 [3]   deform_net.net.{0,2,4,6}
+#include "mlp_chain.h"
+
+namespace nerf {
+namespace p3 {
+
+constexpr int kIn = 84, kHid = 128, kCodeLd = 96, kTimeDim = 21, kPosDim = 63;
+constexpr int kW1 = 0, kB1 = 10752, kW2 = 10880, kB2 = 27264, kW3 = 27392, kB3 = 43776, kW4 = 43904, kB4 = 44288, kParams = 44291;
+constexpr int kThreads = 512, kWaves = kThreads / 64, kTile = kWaves * 32;
+
+// (m-tiles, k-steps fed by accumulators, natural-order k-steps, first fragment)
+struct Step { int mt, ks_acc, ks_nat, frag0; };
+enum { F1, F2, F3, F4, B4t, B3t, B2t, kSteps };
+constexpr Step step_of(int s) {
+  switch (s) {
+    case F1: return {4, 0, 6, 0};       // [xcode | tcode | 1] (96 nat) -> 128
+    case F2: return {4, 8, 0, 24};      // 128 -> 128
+    case F3: return {4, 8, 0, 56};
+    case F4: return {1, 8, 0, 88};      // 128 -> 3
+    case B4t: return {4, 0, 1, 96};     // d dx (16 nat) -> d h3
+    case B3t: return {4, 8, 0, 100};    // dz3 -> d h2
+    default: return {4, 8, 0, 132};     // B2t: dz2 -> d h1
+  }
+}
+constexpr int kFrags = 164;
+constexpr int kFwd0 = 0, kFwdN = 96, kBwd0 = 96, kBwdN = 68;
+constexpr size_t kBiasOff = (size_t)kFrags * 1024;             // b2 [128] | b3 [128] | b4 [3] (fp32)
+constexpr size_t kPackBytes = kBiasOff + 2048;
+constexpr int kFwdLds = kFwdN * 1024 + 2048, kBwdLds = kBwdN * 1024;
+// weight gradients: chunk-partial tiles of every parameter, then one ordered sum
+constexpr int kMaxChunks = 256, kMinChunk = 1024, kSub = 32;
+
+__device__ __forceinline__ int src_of(int step, int row, int k) {
+  switch (step) {
+    case F1: return k < kIn ? kW1 + row * kIn + k : (k == kIn ? kB1 + row : -1);
+    case F2: return kW2 + row * kHid + k;
+    case F3: return kW3 + row * kHid + k;
+    case F4: return row < 3 ? kW4 + row * kHid + k : -1;
+    case B4t: return k < 3 ? kW4 + k * kHid + row : -1;
+    case B3t: return kW3 + k * kHid + row;
+    default: return kW2 + k * kHid + row;
+  }
+}
+
+__global__ void __launch_bounds__(256) pack_kernel(const float* __restrict__ params, char* __restrict__ packed) {
+  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < kFrags * 64; t += gridDim.x * blockDim.x) {
+    const int frag = t >> 6, lane = t & 63;
+    int step = 0;
+    for (int s = 0; s < kSteps; ++s) if (frag >= step_of(s).frag0) step = s;
+    const Step st = step_of(step);
+    const int ksn = st.ks_acc + st.ks_nat, rel = frag - st.frag0, mt = rel / ksn, ks = rel % ksn;
+    const int row = mt * 32 + (lane & 31), h = lane >> 5;
+    const bool nat = ks >= st.ks_acc;
+    const bool fwd = step <= F4;
+    unsigned short out[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int k = nat ? 16 * (ks - st.ks_acc) + 8 * h + j : 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
+      const int src = src_of(step, row, k);
+      const float v = src >= 0 ? params[src] : 0.0f;
+      out[j] = fwd ? __builtin_bit_cast(unsigned short, (_Float16)v) : __builtin_bit_cast(unsigned short, (__bf16)v);
+    }
+    uint4 bits;
+    bits.x = out[0] | ((unsigned)out[1] << 16); bits.y = out[2] | ((unsigned)out[3] << 16);
+    bits.z = out[4] | ((unsigned)out[5] << 16); bits.w = out[6] | ((unsigned)out[7] << 16);
+    *reinterpret_cast<uint4*>(packed + (size_t)frag * 1024 + lane * 16) = bits;
+  }
+  if (blockIdx.x == 0) {
+    float* bias = reinterpret_cast<float*>(packed + kBiasOff);
+    for (int i = threadIdx.x; i < 512; i += blockDim.x)
+      bias[i] = i < 128 ? params[kB2 + i] : (i < 256 ? params[kB3 + i - 128] : (i < 259 ? params[kB4 + i - 256] : 0.0f));
+  }
+}
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+template <int KS, class V, class F>
+__device__ __forceinline__ f32x16 mtile(const char* a_base, int frag_off, const V (&b)[KS], f32x16 acc, F mfma) {
+  constexpr int D = KS < kAhead ? KS : kAhead;
+  V win[D];
+#pragma unroll
+  for (int i = 0; i < D; ++i) win[i] = *reinterpret_cast<const V*>(a_base + (frag_off + i) * 1024);
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    const V cur = win[ks % D];
+    if (ks + D < KS) win[ks % D] = *reinterpret_cast<const V*>(a_base + (frag_off + ks + D) * 1024);
+    acc = mfma(cur, b[ks], acc);
+  }
+  return acc;
+}
+struct Mfma16 {
+  __device__ __forceinline__ f32x16 operator()(f16x8 a, f16x8 b, f32x16 c) const { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
+struct MfmaBf {
+  __device__ __forceinline__ f32x16 operator()(bf16x8 a, bf16x8 b, f32x16 c) const { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+// every m-tile of STEP: acc = bias (or 0) + A B, then epi(m, acc)
+template <int STEP, int KS, class V, class F, class Epi>
+__device__ __forceinline__ void run(const char* wbase, const V (&b)[KS], const float* bias_lds, F mfma, Epi&& epi) {
+  constexpr Step st = step_of(STEP);
+  static_assert(KS == st.ks_acc + st.ks_nat, "k-steps");
+  const int half = (threadIdx.x & 63) >> 5;
+  static_for<st.mt>([&](auto mc) {
+    constexpr int m = decltype(mc)::value;
+    f32x16 acc;
+    if (bias_lds != nullptr) acc = bias_tile(bias_lds, 32 * m, half);
+    else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    }
+    acc = mtile<KS>(wbase, st.frag0 + m * KS, b, acc, mfma);
+    epi(m, acc);
+  });
+}
+
+// accumulator rows of register r in lane-half h: 8 (r >> 2) + 4 h + (r & 3): four runs of 4 consecutive features
+__device__ __forceinline__ void store_rows(__bf16* img, int64_t n, int m, int half, const f32x16& acc) {
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    bf16x4 v;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = (__bf16)acc[4 * g + r];
+    *reinterpret_cast<bf16x4*>(img + n * kHid + 32 * m + 8 * g + 4 * half) = v;
+  }
+}
+__device__ __forceinline__ void load_rows(const __bf16* img, int64_t n, int m, int half, float (&out)[16]) {
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const bf16x4 v = *reinterpret_cast<const bf16x4*>(img + n * kHid + 32 * m + 8 * g + 4 * half);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) out[4 * g + r] = (float)v[r];
+  }
+}
+
+struct Args {
+  const char* packed;
+  const float* x_code;     // [n,3] x' (the Fourier code's input)
+  const float* x;          // [n,3] x (x_c = x + dx)
+  const float* t;          // [n] t'
+  const float* d_dx;       // [n,3]
+  int64_t n, n_pad;
+  float* dx; float* xc;
+  __bf16* code; __bf16* h[3]; __bf16* dz[3];   // training images [n_pad][96] / [n_pad][128]
+};
+
+template <bool TRAIN>
+__global__ void __launch_bounds__(kThreads) fwd_kernel(const Args a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
+  for (int i = tid; i < kFwdN * 64; i += kThreads) reinterpret_cast<uint4*>(smem)[i] = reinterpret_cast<const uint4*>(a.packed)[i];
+  if (tid < 128) reinterpret_cast<uint4*>(smem + kFwdN * 1024)[tid] = reinterpret_cast<const uint4*>(a.packed + kBiasOff)[tid];
+  __syncthreads();
+  const char* wbase = smem + lane * 16;
+  const float* bias = reinterpret_cast<const float*>(smem + kFwdN * 1024);
+  const int64_t n_tiles = a.n_pad / kTile;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const int64_t n = (tile * kWaves + wave) * 32 + col;
+    const bool live = n < a.n;
+    const int64_t nc = live ? n : a.n - 1;
+    const float x0 = a.x_code[nc * 3 + 0], x1 = a.x_code[nc * 3 + 1], x2 = a.x_code[nc * 3 + 2], t = a.t[nc];
+    // layer-1 operand, natural order: column f = 16 ks + 8 half + j of [xcode (63) | tcode (21) | 1 | 0 ...]
+    f16x8 code[6];
+#pragma unroll
+    for (int ks = 0; ks < 6; ++ks) {
+      bf16x8 cb;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int f0 = 16 * ks + j, f1 = f0 + 8;       // this lane's column is f0 (half 0) or f1 (half 1)
+        auto value = [&](int f) -> float {
+          if (f < kPosDim) return feat_eval<kPosDim>(feat_spec<kPosDim>(f), x0, x1, x2);
+          if (f < kIn) {
+            const int c = f - kPosDim;
+            if (c == 0) return t;
+            return sincos_rev(t, (float)(1u << ((c - 1) >> 1)), ((c - 1) & 1) ? 0.25f : 0.0f);
+          }
+          return f == kIn ? 1.0f : 0.0f;
+        };
+        const float v = half ? value(f1) : value(f0);
+        code[ks][j] = (_Float16)v;
+        cb[j] = (__bf16)v;
+      }
+      if constexpr (TRAIN) *reinterpret_cast<bf16x8*>(a.code + n * kCodeLd + 16 * ks + 8 * half) = cb;
+    }
+    auto relu_epi = [&](f16x8* out, __bf16* img) {
+      return [=](int m, f32x16 acc) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.0f);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { out[2 * m][j] = (_Float16)acc[j]; out[2 * m + 1][j] = (_Float16)acc[8 + j]; }
+        if constexpr (TRAIN) store_rows(img, n, m, half, acc);
+      };
+    };
+    f16x8 h1[8], h2[8];
+    run<F1, 6>(wbase, code, nullptr, Mfma16{}, relu_epi(h1, a.h[0]));
+    run<F2, 8>(wbase, h1, bias, Mfma16{}, relu_epi(h2, a.h[1]));
+    run<F3, 8>(wbase, h2, bias + 128, Mfma16{}, relu_epi(h1, a.h[2]));
+    run<F4, 8>(wbase, h1, nullptr, Mfma16{}, [&](int, f32x16 acc) {
+      if (live && half == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float d = acc[c] + bias[256 + c];
+          a.dx[n * 3 + c] = d;
+          a.xc[n * 3 + c] = a.x[n * 3 + c] + d;
+        }
+      }
+    });
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) dgrad_kernel(const Args a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
+  for (int i = tid; i < kBwdLds / 16; i += kThreads)
+    reinterpret_cast<uint4*>(smem)[i] = reinterpret_cast<const uint4*>(a.packed + kBwd0 * 1024)[i];
+  __syncthreads();
+  const char* wbase = smem + lane * 16 - kBwd0 * 1024;
+  const int64_t n_tiles = a.n_pad / kTile;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const int64_t n = (tile * kWaves + wave) * 32 + col;
+    const bool live = n < a.n;
+    bf16x8 small[1];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) small[0][j] = (__bf16)0.0f;
+    if (live && half == 0) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) small[0][c] = (__bf16)a.d_dx[n * 3 + c];
+    }
+    // d h_k -> dz_k = d h_k [h_k > 0] (stored activations), bf16 operand of the next transposed layer + image for the wgrad
+    auto mask_epi = [&](bf16x8* out, const __bf16* h, __bf16* dz) {
+      return [=](int m, f32x16 acc) {
+        float hv[16];
+        load_rows(h, n, m, half, hv);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = hv[r] > 0.0f ? acc[r] : 0.0f;
+        acc_to_operand(acc, out[2 * m], out[2 * m + 1]);
+        store_rows(dz, n, m, half, acc);
+      };
+    };
+    bf16x8 g3[8], g2[8], g1[8];
+    run<B4t, 1>(wbase, small, nullptr, MfmaBf{}, mask_epi(g3, a.h[2], a.dz[2]));
+    run<B3t, 8>(wbase, g3, nullptr, MfmaBf{}, mask_epi(g2, a.h[1], a.dz[1]));
+    run<B2t, 8>(wbase, g2, nullptr, MfmaBf{}, mask_epi(g1, a.h[0], a.dz[0]));
+    (void)g1;
+  }
+}
+
+// Weight gradients of one layer over one chunk of samples: dW[o][i] = sum_n A[n][o] B[n][i], db[o] = sum_n A[n][o].  Thread
+// (ob, ib) owns an 8 x 8 block; samples are staged 32 at a time in LDS as fp32.  The chunk's tile is STORED into its slab row.
+struct WgradArgs {
+  const __bf16* code; const __bf16* h[3]; const __bf16* dz[3];
+  const float* d_dx;
+  int64_t n, chunk;
+  float* slab;             // [chunks][kParams]
+};
+template <int A_LD, int B_LD, int O, int I, bool A_F32>
+__device__ __forceinline__ void wgrad_layer(const void* A, const __bf16* B, int64_t n0, int64_t n1, int w_off, int b_off, float* out, char* smem) {
+  float* As = reinterpret_cast<float*>(smem);                 // [kSub][A_LD]
+  float* Bs = As + kSub * A_LD;                               // [kSub][B_LD]
+  constexpr int OB = (O + 7) / 8, IB = (I + 7) / 8;
+  const int tid = threadIdx.x;
+  const bool owner = tid < OB * IB;
+  const int ob = tid / IB, ib = tid % IB;
+  float acc[8][8], bsum[8];
+#pragma unroll
+  for (int p = 0; p < 8; ++p) {
+    bsum[p] = 0.0f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) acc[p][q] = 0.0f;
+  }
+  for (int64_t s0 = n0; s0 < n1; s0 += kSub) {
+    const int cnt = (int)(n1 - s0 < kSub ? n1 - s0 : kSub);
+    __syncthreads();
+    for (int e = tid; e < kSub * A_LD; e += blockDim.x) {
+      const int s = e / A_LD, c = e % A_LD;
+      float v = 0.0f;
+      if (s < cnt && c < O) v = A_F32 ? static_cast<const float*>(A)[(s0 + s) * 3 + c] : (float)static_cast<const __bf16*>(A)[(s0 + s) * A_LD + c];
+      As[e] = v;
+    }
+    for (int e = tid; e < kSub * B_LD; e += blockDim.x) {
+      const int s = e / B_LD;
+      Bs[e] = s < cnt ? (float)B[(s0 + s) * B_LD + e % B_LD] : 0.0f;
+    }
+    __syncthreads();
+    if (owner) {
+      for (int s = 0; s < kSub; ++s) {
+        const f32x4 a0 = *reinterpret_cast<const f32x4*>(As + s * A_LD + 8 * ob), a1 = *reinterpret_cast<const f32x4*>(As + s * A_LD + 8 * ob + 4);
+        const f32x4 b0 = *reinterpret_cast<const f32x4*>(Bs + s * B_LD + 8 * ib), b1 = *reinterpret_cast<const f32x4*>(Bs + s * B_LD + 8 * ib + 4);
+        const float av[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+        const float bv[8] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+          bsum[p] += av[p];
+#pragma unroll
+          for (int q = 0; q < 8; ++q) acc[p][q] = __builtin_fmaf(av[p], bv[q], acc[p][q]);
+        }
+      }
+    }
+  }
+  if (!owner) return;
+#pragma unroll
+  for (int p = 0; p < 8; ++p) {
+    const int o = 8 * ob + p;
+    if (o >= O) continue;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int i = 8 * ib + q;
+      if (i < I) out[w_off + o * I + i] = acc[p][q];
+    }
+    if (ib == 0) out[b_off + o] = bsum[p];
+  }
+}
+
+// blockIdx.x: chunk, blockIdx.y: layer.  A_LD >= 8 * ceil(O / 8) (the owner reads 8 rows of A).
+__global__ void __launch_bounds__(256) wgrad_kernel(const WgradArgs a) {
+  __shared__ __attribute__((aligned(16))) char smem[kSub * (kHid + kHid) * 4];
+  const int64_t n0 = blockIdx.x * a.chunk;
+  const int64_t n1 = n0 + a.chunk < a.n ? n0 + a.chunk : a.n;
+  float* out = a.slab + (size_t)blockIdx.x * kParams;
+  switch (blockIdx.y) {
+    case 0: wgrad_layer<kHid, kCodeLd, kHid, kIn, false>(a.dz[0], a.code, n0, n1, kW1, kB1, out, smem); break;
+    case 1: wgrad_layer<kHid, kHid, kHid, kHid, false>(a.dz[1], a.h[0], n0, n1, kW2, kB2, out, smem); break;
+    case 2: wgrad_layer<kHid, kHid, kHid, kHid, false>(a.dz[2], a.h[1], n0, n1, kW3, kB3, out, smem); break;
+    default: wgrad_layer<8, kHid, 3, kHid, true>(a.d_dx, a.h[2], n0, n1, kW4, kB4, out, smem); break;
+  }
+}
+
+// grads[p] += sum over chunks, in chunk order
+__global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* __restrict__ slab, int chunks, float* __restrict__ grads) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= kParams) return;
+  float s = 0.0f;
+  for (int c = 0; c < chunks; ++c) s += slab[(size_t)c * kParams + p];
+  grads[p] += s;
+}
+
+struct Layout {
+  int64_t n_pad;
+  size_t code, h[3], dz[3], slab, total;
+};
+static Layout layout(int64_t n) {
+  Layout s{};
+  s.n_pad = (n + kTile - 1) / kTile * kTile;
+  const size_t np = (size_t)s.n_pad;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
+  s.code = take(np * kCodeLd * 2);
+  for (int k = 0; k < 3; ++k) s.h[k] = take(np * kHid * 2);
+  for (int k = 0; k < 3; ++k) s.dz[k] = take(np * kHid * 2);
+  s.slab = take((size_t)kMaxChunks * kParams * 4);
+  s.total = o;
+  return s;
+}
+static Args args_of(const void* packed, void* ws, int64_t n) {
+  const Layout l = layout(n);
+  char* w = static_cast<char*>(ws);
+  Args a{};
+  a.packed = static_cast<const char*>(packed);
+  a.n = n; a.n_pad = l.n_pad;
+  a.code = reinterpret_cast<__bf16*>(w + l.code);
+  for (int k = 0; k < 3; ++k) { a.h[k] = reinterpret_cast<__bf16*>(w + l.h[k]); a.dz[k] = reinterpret_cast<__bf16*>(w + l.dz[k]); }
+  return a;
+}
+static int grid_for(int64_t tiles) {
+  int n_cu = 0;
+  if (device_cu_count(&n_cu) != NERF_OK) return -1;
+  return (int)(tiles < n_cu ? tiles : n_cu);       // one workgroup per CU (LDS)
+}
+
+}  // namespace p3
+}  // namespace nerf
+
+using namespace nerf;
+
+extern "C" int64_t nerf_p3_deform_param_count(void) { return p3::kParams; }
+extern "C" size_t nerf_p3_deform_packed_bytes(void) { return p3::kPackBytes; }
+extern "C" size_t nerf_p3_deform_workspace_bytes(int64_t n) { return n > 0 ? p3::layout(n).total : 0; }
+
+extern "C" int nerf_p3_deform_pack(const float* params_f32, void* packed, nerf_stream_t stream) {
+  NERF_REQUIRE(params_f32 && packed && ((uintptr_t)packed & 255) == 0, "nerf_p3_deform_pack: bad pointer");
+  hipLaunchKernelGGL(p3::pack_kernel, dim3(48), dim3(256), 0, as_stream(stream), params_f32, static_cast<char*>(packed));
+  return check_launch("nerf_p3_deform_pack");
+}
+
+extern "C" int nerf_p3_deform_fwd(const void* packed, void* workspace, const float* x_code, const float* pts, const float* t_deform,
+                                  int64_t n, float* delta_x, float* x_canonical, int train, nerf_stream_t stream) {
+  NERF_REQUIRE(n >= 0, "nerf_p3_deform_fwd: n=%lld", (long long)n);
+  if (n == 0) return NERF_OK;
+  NERF_REQUIRE(packed && pts && t_deform && delta_x && x_canonical, "nerf_p3_deform_fwd: NULL pointer");
+  NERF_REQUIRE(!train || (workspace && ((uintptr_t)workspace & 255) == 0), "nerf_p3_deform_fwd: training needs an aligned workspace");
+  p3::Args a{};
+  if (train) a = p3::args_of(packed, workspace, n);
+  a.packed = static_cast<const char*>(packed);
+  a.n = n; a.n_pad = (n + p3::kTile - 1) / p3::kTile * p3::kTile;
+  a.x_code = x_code ? x_code : pts; a.x = pts; a.t = t_deform; a.dx = delta_x; a.xc = x_canonical;
+  const int grid = p3::grid_for(a.n_pad / p3::kTile);
+  if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_p3_deform_fwd: cannot query device");
+  const void* kernel = train ? (const void*)p3::fwd_kernel<true> : (const void*)p3::fwd_kernel<false>;
+  if (int rc = ensure_dynamic_lds(kernel, p3::kFwdLds, "nerf_p3_deform_fwd"); rc != NERF_OK) return rc;
+  if (train) hipLaunchKernelGGL(p3::fwd_kernel<true>, dim3(grid), dim3(p3::kThreads), p3::kFwdLds, as_stream(stream), a);
+  else hipLaunchKernelGGL(p3::fwd_kernel<false>, dim3(grid), dim3(p3::kThreads), p3::kFwdLds, as_stream(stream), a);
+  return check_launch("nerf_p3_deform_fwd");
+}
+
+extern "C" int nerf_p3_deform_bwd(const void* packed, void* workspace, const float* d_delta_x, int64_t n, float* grads_f32,
+                                  nerf_stream_t stream) {
+  NERF_REQUIRE(n >= 0 && grads_f32, "nerf_p3_deform_bwd: bad arguments");
+  if (n == 0) return NERF_OK;
+  NERF_REQUIRE(packed && workspace && d_delta_x && ((uintptr_t)workspace & 255) == 0, "nerf_p3_deform_bwd: bad pointer");
+  p3::Args a = p3::args_of(packed, workspace, n);
+  a.d_dx = d_delta_x;
+  const int grid = p3::grid_for(a.n_pad / p3::kTile);
+  if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_p3_deform_bwd: cannot query device");
+  if (int rc = ensure_dynamic_lds((const void*)p3::dgrad_kernel, p3::kBwdLds, "nerf_p3_deform_bwd"); rc != NERF_OK) return rc;
+  hipLaunchKernelGGL(p3::dgrad_kernel, dim3(grid), dim3(p3::kThreads), p3::kBwdLds, as_stream(stream), a);
+  if (int rc = check_launch("nerf_p3_deform_bwd (dgrad)"); rc != NERF_OK) return rc;
+  // chunks of at least kMinChunk samples (multiples of kSub), at most kMaxChunks of them
+  int64_t chunks = (n + p3::kMinChunk - 1) / p3::kMinChunk;
+  if (chunks > p3::kMaxChunks) chunks = p3::kMaxChunks;
+  int64_t chunk = (n + chunks - 1) / chunks;
+  chunk = (chunk + p3::kSub - 1) / p3::kSub * p3::kSub;
+  chunks = (n + chunk - 1) / chunk;
+  const p3::Layout l = p3::layout(n);
+  p3::WgradArgs w{};
+  w.code = a.code; w.d_dx = d_delta_x; w.n = n; w.chunk = chunk;
+  for (int k = 0; k < 3; ++k) { w.h[k] = a.h[k]; w.dz[k] = a.dz[k]; }
+  w.slab = reinterpret_cast<float*>(static_cast<char*>(workspace) + l.slab);
+  hipLaunchKernelGGL(p3::wgrad_kernel, dim3((unsigned)chunks, 4), dim3(256), 0, as_stream(stream), w);
+  if (int rc = check_launch("nerf_p3_deform_bwd (wgrad)"); rc != NERF_OK) return rc;
+  hipLaunchKernelGGL(p3::wgrad_reduce_kernel, dim3((p3::kParams + 255) / 256), dim3(256), 0, as_stream(stream), w.slab, (int)chunks, grads_f32);
+  return check_launch("nerf_p3_deform_bwd (reduce)");
+}

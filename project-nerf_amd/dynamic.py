@@ -5,7 +5,8 @@ time anchors, best-on-validation checkpoints, and the loss terms of the referenc
 (``part4_regularisers``: displacement magnitude, total variation on the deformation grids and on the canonical
 grid, temporal smoothness, unsupervised consistency, tri-grid anchor; run.py:1832-1938) with its YAML keys,
 defaults and every-n-steps schedule.  Part 4 at the reference's example shapes trains on part4.DualHashEngine (fused HIP
-chains, no torch autograd / optimiser / library GEMM in the loop); other shapes and Part 3 compose the field from the
+chains, no torch autograd / optimiser / library GEMM in the loop); Part 3 with a hash-grid canonical field and `engine: true`
+trains on part3.Part3InstantEngine; other shapes and Part 3 by default compose the field from the
 stand-alone operators (hash encodings and Fourier codes in HIP, the small MLPs as library GEMMs) under torch autograd."""
 import os
 
@@ -192,11 +193,15 @@ def run_dynamic(cfg, args):
     bg = torch.ones(3, device=device) if white_bkgd else torch.zeros(3, device=device)
     eval_bg = bg                                    # validation / test always composite onto the dataset's background
 
+    engine3 = []                                    # the Part 3 engine once it trains: validation and test renders go through it
+
     def render_band(o, d, t):
         rows, width = o.shape[0], o.shape[1]
         o, d = o.reshape(-1, 3), d.reshape(-1, 3)
         if o.shape[0] == 0:
             return o.new_zeros(0, width, 3)
+        if engine3:
+            return engine3[0].render_image(o.contiguous(), d.contiguous(), t.reshape(1, 1), render_n, chunk=chunk, bg=eval_bg).view(rows, width, 3)
         pred = torch.cat([render_rays(model, o[i:i + chunk], d[i:i + chunk], near, far, render_n, False, density_grid=grid,
                                       times=t.expand(min(chunk, o.shape[0] - i), 1), bg_color=eval_bg)[0]
                           for i in range(0, o.shape[0], chunk)], 0)
@@ -230,9 +235,61 @@ def run_dynamic(cfg, args):
     from . import part4 as p4
     use_engine = (not args.eval_only and not part3 and cfg.get("engine", True) and grid is not None
                   and getattr(model, "_p4_fused", False) and p4.supported(cfg) is None)
+    from . import part3 as p3
+    # Part 3 with a hash-grid canonical field on part3.Part3InstantEngine: only when the YAML asks for it (`engine: true`)
+    use_engine3 = (not args.eval_only and part3 and bool(cfg.get("engine", False)) and grid is not None and p3.supported(cfg) is None)
     if world > 1 and not args.eval_only:
         say(f">>> data parallel: {world} ranks x {local} rays (global batch {local * world}); clip after the all-reduce")
-    if use_engine:
+    if use_engine3:
+        # fused deformation chain + Part 4's canonical chain, fused compositing + loss + regulariser + backward, TV + ONE global-norm
+        # clip + AdamW as one group (no torch autograd / optimiser / library GEMM in the loop); weights are copied into the
+        # NeuralField for checkpoints (reference state-dict keys)
+        from . import ops
+        eng = p3.Part3InstantEngine({**cfg, "train_iters": iters, "learning_rate": lr, "grid_resolution": grid.resolution,
+                                     "grid_threshold": grid.threshold, "grid_bound": grid.bound}, device=str(device),
+                                    seed=int(cfg.get("seed", 0) or 0), world_size=world)
+        eng.load_from_model(model)
+        with torch.no_grad():
+            eng.grid.copy_(grid.grid)
+            eng.binary_grid.copy_(grid.binary_grid)
+        parallel.broadcast_([eng.table, eng.net, eng.grid, eng.binary_grid])
+        eng.repack()
+        sync_async = parallel.allreduce_sum_async if world > 1 else None
+        if world > 1:
+            say(">>> Part 3 engine: replicated optimiser (flat all-reduce of the gradients, every rank steps every parameter)")
+        engine3.append(eng)
+        pixels = train_set.H * train_set.W
+        t_lo, t_hi = float(train_set.times.min()), float(train_set.times.max())
+
+        def sync():
+            eng.copy_to_model(model)
+            grid.grid, grid.binary_grid = eng.grid.clone(), eng.binary_grid.clone()
+
+        active = 1.0
+        for step in range(1, iters + 1):
+            idx = torch.randint(0, len(train_set) * pixels, (local * world,), device=device)[lo:lo + local].contiguous()
+            step_bg = torch.rand(3, device=device) if step >= random_bg_start else eval_bg
+            o, d, target, _ = ops.gather_batch(train_set.rgba, train_set.poses, idx, train_set.focal, train_set.scene_scale, bg=step_bg)
+            t = train_set.times[idx // pixels].view(-1, 1)
+            loss_rgb = eng.train_step(o, d, target, t, n_samples, first_ray=lo, bg=step_bg, sync_grads_async=sync_async,
+                                      probes=p3.probe_draws(cfg, step, device))
+            # run.py:1191-1222: every 16 / 64 / 256 steps the union over 16 (later 8) times across the sequence, no decay
+            interval = 16 if step < iters * 0.1 else (64 if step < iters * 0.5 else 256)
+            if grid.should_update(step, interval, warm):
+                active = eng.update_grid(torch.linspace(t_lo, t_hi, 16 if step < 1000 else 8).tolist())
+            if step % log_every == 0:
+                loss_val = parallel.mean_over_ranks(loss_rgb).item()
+                say(f">>> Step {step}/{iters} | Loss {loss_val:.6f} | PSNR {compute_psnr(loss_val):.2f} dB | LR {eng.lr():.6f}"
+                    f" | Skip: {(1 - active) * 100:.1f}%")
+            if step % cfg.get("val_every", 500) == 0 or step == iters:
+                sync()
+                v = evaluate(range(min(len(test_set), cfg.get("val_views", 4))))
+                say(f"    [Validation] PSNR: {v:.2f} dB")
+                if v > best and main_rank:
+                    best = v
+                    save_best(step, best)
+        sync()
+    elif use_engine:
         # The example shapes train on the flat-parameter engine (part4.DualHashEngine: fused chains, fused compositing + loss
         # + regulariser + backward, one global-norm clip + AdamW with the reference's group rates, no torch autograd / optimiser
         # / library GEMM in the loop); weights and occupancy grid are copied into the NeuralField / DensityGrid for

@@ -1,0 +1,421 @@
+"""Part 3 (D-NeRF with an MLP deformation field) on a hash-grid canonical field -- ``canonical_type: instant`` -- as a
+flat-parameter training engine on fused HIP chains: the loop body of reference run_part3 (run.py:1040-1222) with
+NeuralField('part3') (src/core.py:79-146, 233-281).
+
+    batch -> compaction -> t', x' (+ noise) -> deformation chain (csrc/p3deform.hip: Fourier codes of x', t' -> 128 -> 128
+    -> 128 -> 3, x_c = x + dx) -> canonical hash encoding at x_c -> canonical chain (Part 4's, csrc/p4mlp.hip: the same
+    InstantNeRFDecoder on [hash (32) | time code (21)]) -> compositing + MSE + displacement regulariser + backward (one
+    kernel) -> canonical chain bwd + wgrad -> hash input gradient + counted scatter -> deformation chain bwd + wgrad
+    -> [temporal / consistency probes through the same kernels] -> [all-reduce] -> TV on the canonical table + ONE
+    global-norm clip + AdamW (one group, cosine schedule).
+
+No torch autograd, torch.optim or library GEMM in the loop.  The canonical decoder lives at Part 4's offsets of a Part 4
+parameter vector (its deformation slots stay zero and unused), so Part 4's kernels run unchanged through their existing
+entry points; the deformation MLP follows it in the same flat vector.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional
+
+import torch
+
+from . import _lib, ops
+from . import part4 as p4
+
+Tensor = torch.Tensor
+P = lambda t: None if t is None else t.data_ptr()
+
+DEFORM0 = p4.N_PARAMS                                 # the deformation MLP follows the Part 4 vector
+W1, B1, W2, B2, W3, B3, W4, B4, N_DEFORM = 0, 10752, 10880, 27264, 27392, 43776, 43904, 44288, 44291
+N_PARAMS = DEFORM0 + N_DEFORM
+TABLE_KEY = "canonical_repr.encoding.params"
+# (state-dict key, offset into the flat network vector, shape)
+MODULE_SLICES = (
+    ("decoder.sigma_net.params", p4.S1, (64 * 64 + 16 * 64,)),
+    ("decoder.color_net.params", p4.C1, (64 * 48 + 64 * 64 + 16 * 64,)),
+    ("deform_net.net.0.weight", DEFORM0 + W1, (128, 84)), ("deform_net.net.0.bias", DEFORM0 + B1, (128,)),
+    ("deform_net.net.2.weight", DEFORM0 + W2, (128, 128)), ("deform_net.net.2.bias", DEFORM0 + B2, (128,)),
+    ("deform_net.net.4.weight", DEFORM0 + W3, (128, 128)), ("deform_net.net.4.bias", DEFORM0 + B3, (128,)),
+    ("deform_net.net.6.weight", DEFORM0 + W4, (3, 128)), ("deform_net.net.6.bias", DEFORM0 + B4, (3,)),
+)
+
+
+def supported(cfg: dict) -> Optional[str]:
+    """None if the fused chains are compiled for this configuration, else the reason they are not.  Table size, base
+    resolution, level scale and bound are free."""
+    if cfg.get("mode") != "part3":
+        return f"mode={cfg.get('mode')} (compiled: part3)"
+    if cfg.get("canonical_type", "nerf") != "instant":
+        return f"canonical_type={cfg.get('canonical_type', 'nerf')} (compiled: instant)"
+    if cfg.get("direct_time_conditioning", False):
+        return "direct_time_conditioning=True (compiled: False)"
+    want = {"L_embed": (10, 0), "L_embed_time": (10, 10), "L_embed_dir": (4, 4), "deform_hidden_dim": (128, 128),
+            "deform_num_layers": (4, 4), "hidden_dim": (64, 64), "n_levels": (16, 16), "n_features_per_level": (2, 2)}
+    for key, (compiled, default) in want.items():
+        if cfg.get(key, default) != compiled:
+            return f"{key}={cfg.get(key, default)} (compiled: {compiled})"
+    if not cfg.get("use_positional_encoding", True):
+        return "use_positional_encoding=False (compiled: True)"
+    return None
+
+
+def _check_count():
+    n = _lib.load().nerf_p3_deform_param_count()
+    if n != N_DEFORM:
+        raise _lib.NerfHipError(f"libnerf_hip.so reports {n} Part 3 deformation parameters, this binding expects {N_DEFORM}")
+
+
+# --------------------------------------------------------------------------------------------------- deformation chain
+def deform_pack(params: Tensor, packed: Optional[Tensor] = None) -> Tensor:
+    """fragment image of the deformation MLP ``params`` [44291] (deform_net.net.{0,2,4,6}.{weight,bias} concatenated)"""
+    lib = _lib.load()
+    _check_count()
+    if params.numel() != N_DEFORM or not params.is_contiguous():
+        raise ValueError(f"Part 3 deformation MLP: {N_DEFORM} contiguous parameters expected, got {params.numel()}")
+    if packed is None:
+        packed = torch.empty(lib.nerf_p3_deform_packed_bytes(), dtype=torch.uint8, device=params.device)
+    _lib.check(lib.nerf_p3_deform_pack(P(params), P(packed), ops._stream()), "nerf_p3_deform_pack")
+    return packed
+
+
+def deform_workspace_bytes(n: int) -> int:
+    return max(_lib.load().nerf_p3_deform_workspace_bytes(n), 256)
+
+
+def deform_fwd(packed: Tensor, pts: Tensor, t: Tensor, x_code: Optional[Tensor] = None, workspace: Optional[Tensor] = None):
+    """(delta_x [n,3], x_c [n,3]) of the deformation MLP at the codes of ``x_code`` (default pts) and t [n]; x_c = pts + delta_x.
+    ``workspace`` (>= deform_workspace_bytes(n) bytes): training forward, keeps what deform_bwd reads."""
+    lib = _lib.load()
+    pts = ops._dev(pts, "pts")
+    t = ops._dev(t.reshape(-1), "t")
+    n = pts.shape[0]
+    dx, xc = torch.empty(n, 3, device=pts.device), torch.empty(n, 3, device=pts.device)
+    if workspace is not None and workspace.numel() < deform_workspace_bytes(n):
+        raise ValueError("deform_fwd: workspace too small")
+    _lib.check(lib.nerf_p3_deform_fwd(P(packed), P(workspace), P(None if x_code is None else ops._dev(x_code, "x_code")), P(pts), P(t), n,
+                                      P(dx), P(xc), 1 if workspace is not None else 0, ops._stream()), "nerf_p3_deform_fwd")
+    return dx, xc
+
+
+def deform_bwd(packed: Tensor, workspace: Tensor, d_dx: Tensor, grads: Tensor) -> None:
+    """ADDS the weight and bias gradients of the last training deform_fwd on ``workspace`` into ``grads`` [44291]"""
+    lib = _lib.load()
+    d_dx = ops._dev(d_dx, "d_dx")
+    if grads.numel() != N_DEFORM or not grads.is_contiguous():
+        raise ValueError("deform_bwd: grads must be a contiguous [44291] tensor")
+    _lib.check(lib.nerf_p3_deform_bwd(P(packed), P(workspace), P(d_dx), d_dx.shape[0], P(grads), ops._stream()), "nerf_p3_deform_bwd")
+
+
+def probe_draws(cfg: dict, step: int, device, generator=None) -> Optional[Dict[str, Tensor]]:
+    """The probe points dynamic.part3_regularisers draws on this step (the same keys, defaults, counts and draw order), or
+    None on a step that evaluates neither term."""
+    warm = cfg.get("grid_warmup_iters", 256)
+    bound = float(cfg.get("scene_bound", 1.2))
+    rand = lambda *shape: torch.rand(*shape, device=device, generator=generator)
+    probes = {}
+    if cfg.get("use_temporal_smooth", True) and step > warm and step % 2 == 0:
+        eps, n = float(cfg.get("temporal_epsilon", 0.02)), int(cfg.get("temporal_n_samples", 256))
+        probes["temporal_x"] = (rand(n, 3) * 2 - 1) * bound
+        probes["temporal_t"] = rand(n, 1) * (1.0 - eps)
+    if cfg.get("use_unsupervised_consistency", False) and step > warm and step % 4 == 0:
+        n = min(int(cfg.get("unsup_n_samples", 512)), 512)
+        probes["unsup_t"] = rand(n, 1)
+        probes["unsup_x"] = (rand(n, 3) * 2 - 1) * bound
+    return probes or None
+
+
+# --------------------------------------------------------------------------------------------------- engine
+class Part3InstantEngine:
+    """Flat-parameter training / rendering engine of mode part3 with canonical_type instant (module docstring)."""
+
+    def __init__(self, cfg: dict, device: str = "cuda", seed: int = 0, world_size: int = 1):
+        why = supported(cfg)
+        if why is not None:
+            raise NotImplementedError(f"the fused Part 3 chains are not compiled for {why}")
+        _check_count()
+        p4._check_count()
+        self.cfg = dict(cfg)
+        self.device = torch.device(device)
+        self.seed, self.world_size = int(seed), int(world_size)
+        self.bound = float(cfg.get("scene_bound", 1.0))                 # the canonical grid's bound (src/core.py:118)
+        self.grid_bound = float(cfg.get("grid_bound", cfg.get("scene_bound", 1.5)))
+        self.levels = ops.HashLevelTable(cfg.get("n_levels", 16), cfg.get("log2_hashmap_size", 19), cfg.get("base_resolution", 16),
+                                         cfg.get("per_level_scale", 1.5))
+        n_tab = self.levels.entries * 2
+        g = torch.Generator().manual_seed(seed)
+        self.table = ((torch.rand(n_tab, generator=g) * 2 - 1) * 1e-4).to(self.device)
+        self.table_h = torch.empty(n_tab, dtype=torch.float16, device=self.device)
+        self.g_table = torch.zeros(n_tab, device=self.device)
+        self.net = torch.zeros(N_PARAMS, device=self.device)
+        self._g_net_scalars = torch.zeros(N_PARAMS + 4, device=self.device)
+        self.g_net = self._g_net_scalars[:N_PARAMS]
+        self.state = {"table": (torch.zeros_like(self.table), torch.zeros_like(self.table)),
+                      "net": (torch.zeros_like(self.net), torch.zeros_like(self.net))}
+        self.packed_c = torch.empty(_lib.load().nerf_p4_packed_bytes(), dtype=torch.uint8, device=self.device)
+        self.packed_d = torch.empty(_lib.load().nerf_p3_deform_packed_bytes(), dtype=torch.uint8, device=self.device)
+        self.near, self.far = float(cfg.get("near", 2.0)), float(cfg.get("far", 6.0))
+        self.lr0, self.eta_min = float(cfg.get("learning_rate", 5e-4)), float(cfg.get("eta_min", 1e-4))
+        self.t_max = int(cfg.get("train_iters", 20000))
+        self.wd = float(cfg.get("weight_decay", 1e-5))
+        self.max_norm = float(cfg.get("max_grad_norm", 1.0))
+        self.reg_weight = float(cfg.get("deformation_reg_weight", 1e-4))
+        self.tv = float(cfg.get("tv_loss_weight", 1e-6)) if cfg.get("use_tv_loss", True) else 0.0
+        noisy = bool(cfg.get("use_coord_noise", False))
+        self.std_x = float(cfg.get("coord_noise_std", 0.005)) if noisy else 0.0
+        self.std_t = float(cfg.get("time_noise_std", 0.02)) if noisy else 0.0
+        self.bg = (torch.ones(3) if cfg.get("white_bkgd", True) else torch.zeros(3)).to(self.device)
+        res = int(cfg.get("grid_resolution", 128))
+        self.grid_threshold = float(cfg.get("grid_threshold", 0.01))
+        self.grid = torch.zeros(res, res, res, device=self.device)
+        self.binary_grid = torch.ones(res, res, res, dtype=torch.bool, device=self.device)
+        self.step_count = 0
+        self._normsq_ws = ops.normsq_ws(self.device)
+        # two-bit signs of the TV term; zeroed once (a one-table call never reads a byte pass 1 left unwritten)
+        self._tv_codes = torch.zeros((n_tab + 3) // 4, dtype=torch.uint8, device=self.device)
+        self._ws: Dict[str, Tensor] = {}
+        self._counter = 0
+        self.last_terms: Dict[str, Tensor] = {}
+        self.repack()
+
+    # -- parameters ------------------------------------------------------------------------------------------
+    @property
+    def deform_params(self) -> Tensor:
+        return self.net[DEFORM0:]
+
+    @property
+    def g_deform(self) -> Tensor:
+        return self.g_net[DEFORM0:]
+
+    def repack(self) -> None:
+        p4.pack(self.net[:p4.N_PARAMS], self.packed_c)
+        deform_pack(self.deform_params, self.packed_d)
+        ops.f32_to_f16(self.table, self.table_h)
+
+    @staticmethod
+    def slice_table():
+        """(key, 'net' or 'table', offset, shape) of every module parameter inside the engine's flat buffers"""
+        return [(k, "net", off, shape) for k, off, shape in MODULE_SLICES] + [(TABLE_KEY, "table", 0, None)]
+
+    def load_from_model(self, model) -> None:
+        sd = dict(model.named_parameters())
+        with torch.no_grad():
+            self.net.zero_()
+            for key, off, shape in MODULE_SLICES:
+                cnt = math.prod(shape)
+                self.net[off:off + cnt].copy_(sd[key].reshape(-1))
+            self.table.copy_(sd[TABLE_KEY].reshape(-1))
+        self.repack()
+
+    def copy_to_model(self, model) -> None:
+        sd = dict(model.named_parameters())
+        with torch.no_grad():
+            for key, off, shape in MODULE_SLICES:
+                cnt = math.prod(shape)
+                sd[key].copy_(self.net[off:off + cnt].view(sd[key].shape))
+            sd[TABLE_KEY].copy_(self.table.view(sd[TABLE_KEY].shape))
+
+    def lr(self) -> float:
+        """CosineAnnealingLR of the one group (run.py:1016-1021)"""
+        return self.eta_min + (self.lr0 - self.eta_min) * (1 + math.cos(math.pi * self.step_count / self.t_max)) / 2
+
+    def _buf(self, which: str, need: int) -> Tensor:
+        """grow-only buffers: the active-point count changes almost every step"""
+        buf = self._ws.get(which)
+        if buf is None or buf.numel() < need:
+            self._ws.pop(which, None)
+            buf = self._ws[which] = torch.empty(int(need * 1.25) + 256, dtype=torch.uint8, device=self.device)
+        return buf
+
+    def _p4_ws(self, n: int, which: str = "batch") -> p4.Workspace:
+        return p4.Workspace(n, self.device, buf=self._buf("p4_" + which, p4.Workspace.bytes(n)))
+
+    def _deform_ws(self, n: int, which: str = "batch") -> Tensor:
+        return self._buf("p3_" + which, deform_workspace_bytes(n))
+
+    def _hash_scratch(self, n: int) -> Tensor:
+        return self._buf("hash", ops.hash_encode_bwd_workspace_bytes(n, self.levels.n_levels))
+
+    # -- field -----------------------------------------------------------------------------------------------
+    def _canonical(self, xc: Tensor, t: Tensor, dirs: Tensor, ws: p4.Workspace, train: bool):
+        lib = _lib.load()
+        n = xc.shape[0]
+        ops.hash_encode_fwd_nat(xc, self.table_h.view(-1, 2), self.levels, self.bound, ws.nat(3), fp16=True)
+        rgb, sigma = torch.empty(n, 3, device=self.device), torch.empty(n, device=self.device)
+        _lib.check(lib.nerf_p4_canon_fwd(P(self.packed_c), P(ws.buf), P(t), P(dirs), n, P(rgb), P(sigma), 1 if train else 0, ops._stream()),
+                   "nerf_p4_canon_fwd")
+        return rgb, sigma
+
+    @torch.no_grad()
+    def field(self, pts: Tensor, dirs: Tensor, t: Tensor):
+        """(rgb [n,3], sigma [n], delta_x [n,3]) at points with per-point times, evaluation mode (no noise)"""
+        pts, dirs, t = pts.contiguous(), dirs.contiguous(), t.reshape(-1).contiguous()
+        n = pts.shape[0]
+        if n == 0:
+            return pts.new_zeros(0, 3), pts.new_zeros(0), pts.new_zeros(0, 3)
+        dx, xc = deform_fwd(self.packed_d, pts, t)
+        rgb, sigma = self._canonical(xc, t, dirs, self._p4_ws(n, "eval"), False)
+        return rgb, sigma, dx
+
+    def prepare_batch(self, rays_o: Tensor, rays_d: Tensor, n_samples: int, first_ray: int = 0):
+        self._counter += 1
+        return ops.sample_compact_async(rays_o, rays_d, self.near, self.far, n_samples, self.binary_grid, self.grid_bound,
+                                        jitter=(self.seed, self._counter), first_ray=first_ray), self._counter
+
+    def compute_gradients(self, rays_o: Tensor, rays_d: Tensor, target: Tensor, times: Tensor, n_samples: int, prepared=None,
+                          first_ray: int = 0, bg: Optional[Tensor] = None, sync_grads_async=None, probes=None) -> Tensor:
+        """Forward + backward of one batch: fills g_net / g_table with the gradient of MSE + deformation_reg_weight *
+        mean(mean_delta_x^2) (+ the probe terms) of the LOCAL rays and returns the RGB loss.  ``sync_grads_async(view)``:
+        data-parallel hook (a summing all-reduce; apply_gradients divides by the world size)."""
+        lib = _lib.load()
+        R = rays_o.shape[0]
+        prepared, counter = prepared if prepared is not None else self.prepare_batch(rays_o, rays_d, n_samples, first_ray)
+        z, slots, pts, dirs = prepared.get()
+        n = pts.shape[0]
+        bg = self.bg if bg is None else bg
+        self._g_net_scalars.zero_()
+        scalars = self._g_net_scalars[N_PARAMS:]
+        loss, reg = scalars[0:1], scalars[1:2]
+        if n == 0:
+            self.g_table.zero_()
+            loss = ((bg.expand(R, 3) - target) ** 2).mean().reshape(1)
+        else:
+            x_def, t_def = p4.sample_inputs(slots, pts, times, R, n_samples, self.std_x, self.std_t, self.seed, counter, first_ray)
+            dws = self._deform_ws(n)
+            dx, xc = deform_fwd(self.packed_d, pts, t_def, x_code=x_def, workspace=dws)
+            ws = self._p4_ws(n)
+            rgb, sigma = self._canonical(xc, t_def, dirs, ws, True)
+            d_rgb, d_sigma, d_dx = torch.empty_like(rgb), torch.empty_like(sigma), torch.empty_like(dx)
+            _lib.check(lib.nerf_composite_mse_reg_bwd(P(rgb), P(sigma), P(slots), P(z), P(rays_d), P(bg), 1, P(target), 1.0 / (3 * R),
+                                                      P(dx), self.reg_weight / (3 * R), R, n_samples, None, None, P(loss), P(reg),
+                                                      P(d_rgb), P(d_sigma), P(d_dx), P(ops.sum_ws(self.device)), ops._stream()),
+                       "nerf_composite_mse_reg_bwd")
+            _lib.check(lib.nerf_p4_canon_bwd(P(self.packed_c), P(ws.buf), P(rgb), P(sigma), P(d_rgb), P(d_sigma), n, P(self.g_net), None, None,
+                                             ops._stream()), "nerf_p4_canon_bwd")
+            d_feat = ws.d_feat(3)
+            # d x_c through the grid ADDED to the regulariser's d delta_x (x_c = x + delta_x), then the counted scatter
+            ops.hash_encode_bwd_input(xc, self.table_h.view(-1, 2), self.levels, self.bound, d_feat, add_to=d_dx)
+            ops.hash_encode_bwd(xc, self.levels, self.bound, d_feat, self.g_table, workspace=self._hash_scratch(n), overwrite=True)
+            deform_bwd(self.packed_d, dws, d_dx, self.g_deform)
+        self.last_reg = reg[0]
+        self.last_terms = self._probe_regularisers(probes) if probes else {}
+        if sync_grads_async is not None:
+            handles = [sync_grads_async(self.g_table), sync_grads_async(self.g_net)]
+            for h in handles:
+                if h is not None:
+                    h.wait()
+        return loss[0]
+
+    def _probe_regularisers(self, probes: Dict[str, Tensor]) -> Dict[str, Tensor]:
+        """temporal smoothness and unsupervised consistency of dynamic.part3_regularisers on the given probes: deformation
+        chain forward (one batch of rows), the terms and their gradients w.r.t. delta_x as elementwise arithmetic, deformation
+        chain backward ADDING into g_net.  Returns the weighted terms."""
+        cfg = self.cfg
+        rows_x, rows_t, spans, terms = [], [], {}, {}
+        if "temporal_x" in probes:
+            eps = float(cfg.get("temporal_epsilon", 0.02))
+            x, t = probes["temporal_x"], probes["temporal_t"].reshape(-1)
+            m = x.shape[0]
+            spans["tmp"] = (0, m)
+            rows_x += [x, x]
+            rows_t += [t, t + eps]
+        if "unsup_x" in probes:
+            at = sum(r.shape[0] for r in rows_x)
+            spans["unsup"] = (at, probes["unsup_x"].shape[0])
+            rows_x.append(probes["unsup_x"])
+            rows_t.append(probes["unsup_t"].reshape(-1))
+        if not rows_x:
+            return terms
+        X, T = torch.cat(rows_x).contiguous(), torch.cat(rows_t).contiguous()
+        ws = self._deform_ws(X.shape[0], "probes")
+        dx, _ = deform_fwd(self.packed_d, X, T, workspace=ws)
+        g = torch.zeros_like(dx)
+        if "tmp" in spans:
+            lo, m = spans["tmp"]
+            w = float(cfg.get("temporal_smooth_weight", 1e-4)) * 2
+            diff = dx[lo:lo + m] - dx[lo + m:lo + 2 * m]
+            terms["temporal"] = torch.mean(diff ** 2) * w
+            g[lo:lo + m] += 2 * w * diff / diff.numel()
+            g[lo + m:lo + 2 * m] -= 2 * w * diff / diff.numel()
+        if "unsup" in spans:
+            lo, m = spans["unsup"]
+            w = float(cfg.get("unsup_consistency_weight", 0.001)) * 4
+            mean = dx[lo:lo + m].mean(dim=0, keepdim=True)
+            terms["unsup"] = torch.mean(torch.abs(mean)) * w
+            g[lo:lo + m] += (w / 3.0) * torch.sign(mean).expand(m, 3) / m
+        deform_bwd(self.packed_d, ws, g, self.g_deform)
+        return terms
+
+    def apply_gradients(self) -> None:
+        """TV-L1 on the canonical table, ONE global-norm clip over every parameter (clip_grad_norm_(model.parameters()),
+        run.py:1174) and AdamW as one group with the cosine schedule; after a summing all-reduce the data gradient is
+        averaged (1/world), the TV term is added unscaled."""
+        lib = _lib.load()
+        st = ops._stream()
+        scale = 1.0 / self.world_size
+        normsq = self._normsq_ws
+        n_tab = self.table.numel()
+        codes = self._tv_codes if self.tv != 0.0 else None
+        # pass 1: the table STORES the squared norm (no zeroing launch), the networks add to it
+        _lib.check(lib.nerf_tv_normsq_codes(P(self.table), P(self.g_table), n_tab, 1, self.tv, scale, P(normsq), 0, P(codes), st),
+                   "nerf_tv_normsq_codes")
+        _lib.check(lib.nerf_tv_normsq_codes(P(self.net), P(self.g_net), N_PARAMS, 1, 0.0, scale, P(normsq), 1, None, st), "nerf_tv_normsq_codes")
+        lr = self.lr()                             # the rate of THIS step: scheduler.step() follows optimizer.step()
+        self.step_count += 1
+        step = self.step_count
+        # pass 2: the whole table is the "lo" range of ONE table (tv_split = n): the seam path of two ranges is never reached
+        m, v = self.state["table"]
+        _lib.check(lib.nerf_adamw_clip_step_tv(P(self.table), P(self.g_table), P(m), P(v), n_tab, step, lr, 0.9, 0.999, 1e-8, self.wd,
+                                               P(normsq), self.max_norm, scale, P(codes), n_tab, self.tv, n_tab, 0.0, 0, 0, 0.0,
+                                               P(self.table_h), st), "nerf_adamw_clip_step_tv")
+        m, v = self.state["net"]
+        _lib.check(lib.nerf_adamw_clip_step_tv(P(self.net), P(self.g_net), P(m), P(v), N_PARAMS, step, lr, 0.9, 0.999, 1e-8, self.wd,
+                                               P(normsq), self.max_norm, scale, None, 0, 0.0, 0, 0.0, 0, 0, 0.0, None, st),
+                   "nerf_adamw_clip_step_tv")
+        p4.pack(self.net[:p4.N_PARAMS], self.packed_c)
+        deform_pack(self.deform_params, self.packed_d)
+
+    def train_step(self, rays_o, rays_d, target, times, n_samples, prepared=None, first_ray: int = 0, bg=None, sync_grads_async=None,
+                   probes=None) -> Tensor:
+        loss = self.compute_gradients(rays_o, rays_d, target, times, n_samples, prepared=prepared, first_ray=first_ray, bg=bg,
+                                      sync_grads_async=sync_grads_async, probes=probes)
+        self.apply_gradients()
+        return loss
+
+    # -- occupancy grid / rendering ----------------------------------------------------------------------------
+    @torch.no_grad()
+    def update_grid(self, times) -> float:
+        """Part 3's DensityGrid refresh (reference run.py:1191-1222, renderer.py:87-101): density on the lattice at each of
+        ``times``, running maximum with decay 1.0 -- the union over the times."""
+        res = self.grid.shape[0]
+        pts = ops.grid_lattice(self.grid_bound, res, self.device)
+        batch = 2 ** 18
+        zeros = torch.zeros(batch, 3, device=self.device)
+        ratio = 0.0
+        for t_val in times:
+            sig = torch.empty(res ** 3, device=self.device)
+            for i in range(0, pts.shape[0], batch):
+                p = pts[i:i + batch]
+                sig[i:i + batch] = self.field(p, zeros[:p.shape[0]], torch.full((p.shape[0],), float(t_val), device=self.device))[1]
+            self.binary_grid, ratio = ops.grid_threshold(sig.view(res, res, res), self.grid_threshold, prev=self.grid, decay=1.0)
+        return ratio
+
+    @torch.no_grad()
+    def render_rays(self, rays_o: Tensor, rays_d: Tensor, times: Tensor, n_samples: int, bg: Optional[Tensor] = None):
+        z, slots, pts, dirs = ops.sample_compact(rays_o, rays_d, self.near, self.far, n_samples, self.binary_grid, self.grid_bound)
+        R = rays_o.shape[0]
+        bg = self.bg if bg is None else bg
+        if pts.shape[0] == 0:
+            return bg.expand(R, 3).clone(), torch.zeros(R, device=self.device), torch.zeros(R, device=self.device)
+        _, t_def = p4.sample_inputs(slots, pts, times.expand(R, 1) if times.numel() == 1 else times, R, n_samples)
+        rgb, sigma, _ = self.field(pts, dirs, t_def)
+        return ops.composite_indexed(rgb, sigma, slots, z, rays_d, bg)
+
+    @torch.no_grad()
+    def render_image(self, rays_o: Tensor, rays_d: Tensor, time: Tensor, n_samples: int, chunk: int = 65536, bg: Optional[Tensor] = None) -> Tensor:
+        shape = rays_o.shape[:-1]
+        o, d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
+        out = torch.empty(o.shape[0], 3, device=self.device)
+        for i in range(0, o.shape[0], chunk):
+            out[i:i + chunk] = self.render_rays(o[i:i + chunk], d[i:i + chunk], time.reshape(1, 1).to(self.device), n_samples, bg=bg)[0]
+        return out.view(*shape, 3)
