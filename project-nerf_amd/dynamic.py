@@ -194,15 +194,15 @@ def run_dynamic(cfg, args):
     bg = torch.ones(3, device=device) if white_bkgd else torch.zeros(3, device=device)
     eval_bg = bg                                    # validation / test always composite onto the dataset's background
 
-    engine3 = []                                    # the Part 3 engine once it trains: validation and test renders go through it
+    eng = None                                      # the flat-parameter engine once one trains
 
     def render_band(o, d, t):
         rows, width = o.shape[0], o.shape[1]
         o, d = o.reshape(-1, 3), d.reshape(-1, 3)
         if o.shape[0] == 0:
             return o.new_zeros(0, width, 3)
-        if engine3:
-            return engine3[0].render_image(o.contiguous(), d.contiguous(), t.reshape(1, 1), render_n, chunk=chunk, bg=eval_bg).view(rows, width, 3)
+        if eng is not None and part3:               # a Part 3 engine renders validation and test views itself
+            return eng.render_image(o.contiguous(), d.contiguous(), t.reshape(1, 1), render_n, chunk=chunk, bg=eval_bg).view(rows, width, 3)
         pred = torch.cat([render_rays(model, o[i:i + chunk], d[i:i + chunk], near, far, render_n, False, density_grid=grid,
                                       times=t.expand(min(chunk, o.shape[0] - i), 1), bg_color=eval_bg)[0]
                           for i in range(0, o.shape[0], chunk)], 0)
@@ -227,12 +227,34 @@ def run_dynamic(cfg, args):
             save["density_grid"] = grid.state_dict()
         torch.save(save, os.path.join(log_dir, "best_model.pth"))
 
+    def sync():
+        """an engine's weights and occupancy grid into the NeuralField / DensityGrid (validation, checkpoints, evaluation)"""
+        if eng is None:
+            return
+        if use_engine:
+            eng.gather_master()                             # sharded optimiser: the other ranks' slices of the fp32 master
+        eng.copy_to_model(model)
+        if grid is not None:
+            grid.grid, grid.binary_grid = eng.grid.clone(), eng.binary_grid.clone()
+
     best = 0.0
+
+    def validate(step):
+        nonlocal best
+        if step % cfg.get("val_every", 500) == 0 or step == iters:
+            sync()
+            v = evaluate(range(min(len(test_set), cfg.get("val_views", 4))))
+            say(f"    [Validation] PSNR: {v:.2f} dB")
+            if v > best and main_rank:
+                best = v
+                save_best(step, best)
+
     local = parallel.check_global_batch(batch, world)       # this rank's shard [lo, hi) of the step's global batch
     lo = rank * local
     warm, stop, decay = cfg.get("grid_warmup_iters", 256), cfg.get("grid_stop_ratio", 0.9), cfg.get("grid_decay", 0.95)
     # random-background augmentation (run.py:1043-1044, 1771-1772): a fresh colour per step for target AND render
     random_bg_start = cfg.get("random_bg_start", 0) if cfg.get("use_random_bg", False) else float("inf")
+    from . import ops
     from . import part4 as p4
     use_engine = (not args.eval_only and not part3 and cfg.get("engine", True) and grid is not None
                   and getattr(model, "_p4_fused", False) and p4.supported(cfg) is None)
@@ -250,135 +272,91 @@ def run_dynamic(cfg, args):
             say(f">>> Part 3 engine not compiled for {why}: module path")
     if world > 1 and not args.eval_only:
         say(f">>> data parallel: {world} ranks x {local} rays (global batch {local * world}); clip after the all-reduce")
-    if use_engine3:
-        # fused deformation chain + Part 4's canonical chain, fused compositing + loss + regulariser + backward, TV + ONE global-norm
-        # clip + AdamW as one group (no torch autograd / optimiser / library GEMM in the loop); weights are copied into the
-        # NeuralField for checkpoints (reference state-dict keys)
-        from . import ops
-        eng = p3.Part3InstantEngine({**cfg, "train_iters": iters, "learning_rate": lr, "grid_resolution": grid.resolution,
-                                     "grid_threshold": grid.threshold, "grid_bound": grid.bound}, device=str(device),
-                                    seed=int(cfg.get("seed", 0) or 0), world_size=world)
-        eng.load_from_model(model)
-        with torch.no_grad():
-            eng.grid.copy_(grid.grid)
-            eng.binary_grid.copy_(grid.binary_grid)
-        parallel.broadcast_([eng.table, eng.net, eng.grid, eng.binary_grid])
-        eng.repack()
-        sync_async = parallel.allreduce_sum_async if world > 1 else None
+    sync_async = parallel.allreduce_sum_async if world > 1 else None
+    pixels = train_set.H * train_set.W
+
+    def start_engine(cls, table=None, **grid_cfg):
+        """The engine on the module's weights (and on the DensityGrid, for the classes that take ``grid_cfg``); replicas start
+        from rank 0's values whatever the seeds did (then stay equal: identical all-reduced gradients, ONE squared norm summed in
+        a fixed order, replicated occupancy-grid updates).  ``table``: the attribute holding the engine's hash tables."""
+        e = cls({**cfg, "train_iters": iters, "learning_rate": lr, **grid_cfg}, device=str(device), seed=int(cfg.get("seed", 0) or 0),
+                world_size=world)
+        e.load_from_model(model)
+        shared = ([getattr(e, table)] if table else []) + [e.net]
+        if grid_cfg:
+            with torch.no_grad():
+                e.grid.copy_(grid.grid)
+                e.binary_grid.copy_(grid.binary_grid)
+            shared += [e.grid, e.binary_grid]
+        parallel.broadcast_(shared)
+        e.repack()
+        return e
+
+    def draw(step):
+        # one uniform draw over all pixels of all frames (the same draw on every rank), this rank's shard of it; the time
+        # stamp of a ray is its frame's
+        idx = torch.randint(0, len(train_set) * pixels, (local * world,), device=device)[lo:lo + local].contiguous()
+        step_bg = torch.rand(3, device=device) if step >= random_bg_start else eval_bg
+        o, d, target, _ = ops.gather_batch(train_set.rgba, train_set.poses, idx, train_set.focal, train_set.scene_scale, bg=step_bg)
+        return o, d, target, train_set.times[idx // pixels].view(-1, 1), step_bg
+
+    def log(step, loss_rgb, active=None):
+        if step % log_every == 0:
+            loss_val = parallel.mean_over_ranks(loss_rgb).item()
+            say(f">>> Step {step}/{iters} | Loss {loss_val:.6f} | PSNR {compute_psnr(loss_val):.2f} dB | LR {eng.lr():.6f}"
+                + ("" if active is None else f" | Skip: {(1 - active) * 100:.1f}%"))
+
+    if use_engine3 or use_engine3n:
+        # Part 3 on a flat-parameter engine: fused deformation chain + canonical chain (hash grid + Part 4's decoder, or the 8x256
+        # decoder on every sample of every ray: no occupancy grid for that canonical type), fused compositing + loss + regulariser
+        # + backward, [TV +] ONE global-norm clip + AdamW as one group (no torch autograd / optimiser / library GEMM in the
+        # loop); weights are copied into the NeuralField for checkpoints (reference state-dict keys)
+        if use_engine3:
+            eng = start_engine(p3.Part3InstantEngine, "table", grid_resolution=grid.resolution, grid_threshold=grid.threshold,
+                               grid_bound=grid.bound)
+            t_lo, t_hi = float(train_set.times.min()), float(train_set.times.max())
+        else:
+            eng = start_engine(p3n.Part3NerfEngine)
         if world > 1:
             say(">>> Part 3 engine: replicated optimiser (flat all-reduce of the gradients, every rank steps every parameter)")
-        engine3.append(eng)
-        pixels = train_set.H * train_set.W
-        t_lo, t_hi = float(train_set.times.min()), float(train_set.times.max())
-
-        def sync():
-            eng.copy_to_model(model)
-            grid.grid, grid.binary_grid = eng.grid.clone(), eng.binary_grid.clone()
-
-        active = 1.0
+        direct = use_engine3n and eng.dtc                   # direct time conditioning: no deformation field to probe
+        active = 1.0 if use_engine3 else None
         for step in range(1, iters + 1):
-            idx = torch.randint(0, len(train_set) * pixels, (local * world,), device=device)[lo:lo + local].contiguous()
-            step_bg = torch.rand(3, device=device) if step >= random_bg_start else eval_bg
-            o, d, target, _ = ops.gather_batch(train_set.rgba, train_set.poses, idx, train_set.focal, train_set.scene_scale, bg=step_bg)
-            t = train_set.times[idx // pixels].view(-1, 1)
+            o, d, target, t, step_bg = draw(step)
             loss_rgb = eng.train_step(o, d, target, t, n_samples, first_ray=lo, bg=step_bg, sync_grads_async=sync_async,
-                                      probes=p3.probe_draws(cfg, step, device))
-            # run.py:1191-1222: every 16 / 64 / 256 steps the union over 16 (later 8) times across the sequence, no decay
-            interval = 16 if step < iters * 0.1 else (64 if step < iters * 0.5 else 256)
-            if grid.should_update(step, interval, warm):
-                active = eng.update_grid(torch.linspace(t_lo, t_hi, 16 if step < 1000 else 8).tolist())
-            if step % log_every == 0:
-                loss_val = parallel.mean_over_ranks(loss_rgb).item()
-                say(f">>> Step {step}/{iters} | Loss {loss_val:.6f} | PSNR {compute_psnr(loss_val):.2f} dB | LR {eng.lr():.6f}"
-                    f" | Skip: {(1 - active) * 100:.1f}%")
-            if step % cfg.get("val_every", 500) == 0 or step == iters:
-                sync()
-                v = evaluate(range(min(len(test_set), cfg.get("val_views", 4))))
-                say(f"    [Validation] PSNR: {v:.2f} dB")
-                if v > best and main_rank:
-                    best = v
-                    save_best(step, best)
+                                      probes=None if direct else p3.probe_draws(cfg, step, device))
+            if use_engine3:
+                # run.py:1191-1222: every 16 / 64 / 256 steps the union over 16 (later 8) times across the sequence, no decay
+                interval = 16 if step < iters * 0.1 else (64 if step < iters * 0.5 else 256)
+                if grid.should_update(step, interval, warm):
+                    active = eng.update_grid(torch.linspace(t_lo, t_hi, 16 if step < 1000 else 8).tolist())
+            log(step, loss_rgb, active)
+            validate(step)
         sync()
-    elif use_engine3n:
-        # fused canonical chain (+ the deformation chain unless direct time conditioning), fused compositing + loss + regulariser
-        # + backward, ONE global-norm clip + AdamW as one group (no torch autograd / optimiser / library GEMM in the loop); every
-        # sample of every ray (no occupancy grid for this canonical type); weights are copied into the NeuralField for checkpoints
-        from . import ops
-        eng = p3n.Part3NerfEngine({**cfg, "train_iters": iters, "learning_rate": lr}, device=str(device), seed=int(cfg.get("seed", 0) or 0),
-                                  world_size=world)
-        eng.load_from_model(model)
-        parallel.broadcast_([eng.net])
-        eng.repack()
-        sync_async = parallel.allreduce_sum_async if world > 1 else None
-        if world > 1:
-            say(">>> Part 3 engine: replicated optimiser (flat all-reduce of the gradients, every rank steps every parameter)")
-        engine3.append(eng)
-        pixels = train_set.H * train_set.W
-        for step in range(1, iters + 1):
-            idx = torch.randint(0, len(train_set) * pixels, (local * world,), device=device)[lo:lo + local].contiguous()
-            step_bg = torch.rand(3, device=device) if step >= random_bg_start else eval_bg
-            o, d, target, _ = ops.gather_batch(train_set.rgba, train_set.poses, idx, train_set.focal, train_set.scene_scale, bg=step_bg)
-            t = train_set.times[idx // pixels].view(-1, 1)
-            loss_rgb = eng.train_step(o, d, target, t, n_samples, first_ray=lo, bg=step_bg, sync_grads_async=sync_async,
-                                      probes=None if eng.dtc else p3.probe_draws(cfg, step, device))
-            if step % log_every == 0:
-                loss_val = parallel.mean_over_ranks(loss_rgb).item()
-                say(f">>> Step {step}/{iters} | Loss {loss_val:.6f} | PSNR {compute_psnr(loss_val):.2f} dB | LR {eng.lr():.6f}")
-            if step % cfg.get("val_every", 500) == 0 or step == iters:
-                eng.copy_to_model(model)
-                v = evaluate(range(min(len(test_set), cfg.get("val_views", 4))))
-                say(f"    [Validation] PSNR: {v:.2f} dB")
-                if v > best and main_rank:
-                    best = v
-                    save_best(step, best)
-        eng.copy_to_model(model)
     elif use_engine:
         # The example shapes train on the flat-parameter engine (part4.DualHashEngine: fused chains, fused compositing + loss
         # + regulariser + backward, one global-norm clip + AdamW with the reference's group rates, no torch autograd / optimiser
         # / library GEMM in the loop); weights and occupancy grid are copied into the NeuralField / DensityGrid for
         # validation, checkpoints and evaluation.  `engine: false` in the YAML or another shape: the module path below.
-        from . import ops
-        eng = p4.DualHashEngine({**cfg, "train_iters": iters, "learning_rate": lr, "grid_resolution": grid.resolution,
-                                 "grid_threshold": grid.threshold, "scene_bound": grid.bound}, device=str(device),
-                                seed=int(cfg.get("seed", 0) or 0), world_size=world)
-        eng.load_from_model(model)
-        with torch.no_grad():
-            eng.grid.copy_(grid.grid)
-            eng.binary_grid.copy_(grid.binary_grid)
-        # replicas start from rank 0's values whatever the seeds did (then stay equal: identical all-reduced gradients, ONE
-        # squared norm summed in a fixed order, replicated occupancy-grid updates)
-        parallel.broadcast_([eng.tables, eng.net, eng.grid, eng.binary_grid])
-        eng.repack()
-        sync_async = parallel.allreduce_sum_async if world > 1 else None
+        eng = start_engine(p4.DualHashEngine, "tables", grid_resolution=grid.resolution, grid_threshold=grid.threshold, scene_bound=grid.bound)
         if world > 1 and cfg.get("dp_sharded_optimizer", True):
             # SURVEY 8(e): reduce-scatter of the flat table gradient, every rank steps its 1/N slice of the four grids (TV + ONE
             # squared norm + AdamW), all-gather of the fp16 copies the forward reads (project-nerf_amd/sharded.py)
             eng.enable_sharded_optimizer(rank)
             sync_async = None
             say(f">>> sharded optimiser: every rank steps {eng.shard.per} of {eng.tables.numel()} table parameters")
-        pixels = train_set.H * train_set.W
 
-        def sync():
-            eng.gather_master()                             # sharded optimiser: the other ranks' slices of the fp32 master
-            eng.copy_to_model(model)
-            grid.grid, grid.binary_grid = eng.grid.clone(), eng.binary_grid.clone()
-
-        def draw(step):
-            # one uniform draw over all pixels of all frames (the same draw on every rank), this rank's shard of it; the time
-            # stamp of a ray is its frame's
-            idx = torch.randint(0, len(train_set) * pixels, (local * world,), device=device)[lo:lo + local].contiguous()
-            step_bg = torch.rand(3, device=device) if step >= random_bg_start else eval_bg
-            o, d, target, _ = ops.gather_batch(train_set.rgba, train_set.poses, idx, train_set.focal, train_set.scene_scale, bg=step_bg)
-            t = train_set.times[idx // pixels].view(-1, 1)
-            return o, d, target, t, step_bg, eng.prepare_batch(o, d, n_samples, first_ray=lo)
+        def draw_ahead(step):
+            o, d, *rest = draw(step)
+            return (o, d, *rest, eng.prepare_batch(o, d, n_samples, first_ray=lo))
 
         active, ahead = 1.0, []
         for step in range(1, iters + 1):
             if not ahead:
-                ahead.append(draw(step))
+                ahead.append(draw_ahead(step))
             o, d, target, t, step_bg, prepared = ahead.pop()
             if step < iters:
-                ahead.append(draw(step + 1))                # compaction of the next batch queued ahead of this step's kernels
+                ahead.append(draw_ahead(step + 1))          # compaction of the next batch queued ahead of this step's kernels
             loss_rgb = eng.train_step(o, d, target, t, n_samples, prepared=prepared, first_ray=lo, bg=step_bg,
                                       sync_grads_async=sync_async, probes=part4_probe_draws(cfg, step, device))
             if step < iters * stop:
@@ -386,17 +364,8 @@ def run_dynamic(cfg, args):
                 if step >= warm and step % interval == 0:
                     active = eng.update_grid(decay=decay)   # three time anchors, running maximum (replicated)
                     ahead.clear()                           # the waiting batch was compacted against the previous grid
-            if step % log_every == 0:
-                loss_val = parallel.mean_over_ranks(loss_rgb).item()
-                say(f">>> Step {step}/{iters} | Loss {loss_val:.6f} | PSNR {compute_psnr(loss_val):.2f} dB | LR {eng.lr():.6f}"
-                    f" | Skip: {(1 - active) * 100:.1f}%")
-            if step % cfg.get("val_every", 500) == 0 or step == iters:
-                sync()
-                v = evaluate(range(min(len(test_set), cfg.get("val_views", 4))))
-                say(f"    [Validation] PSNR: {v:.2f} dB")
-                if v > best and main_rank:
-                    best = v
-                    save_best(step, best)
+            log(step, loss_rgb, active)
+            validate(step)
         if world > 1:
             eng.gather_master()
             say(f">>> replica divergence after {iters} steps: {parallel.replica_divergence([eng.tables, eng.net, eng.binary_grid]):.3e}")
@@ -441,12 +410,7 @@ def run_dynamic(cfg, args):
             if step % log_every == 0:
                 say(f">>> Step {step}/{iters} | Loss {parallel.mean_over_ranks(loss).item():.6f} | PSNR "
                     f"{compute_psnr(parallel.mean_over_ranks(loss_rgb).item()):.2f} dB | Skip: {(1 - active) * 100:.1f}%")
-            if step % cfg.get("val_every", 500) == 0 or step == iters:
-                v = evaluate(range(min(len(test_set), cfg.get("val_views", 4))))
-                say(f"    [Validation] PSNR: {v:.2f} dB")
-                if v > best and main_rank:
-                    best = v
-                    save_best(step, best)
+            validate(step)
     n_eval = len(test_set) if args.render_n in (None, -1) else min(args.render_n, len(test_set))
     avg = evaluate(range(n_eval))
     say(f">>> Test PSNR: {avg:.2f} dB (best validation {best:.2f} dB)")

@@ -15,13 +15,13 @@ entry points; the deformation MLP follows it in the same flat vector.
 """
 from __future__ import annotations
 
-import math
 from typing import Dict, Optional
 
 import torch
 
 from . import _lib, ops
 from . import part4 as p4
+from .dynamic_engine import GridEngine, clip_adamw_flat, composite_mse_reg_bwd, normsq_flat, sample_inputs
 
 Tensor = torch.Tensor
 P = lambda t: None if t is None else t.data_ptr()
@@ -167,8 +167,9 @@ def deform_probe_regularisers(cfg: dict, packed_d: Tensor, workspace, g_deform: 
 
 
 # --------------------------------------------------------------------------------------------------- engine
-class Part3InstantEngine:
+class Part3InstantEngine(GridEngine):
     """Flat-parameter training / rendering engine of mode part3 with canonical_type instant (module docstring)."""
+    SLACK = (1.25, 256)
 
     def __init__(self, cfg: dict, device: str = "cuda", seed: int = 0, world_size: int = 1):
         why = supported(cfg)
@@ -176,9 +177,7 @@ class Part3InstantEngine:
             raise NotImplementedError(f"the fused Part 3 chains are not compiled for {why}")
         _check_count()
         p4._check_count()
-        self.cfg = dict(cfg)
-        self.device = torch.device(device)
-        self.seed, self.world_size = int(seed), int(world_size)
+        super().__init__(cfg, device, seed, world_size)
         self.bound = float(cfg.get("scene_bound", 1.0))                 # the canonical grid's bound (src/core.py:118)
         self.grid_bound = float(cfg.get("grid_bound", cfg.get("scene_bound", 1.5)))
         self.levels = ops.HashLevelTable(cfg.get("n_levels", 16), cfg.get("log2_hashmap_size", 19), cfg.get("base_resolution", 16),
@@ -195,28 +194,9 @@ class Part3InstantEngine:
                       "net": (torch.zeros_like(self.net), torch.zeros_like(self.net))}
         self.packed_c = torch.empty(_lib.load().nerf_p4_packed_bytes(), dtype=torch.uint8, device=self.device)
         self.packed_d = torch.empty(_lib.load().nerf_p3_deform_packed_bytes(), dtype=torch.uint8, device=self.device)
-        self.near, self.far = float(cfg.get("near", 2.0)), float(cfg.get("far", 6.0))
-        self.lr0, self.eta_min = float(cfg.get("learning_rate", 5e-4)), float(cfg.get("eta_min", 1e-4))
-        self.t_max = int(cfg.get("train_iters", 20000))
-        self.wd = float(cfg.get("weight_decay", 1e-5))
-        self.max_norm = float(cfg.get("max_grad_norm", 1.0))
-        self.reg_weight = float(cfg.get("deformation_reg_weight", 1e-4))
         self.tv = float(cfg.get("tv_loss_weight", 1e-6)) if cfg.get("use_tv_loss", True) else 0.0
-        noisy = bool(cfg.get("use_coord_noise", False))
-        self.std_x = float(cfg.get("coord_noise_std", 0.005)) if noisy else 0.0
-        self.std_t = float(cfg.get("time_noise_std", 0.02)) if noisy else 0.0
-        self.bg = (torch.ones(3) if cfg.get("white_bkgd", True) else torch.zeros(3)).to(self.device)
-        res = int(cfg.get("grid_resolution", 128))
-        self.grid_threshold = float(cfg.get("grid_threshold", 0.01))
-        self.grid = torch.zeros(res, res, res, device=self.device)
-        self.binary_grid = torch.ones(res, res, res, dtype=torch.bool, device=self.device)
-        self.step_count = 0
-        self._normsq_ws = ops.normsq_ws(self.device)
         # two-bit signs of the TV term; zeroed once (a one-table call never reads a byte pass 1 left unwritten)
         self._tv_codes = torch.zeros((n_tab + 3) // 4, dtype=torch.uint8, device=self.device)
-        self._ws: Dict[str, Tensor] = {}
-        self._counter = 0
-        self.last_terms: Dict[str, Tensor] = {}
         self.repack()
 
     # -- parameters ------------------------------------------------------------------------------------------
@@ -228,9 +208,12 @@ class Part3InstantEngine:
     def g_deform(self) -> Tensor:
         return self.g_net[DEFORM0:]
 
-    def repack(self) -> None:
+    def _pack_nets(self) -> None:
         p4.pack(self.net[:p4.N_PARAMS], self.packed_c)
         deform_pack(self.deform_params, self.packed_d)
+
+    def repack(self) -> None:
+        self._pack_nets()
         ops.f32_to_f16(self.table, self.table_h)
 
     @staticmethod
@@ -239,34 +222,9 @@ class Part3InstantEngine:
         return [(k, "net", off, shape) for k, off, shape in MODULE_SLICES] + [(TABLE_KEY, "table", 0, None)]
 
     def load_from_model(self, model) -> None:
-        sd = dict(model.named_parameters())
         with torch.no_grad():
-            self.net.zero_()
-            for key, off, shape in MODULE_SLICES:
-                cnt = math.prod(shape)
-                self.net[off:off + cnt].copy_(sd[key].reshape(-1))
-            self.table.copy_(sd[TABLE_KEY].reshape(-1))
-        self.repack()
-
-    def copy_to_model(self, model) -> None:
-        sd = dict(model.named_parameters())
-        with torch.no_grad():
-            for key, off, shape in MODULE_SLICES:
-                cnt = math.prod(shape)
-                sd[key].copy_(self.net[off:off + cnt].view(sd[key].shape))
-            sd[TABLE_KEY].copy_(self.table.view(sd[TABLE_KEY].shape))
-
-    def lr(self) -> float:
-        """CosineAnnealingLR of the one group (run.py:1016-1021)"""
-        return self.eta_min + (self.lr0 - self.eta_min) * (1 + math.cos(math.pi * self.step_count / self.t_max)) / 2
-
-    def _buf(self, which: str, need: int) -> Tensor:
-        """grow-only buffers: the active-point count changes almost every step"""
-        buf = self._ws.get(which)
-        if buf is None or buf.numel() < need:
-            self._ws.pop(which, None)
-            buf = self._ws[which] = torch.empty(int(need * 1.25) + 256, dtype=torch.uint8, device=self.device)
-        return buf
+            self.net.zero_()                       # Part 4's deformation slots: zero and unused
+        super().load_from_model(model)
 
     def _p4_ws(self, n: int, which: str = "batch") -> p4.Workspace:
         return p4.Workspace(n, self.device, buf=self._buf("p4_" + which, p4.Workspace.bytes(n)))
@@ -298,11 +256,6 @@ class Part3InstantEngine:
         rgb, sigma = self._canonical(xc, t, dirs, self._p4_ws(n, "eval"), False)
         return rgb, sigma, dx
 
-    def prepare_batch(self, rays_o: Tensor, rays_d: Tensor, n_samples: int, first_ray: int = 0):
-        self._counter += 1
-        return ops.sample_compact_async(rays_o, rays_d, self.near, self.far, n_samples, self.binary_grid, self.grid_bound,
-                                        jitter=(self.seed, self._counter), first_ray=first_ray), self._counter
-
     def compute_gradients(self, rays_o: Tensor, rays_d: Tensor, target: Tensor, times: Tensor, n_samples: int, prepared=None,
                           first_ray: int = 0, bg: Optional[Tensor] = None, sync_grads_async=None, probes=None) -> Tensor:
         """Forward + backward of one batch: fills g_net / g_table with the gradient of MSE + deformation_reg_weight *
@@ -321,16 +274,13 @@ class Part3InstantEngine:
             self.g_table.zero_()
             loss = ((bg.expand(R, 3) - target) ** 2).mean().reshape(1)
         else:
-            x_def, t_def = p4.sample_inputs(slots, pts, times, R, n_samples, self.std_x, self.std_t, self.seed, counter, first_ray)
+            x_def, t_def = sample_inputs(slots, pts, times, R, n_samples, self.std_x, self.std_t, self.seed, counter, first_ray)
             dws = self._deform_ws(n)
             dx, xc = deform_fwd(self.packed_d, pts, t_def, x_code=x_def, workspace=dws)
             ws = self._p4_ws(n)
             rgb, sigma = self._canonical(xc, t_def, dirs, ws, True)
-            d_rgb, d_sigma, d_dx = torch.empty_like(rgb), torch.empty_like(sigma), torch.empty_like(dx)
-            _lib.check(lib.nerf_composite_mse_reg_bwd(P(rgb), P(sigma), P(slots), P(z), P(rays_d), P(bg), 1, P(target), 1.0 / (3 * R),
-                                                      P(dx), self.reg_weight / (3 * R), R, n_samples, None, None, P(loss), P(reg),
-                                                      P(d_rgb), P(d_sigma), P(d_dx), P(ops.sum_ws(self.device)), ops._stream()),
-                       "nerf_composite_mse_reg_bwd")
+            d_rgb, d_sigma, d_dx = composite_mse_reg_bwd(rgb, sigma, slots, z, rays_d, bg, target, dx, self.reg_weight, R, n_samples, loss, reg,
+                                                         ops.sum_ws(self.device))
             _lib.check(lib.nerf_p4_canon_bwd(P(self.packed_c), P(ws.buf), P(rgb), P(sigma), P(d_rgb), P(d_sigma), n, P(self.g_net), None, None,
                                              ops._stream()), "nerf_p4_canon_bwd")
             d_feat = ws.d_feat(3)
@@ -340,11 +290,7 @@ class Part3InstantEngine:
             deform_bwd(self.packed_d, dws, d_dx, self.g_deform)
         self.last_reg = reg[0]
         self.last_terms = self._probe_regularisers(probes) if probes else {}
-        if sync_grads_async is not None:
-            handles = [sync_grads_async(self.g_table), sync_grads_async(self.g_net)]
-            for h in handles:
-                if h is not None:
-                    h.wait()
+        self._sync_grads(sync_grads_async, self.g_table, self.g_net)
         return loss[0]
 
     def _probe_regularisers(self, probes: Dict[str, Tensor]) -> Dict[str, Tensor]:
@@ -364,63 +310,28 @@ class Part3InstantEngine:
         # pass 1: the table STORES the squared norm (no zeroing launch), the networks add to it
         _lib.check(lib.nerf_tv_normsq_codes(P(self.table), P(self.g_table), n_tab, 1, self.tv, scale, P(normsq), 0, P(codes), st),
                    "nerf_tv_normsq_codes")
-        _lib.check(lib.nerf_tv_normsq_codes(P(self.net), P(self.g_net), N_PARAMS, 1, 0.0, scale, P(normsq), 1, None, st), "nerf_tv_normsq_codes")
+        normsq_flat(self.net, self.g_net, N_PARAMS, scale, normsq, first=False)
         lr = self.lr()                             # the rate of THIS step: scheduler.step() follows optimizer.step()
         self.step_count += 1
-        step = self.step_count
         # pass 2: the whole table is the "lo" range of ONE table (tv_split = n): the seam path of two ranges is never reached
         m, v = self.state["table"]
-        _lib.check(lib.nerf_adamw_clip_step_tv(P(self.table), P(self.g_table), P(m), P(v), n_tab, step, lr, 0.9, 0.999, 1e-8, self.wd,
+        _lib.check(lib.nerf_adamw_clip_step_tv(P(self.table), P(self.g_table), P(m), P(v), n_tab, self.step_count, lr, 0.9, 0.999, 1e-8, self.wd,
                                                P(normsq), self.max_norm, scale, P(codes), n_tab, self.tv, n_tab, 0.0, 0, 0, 0.0,
                                                P(self.table_h), st), "nerf_adamw_clip_step_tv")
-        m, v = self.state["net"]
-        _lib.check(lib.nerf_adamw_clip_step_tv(P(self.net), P(self.g_net), P(m), P(v), N_PARAMS, step, lr, 0.9, 0.999, 1e-8, self.wd,
-                                               P(normsq), self.max_norm, scale, None, 0, 0.0, 0, 0.0, 0, 0, 0.0, None, st),
-                   "nerf_adamw_clip_step_tv")
-        p4.pack(self.net[:p4.N_PARAMS], self.packed_c)
-        deform_pack(self.deform_params, self.packed_d)
+        clip_adamw_flat(self.net, self.g_net, self.state["net"], N_PARAMS, self.step_count, lr, self.wd, normsq, self.max_norm, scale)
+        self._pack_nets()
 
-    def train_step(self, rays_o, rays_d, target, times, n_samples, prepared=None, first_ray: int = 0, bg=None, sync_grads_async=None,
-                   probes=None) -> Tensor:
-        loss = self.compute_gradients(rays_o, rays_d, target, times, n_samples, prepared=prepared, first_ray=first_ray, bg=bg,
-                                      sync_grads_async=sync_grads_async, probes=probes)
-        self.apply_gradients()
-        return loss
-
-    # -- occupancy grid / rendering ----------------------------------------------------------------------------
+    # -- occupancy grid --------------------------------------------------------------------------------------
     @torch.no_grad()
     def update_grid(self, times) -> float:
         """Part 3's DensityGrid refresh (reference run.py:1191-1222, renderer.py:87-101): density on the lattice at each of
         ``times``, running maximum with decay 1.0 -- the union over the times."""
         res = self.grid.shape[0]
-        pts = ops.grid_lattice(self.grid_bound, res, self.device)
-        batch = 2 ** 18
-        zeros = torch.zeros(batch, 3, device=self.device)
+        lattice = self._lattice()
         ratio = 0.0
         for t_val in times:
             sig = torch.empty(res ** 3, device=self.device)
-            for i in range(0, pts.shape[0], batch):
-                p = pts[i:i + batch]
-                sig[i:i + batch] = self.field(p, zeros[:p.shape[0]], torch.full((p.shape[0],), float(t_val), device=self.device))[1]
+            for i, s in self.lattice_density(lattice, t_val):
+                sig[i:i + s.shape[0]] = s
             self.binary_grid, ratio = ops.grid_threshold(sig.view(res, res, res), self.grid_threshold, prev=self.grid, decay=1.0)
         return ratio
-
-    @torch.no_grad()
-    def render_rays(self, rays_o: Tensor, rays_d: Tensor, times: Tensor, n_samples: int, bg: Optional[Tensor] = None):
-        z, slots, pts, dirs = ops.sample_compact(rays_o, rays_d, self.near, self.far, n_samples, self.binary_grid, self.grid_bound)
-        R = rays_o.shape[0]
-        bg = self.bg if bg is None else bg
-        if pts.shape[0] == 0:
-            return bg.expand(R, 3).clone(), torch.zeros(R, device=self.device), torch.zeros(R, device=self.device)
-        _, t_def = p4.sample_inputs(slots, pts, times.expand(R, 1) if times.numel() == 1 else times, R, n_samples)
-        rgb, sigma, _ = self.field(pts, dirs, t_def)
-        return ops.composite_indexed(rgb, sigma, slots, z, rays_d, bg)
-
-    @torch.no_grad()
-    def render_image(self, rays_o: Tensor, rays_d: Tensor, time: Tensor, n_samples: int, chunk: int = 65536, bg: Optional[Tensor] = None) -> Tensor:
-        shape = rays_o.shape[:-1]
-        o, d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
-        out = torch.empty(o.shape[0], 3, device=self.device)
-        for i in range(0, o.shape[0], chunk):
-            out[i:i + chunk] = self.render_rays(o[i:i + chunk], d[i:i + chunk], time.reshape(1, 1).to(self.device), n_samples, bg=bg)[0]
-        return out.view(*shape, 3)

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib, ops
 from . import part3 as p3
-from . import part4 as p4
+from .dynamic_engine import DynamicEngine, clip_adamw_flat, composite_mse_reg_bwd, normsq_flat, sample_inputs
 
 Tensor = torch.Tensor
 P = lambda t: None if t is None else t.data_ptr()
@@ -131,15 +131,17 @@ def canon_bwd(packed: Tensor, workspace: Tensor, tdim: int, rgb: Tensor, sigma: 
 
 
 # --------------------------------------------------------------------------------------------------- engine
-class Part3NerfEngine:
+class Part3NerfEngine(DynamicEngine):
     """Flat-parameter training / rendering engine of mode part3 with canonical_type nerf (module docstring)."""
+    SLACK = (1.0, 0)                 # exact sizes: n = rays x samples is the same every step
+    RENDER_CHUNK = 16384
 
     def __init__(self, cfg: dict, device: str = "cuda", seed: int = 0, world_size: int = 1):
         why = supported_nerf(cfg)
         if why is not None:
             raise NotImplementedError(f"the fused Part 3 canonical chains are not compiled for {why}")
         lib = _lib.load()
-        self.cfg = dict(cfg)
+        super().__init__(cfg, device, seed, world_size)
         self.dtc = _dtc(cfg)
         self.tdim = time_dim(cfg)
         self.n_canon = int(lib.nerf_p3_canon_param_count(self.tdim))
@@ -150,29 +152,14 @@ class Part3NerfEngine:
                                     f"{self.n_params - (0 if self.dtc else p3.N_DEFORM)}")
         if not self.dtc:
             p3._check_count()
-        self.device = torch.device(device)
-        self.seed, self.world_size = int(seed), int(world_size)
         self.net = torch.zeros(self.n_params, device=self.device)
         self._g_net_scalars = torch.zeros(self.n_params + 4, device=self.device)
         self.g_net = self._g_net_scalars[:self.n_params]
         self.state = {"net": (torch.zeros_like(self.net), torch.zeros_like(self.net))}
         self.packed_c = torch.empty(lib.nerf_p3_canon_packed_bytes(), dtype=torch.uint8, device=self.device)
         self.packed_d = None if self.dtc else torch.empty(lib.nerf_p3_deform_packed_bytes(), dtype=torch.uint8, device=self.device)
-        self.near, self.far = float(cfg.get("near", 2.0)), float(cfg.get("far", 6.0))
-        self.lr0, self.eta_min = float(cfg.get("learning_rate", 5e-4)), float(cfg.get("eta_min", 1e-4))
-        self.t_max = int(cfg.get("train_iters", 20000))
-        self.wd = float(cfg.get("weight_decay", 1e-5))
-        self.max_norm = float(cfg.get("max_grad_norm", 1.0))
-        self.reg_weight = 0.0 if self.dtc else float(cfg.get("deformation_reg_weight", 1e-4))
-        noisy = bool(cfg.get("use_coord_noise", False)) and not self.dtc      # the noise feeds the deformation branch only
-        self.std_x = float(cfg.get("coord_noise_std", 0.005)) if noisy else 0.0
-        self.std_t = float(cfg.get("time_noise_std", 0.02)) if noisy else 0.0
-        self.bg = (torch.ones(3) if cfg.get("white_bkgd", True) else torch.zeros(3)).to(self.device)
-        self.step_count = 0
-        self._normsq_ws = ops.normsq_ws(self.device)
-        self._ws: Dict[str, Tensor] = {}
-        self._counter = 0
-        self.last_terms: Dict[str, Tensor] = {}
+        if self.dtc:                 # no deformation branch: nothing to regularise, and the noise feeds that branch only
+            self.reg_weight = self.std_x = self.std_t = 0.0
         self.last_reg = torch.zeros((), device=self.device)
         self.last_d_dx: Optional[Tensor] = None
         self.repack()
@@ -202,31 +189,6 @@ class Part3NerfEngine:
     def slice_table(self):
         """(key, 'net', offset, shape) of every module parameter the engine trains"""
         return list(self.slices)
-
-    def load_from_model(self, model) -> None:
-        sd = dict(model.named_parameters())
-        with torch.no_grad():
-            for key, _, off, shape in self.slices:
-                self.net[off:off + math.prod(shape)].copy_(sd[key].reshape(-1))
-        self.repack()
-
-    def copy_to_model(self, model) -> None:
-        """the trained parameters only: every other parameter of the module is left as it is"""
-        sd = dict(model.named_parameters())
-        with torch.no_grad():
-            for key, _, off, shape in self.slices:
-                sd[key].copy_(self.net[off:off + math.prod(shape)].view(sd[key].shape))
-
-    def lr(self) -> float:
-        """CosineAnnealingLR of the one group (run.py:1016-1021)"""
-        return self.eta_min + (self.lr0 - self.eta_min) * (1 + math.cos(math.pi * self.step_count / self.t_max)) / 2
-
-    def _buf(self, which: str, need: int) -> Tensor:
-        buf = self._ws.get(which)
-        if buf is None or buf.numel() < need:
-            self._ws.pop(which, None)
-            buf = self._ws[which] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return buf
 
     def _deform_ws(self, n: int, which: str = "batch") -> Tensor:
         return self._buf("p3_" + which, p3.deform_workspace_bytes(n))
@@ -258,7 +220,6 @@ class Part3NerfEngine:
         (+ the probe terms) of the LOCAL rays and returns the RGB loss.  ``u`` [R,S]: the stratified jitter (default: torch.rand,
         as render_rays draws it).  ``sync_grads_async(view)``: data-parallel hook (a summing all-reduce; apply_gradients
         divides by the world size)."""
-        lib = _lib.load()
         R, S = rays_o.shape[0], int(n_samples)
         n = R * S
         bg = self.bg if bg is None else bg
@@ -270,7 +231,7 @@ class Part3NerfEngine:
         self._g_net_scalars.zero_()
         scalars = self._g_net_scalars[self.n_params:]
         loss, reg = scalars[0:1], scalars[1:2]
-        x_def, t_def = p4.sample_inputs(slots, pts, times, R, S, self.std_x, self.std_t, self.seed, self._counter, first_ray)
+        x_def, t_def = sample_inputs(slots, pts, times, R, S, self.std_x, self.std_t, self.seed, self._counter, first_ray)
         cws = self._buf("canon", canon_workspace_bytes(n))
         if self.dtc:
             dx = self._ws.get("zeros")
@@ -283,11 +244,8 @@ class Part3NerfEngine:
             dx, xc = p3.deform_fwd(self.packed_d, pts, t_def, x_code=x_def, workspace=dws)
         # the canonical decoder sees t' as well (src/core.py:136-139); under direct time conditioning t' = t (no noise)
         rgb, sigma = canon_fwd(self.packed_c, xc, t_def, dirs, workspace=cws)
-        d_rgb, d_sigma, d_dx = torch.empty_like(rgb), torch.empty_like(sigma), torch.empty(n, 3, device=self.device)
-        _lib.check(lib.nerf_composite_mse_reg_bwd(P(rgb), P(sigma), P(slots), P(z), P(rays_d), P(bg), 1, P(target), 1.0 / (3 * R),
-                                                  P(dx), self.reg_weight / (3 * R), R, S, None, None, P(loss), P(reg),
-                                                  P(d_rgb), P(d_sigma), P(d_dx), P(ops.sum_ws(self.device)), ops._stream()),
-                   "nerf_composite_mse_reg_bwd")
+        d_rgb, d_sigma, d_dx = composite_mse_reg_bwd(rgb, sigma, slots, z, rays_d, bg, target, dx, self.reg_weight, R, S, loss, reg,
+                                                     ops.sum_ws(self.device))
         if self.dtc:
             canon_bwd(self.packed_c, cws, self.tdim, rgb, sigma, d_rgb, d_sigma, self.g_canon)
         else:
@@ -297,10 +255,7 @@ class Part3NerfEngine:
             p3.deform_bwd(self.packed_d, dws, d_dx, self.g_deform)
         self.last_reg = reg[0]
         self.last_terms = self._probe_regularisers(probes) if (probes and not self.dtc) else {}
-        if sync_grads_async is not None:
-            h = sync_grads_async(self.g_net)
-            if h is not None:
-                h.wait()
+        self._sync_grads(sync_grads_async, self.g_net)
         return loss[0]
 
     def _probe_regularisers(self, probes: Dict[str, Tensor]) -> Dict[str, Tensor]:
@@ -311,25 +266,13 @@ class Part3NerfEngine:
     def apply_gradients(self) -> None:
         """ONE global-norm clip over every trained parameter (clip_grad_norm_(model.parameters()), run.py:1174) and AdamW as one
         group with the cosine schedule; after a summing all-reduce the gradient is averaged (1/world)."""
-        lib = _lib.load()
-        st = ops._stream()
         scale = 1.0 / self.world_size
-        _lib.check(lib.nerf_tv_normsq_codes(P(self.net), P(self.g_net), self.n_params, 1, 0.0, scale, P(self._normsq_ws), 0, None, st),
-                   "nerf_tv_normsq_codes")
+        normsq_flat(self.net, self.g_net, self.n_params, scale, self._normsq_ws, first=True)
         lr = self.lr()                             # the rate of THIS step: scheduler.step() follows optimizer.step()
         self.step_count += 1
-        m, v = self.state["net"]
-        _lib.check(lib.nerf_adamw_clip_step_tv(P(self.net), P(self.g_net), P(m), P(v), self.n_params, self.step_count, lr, 0.9, 0.999, 1e-8,
-                                               self.wd, P(self._normsq_ws), self.max_norm, scale, None, 0, 0.0, 0, 0.0, 0, 0, 0.0, None, st),
-                   "nerf_adamw_clip_step_tv")
+        clip_adamw_flat(self.net, self.g_net, self.state["net"], self.n_params, self.step_count, lr, self.wd, self._normsq_ws, self.max_norm,
+                        scale)
         self.repack()
-
-    def train_step(self, rays_o, rays_d, target, times, n_samples, u=None, first_ray: int = 0, bg=None, sync_grads_async=None,
-                   probes=None) -> Tensor:
-        loss = self.compute_gradients(rays_o, rays_d, target, times, n_samples, u=u, first_ray=first_ray, bg=bg,
-                                      sync_grads_async=sync_grads_async, probes=probes)
-        self.apply_gradients()
-        return loss
 
     # -- rendering -------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -342,13 +285,3 @@ class Part3NerfEngine:
         rgb, sigma, _ = self.field(pts, dirs, t)
         out_rgb, depth, acc, _ = ops.composite(rgb.view(R, n_samples, 3), sigma.view(R, n_samples), z, rays_d.contiguous(), bg)
         return out_rgb, depth, acc
-
-    @torch.no_grad()
-    def render_image(self, rays_o: Tensor, rays_d: Tensor, time: Tensor, n_samples: int, chunk: int = 16384,
-                     bg: Optional[Tensor] = None) -> Tensor:
-        shape = rays_o.shape[:-1]
-        o, d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
-        out = torch.empty(o.shape[0], 3, device=self.device)
-        for i in range(0, o.shape[0], chunk):
-            out[i:i + chunk] = self.render_rays(o[i:i + chunk], d[i:i + chunk], time.reshape(1, 1).to(self.device), n_samples, bg=bg)[0]
-        return out.view(*shape, 3)

@@ -12,13 +12,13 @@ Two entry points over the same kernels:
 """
 from __future__ import annotations
 
-import math
 import os
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 
 from . import _lib, ops
+from .dynamic_engine import GridEngine, clip_adamw_flat, composite_mse_reg_bwd, normsq_flat, sample_inputs, wait_all
 
 Tensor = torch.Tensor
 P = lambda t: None if t is None else t.data_ptr()
@@ -89,20 +89,6 @@ def pack(params: Tensor, packed: Optional[Tensor] = None) -> Tensor:
         packed = torch.empty(lib.nerf_p4_packed_bytes(), dtype=torch.uint8, device=params.device)
     _lib.check(lib.nerf_p4_pack(P(params), P(packed), ops._stream()), "nerf_p4_pack")
     return packed
-
-
-def sample_inputs(slots: Optional[Tensor], pts: Tensor, times: Tensor, n_rays: int, n_samples: int, std_x: float = 0.0,
-                  std_t: float = 0.0, seed: int = 0, counter: int = 0, first_ray: int = 0):
-    """(x' [n,3] or None, t' [n]) of the compacted samples (``n_samples`` > 0: ``times`` per ray) or of plain points
-    (``n_samples`` == 0: ``times`` per point)."""
-    lib = _lib.load()
-    n = pts.shape[0]
-    t_def = torch.empty(n, device=pts.device)
-    x_def = torch.empty(n, 3, device=pts.device) if std_x > 0.0 else None
-    _lib.check(lib.nerf_p4_sample_inputs(P(slots), P(pts), P(ops._dev(times.reshape(-1), "times")), n_rays, n_samples, float(std_x),
-                                         float(std_t), int(seed), int(counter) & 0xFFFFFF, int(first_ray), P(x_def), P(t_def),
-                                         ops._stream()), "nerf_p4_sample_inputs")
-    return x_def, t_def
 
 
 def forward_chain(packed, params, tables, levels_d, levels_c, bound, pts, x_def, t_def, dirs, ws: Workspace, train: bool,
@@ -259,7 +245,7 @@ def field(model, x: Tensor, d: Tensor, t: Tensor, x_deform: Optional[Tensor] = N
 
 
 # --------------------------------------------------------------------------------------------------- engine
-class DualHashEngine:
+class DualHashEngine(GridEngine):
     """Flat-parameter training / rendering engine of mode part4 (loop body of reference run_part4, run.py:1808-1990):
 
         batch -> compaction -> t', x' (+ noise) -> 3 deformation hash encodings -> deformation chain -> canonical hash
@@ -268,16 +254,15 @@ class DualHashEngine:
         -> [regulariser probes through the same kernels] -> [all-reduce] -> TV terms + ONE global-norm clip + AdamW
         (2x lr for the four grids, 5x for displacement_scale, cosine schedule) -> repack.
     """
+    REG_WEIGHT = 0.01
 
     def __init__(self, cfg: dict, device: str = "cuda", seed: int = 0, world_size: int = 1):
         why = supported(cfg)
         if why is not None:
             raise NotImplementedError(f"the fused Part 4 chains are not compiled for {why}")
         _check_count()
-        self.cfg = dict(cfg)
-        self.device = torch.device(device)
-        self.seed, self.world_size = int(seed), int(world_size)
-        self.bound = float(cfg.get("scene_bound", 1.5))
+        super().__init__(cfg, device, seed, world_size)
+        self.bound = self.grid_bound = float(cfg.get("scene_bound", 1.5))      # the hash grids' and the occupancy grid's
         self.levels_d = ops.HashLevelTable(cfg.get("deform_n_levels", 14), cfg.get("deform_log2_hashmap_size", 19),
                                            cfg.get("deform_base_resolution", 16), cfg.get("deform_per_level_scale", 1.5))
         self.levels_c = ops.HashLevelTable(cfg.get("n_levels", 16), cfg.get("log2_hashmap_size", 19), cfg.get("base_resolution", 16),
@@ -305,36 +290,15 @@ class DualHashEngine:
         self._m_buf, self._v_buf = torch.zeros(n_pad, device=self.device), torch.zeros(n_pad, device=self.device)
         self.state = {"tables": (self._m_buf[:total], self._v_buf[:total]), "net": (torch.zeros_like(self.net), torch.zeros_like(self.net))}
         self.packed = torch.empty(_lib.load().nerf_p4_packed_bytes(), dtype=torch.uint8, device=self.device)
-        self.near, self.far = float(cfg.get("near", 2.0)), float(cfg.get("far", 6.0))
-        self.lr0, self.eta_min = float(cfg.get("learning_rate", 5e-4)), float(cfg.get("eta_min", 1e-4))
-        self.t_max = int(cfg.get("train_iters", 20000))
-        self.wd = float(cfg.get("weight_decay", 1e-5))
-        self.max_norm = float(cfg.get("max_grad_norm", 1.0))
-        self.reg_weight = float(cfg.get("deformation_reg_weight", 0.01))
         self.tv_disp = float(cfg.get("tv_displacement_weight", 0.001)) / 3.0 if cfg.get("use_tv_displacement", True) else 0.0
         self.tv_canon = float(cfg.get("tv_loss_weight", 1e-5))
-        noisy = bool(cfg.get("use_coord_noise", False))
-        self.std_x = float(cfg.get("coord_noise_std", 0.005)) if noisy else 0.0
-        self.std_t = float(cfg.get("time_noise_std", 0.02)) if noisy else 0.0
-        self.bg = (torch.ones(3) if cfg.get("white_bkgd", True) else torch.zeros(3)).to(self.device)
-        res = int(cfg.get("grid_resolution", 128))
-        self.grid_threshold = float(cfg.get("grid_threshold", 0.01))
-        self.grid = torch.zeros(res, res, res, device=self.device)
-        self.binary_grid = torch.ones(res, res, res, dtype=torch.bool, device=self.device)
-        self.step_count = 0
         self._scalars = self._g_net_scalars[N_PARAMS:]
         self._loss_ring, self._grad_calls = torch.zeros(32768, 2, device=self.device), -1
-        self._normsq_ws = ops.normsq_ws(self.device)
         assert (3 * nd) % 4 == 0
         self._tv_codes = torch.empty((total + 3) // 4, dtype=torch.uint8, device=self.device)   # two-bit signs of the TV terms
-        self._ws: Dict[str, Tensor] = {}
-        self._hash_ws = None
-        self._hash_ws_tables = None
-        self._hash_ws_probes = None
         from .specbwd import SpeculativeScatter
         on = bool(cfg.get("speculative_hash_backward", True)) and not os.environ.get("NERF_NO_SPECULATIVE_BWD")      # env: A/B aid
         self.spec_c, self.spec_d = SpeculativeScatter(on), SpeculativeScatter(on)
-        self._counter = 0
         self.repack()
 
     # -- parameters ------------------------------------------------------------------------------------------
@@ -349,69 +313,41 @@ class DualHashEngine:
         pack(self.net, self.packed)
         ops.f32_to_f16(self.tables, self.tables_h)
 
+    @staticmethod
+    def slice_table():
+        """(key, 'net', offset, shape) of every network parameter inside the flat vector (the four grids: load_from_model)"""
+        return [(key, "net", off, (cnt,)) for key, off, cnt in MODULE_SLICES]
+
     def load_from_model(self, model) -> None:
-        sd = dict(model.named_parameters())
         with torch.no_grad():
-            for key, off, cnt in MODULE_SLICES:
-                self.net[off:off + cnt].copy_(sd[key].reshape(-1))
             for k, name in enumerate(GRIDS):
                 self.table(k).copy_(getattr(model, name).encoding.params)
-        self.repack()
+        super().load_from_model(model)
 
     def copy_to_model(self, model) -> None:
-        sd = dict(model.named_parameters())
+        super().copy_to_model(model)
         with torch.no_grad():
-            for key, off, cnt in MODULE_SLICES:
-                sd[key].copy_(self.net[off:off + cnt].view(sd[key].shape))
             for k, name in enumerate(GRIDS):
                 getattr(model, name).encoding.params.copy_(self.table(k))
 
-    def lr(self, mult: float = 1.0) -> float:
-        """CosineAnnealingLR of a group whose initial rate is mult * learning_rate (run.py:1684-1743)"""
-        base = self.lr0 * mult
-        return self.eta_min + (base - self.eta_min) * (1 + math.cos(math.pi * self.step_count / self.t_max)) / 2
-
     def _workspace(self, n: int, which: str = "batch") -> Workspace:
-        """the step's workspace laid out in ONE grow-only buffer per use (data batch / regulariser probes): the active-point
-        count changes almost every step, a buffer per count would churn hundreds of MB through the allocator"""
-        need = Workspace.bytes(n)
-        buf = self._ws.get(which)
-        if buf is None or buf.numel() < need:
-            self._ws.pop(which, None)                        # release before growing
-            buf = self._ws[which] = torch.empty(int(need * 1.25), dtype=torch.uint8, device=self.device)
-        return Workspace(n, self.device, buf=buf)
+        """the step's workspace laid out in one grow-only buffer per use (data batch / regulariser probes)"""
+        return Workspace(n, self.device, buf=self._buf(which, Workspace.bytes(n)))
 
     def _hash_scratch_tables(self, n: int, n_levels: int, n_tables: int) -> Tensor:
-        need = _lib.load().nerf_hash_encode_bwd_tables_workspace_bytes(n, n_levels, n_tables)
-        if self._hash_ws_tables is None or self._hash_ws_tables.numel() < need:
-            self._hash_ws_tables = None
-            self._hash_ws_tables = torch.empty(int(need * 1.25), dtype=torch.uint8, device=self.device)
-        return self._hash_ws_tables
+        return self._buf("hash_tables", _lib.load().nerf_hash_encode_bwd_tables_workspace_bytes(n, n_levels, n_tables))
 
     def _hash_scratch_probes(self, n: int, n_levels: int) -> Tensor:
         """the probes' (accumulating, counted) scatters: their own workspace -- the data batch's keep their bin estimates"""
-        need = ops.hash_encode_bwd_workspace_bytes(n, n_levels)
-        if self._hash_ws_probes is None or self._hash_ws_probes.numel() < need:
-            self._hash_ws_probes = None
-            self._hash_ws_probes = torch.empty(int(need * 1.25), dtype=torch.uint8, device=self.device)
-        return self._hash_ws_probes
+        return self._buf("hash_probes", ops.hash_encode_bwd_workspace_bytes(n, n_levels))
 
     def _hash_scratch(self, n: int, n_levels: int) -> Tensor:
-        need = ops.hash_encode_bwd_workspace_bytes(n, n_levels)
-        if self._hash_ws is None or self._hash_ws.numel() < need:
-            self._hash_ws = None
-            self._hash_ws = torch.empty(int(need * 1.25), dtype=torch.uint8, device=self.device)
-        return self._hash_ws
+        return self._buf("hash", ops.hash_encode_bwd_workspace_bytes(n, n_levels))
 
     def _tables_for_forward(self):
         return [self.table(k, half=True).view(-1, 2) for k in range(4)]
 
     # -- field -----------------------------------------------------------------------------------------------
-    def prepare_batch(self, rays_o: Tensor, rays_d: Tensor, n_samples: int, first_ray: int = 0):
-        self._counter += 1
-        return ops.sample_compact_async(rays_o, rays_d, self.near, self.far, n_samples, self.binary_grid, self.bound,
-                                        jitter=(self.seed, self._counter), first_ray=first_ray), self._counter
-
     def compute_gradients(self, rays_o: Tensor, rays_d: Tensor, target: Tensor, times: Tensor, n_samples: int, prepared=None,
                           first_ray: int = 0, bg: Optional[Tensor] = None, sync_grads_async=None, probes=None,
                           shard_grads: bool = False) -> Tensor:
@@ -439,16 +375,12 @@ class DualHashEngine:
             self.g_tables.zero_()
             loss = ((bg.expand(R, 3) - target) ** 2).mean().reshape(1)
         else:
-            lib = _lib.load()
             ws = self._workspace(n)
             x_def, t_def = sample_inputs(slots, pts, times, R, n_samples, self.std_x, self.std_t, self.seed, counter, first_ray)
             rgb, sigma, dx, xc = forward_chain(self.packed, self.net, self._tables_for_forward(), self.levels_d, self.levels_c, self.bound,
                                                pts, x_def, t_def, dirs, ws, True)
-            d_rgb, d_sigma, d_extra = torch.empty_like(rgb), torch.empty_like(sigma), torch.empty_like(dx)
-            _lib.check(lib.nerf_composite_mse_reg_bwd(P(rgb), P(sigma), P(slots), P(z), P(rays_d), P(bg), 1, P(target), 1.0 / (3 * R),
-                                                      P(dx), self.reg_weight / (3 * R), R, n_samples, None, None, P(loss), P(reg),
-                                                      P(d_rgb), P(d_sigma), P(d_extra), P(ops.sum_ws(self.device)), ops._stream()),
-                       "nerf_composite_mse_reg_bwd")
+            d_rgb, d_sigma, d_extra = composite_mse_reg_bwd(rgb, sigma, slots, z, rays_d, bg, target, dx, self.reg_weight, R, n_samples, loss,
+                                                            reg, ops.sum_ws(self.device))
             g_tabs = [self.g_table(k) for k in range(4)]
             backward_chain(self.packed, self.net, self.table(3, half=True), self.levels_d, self.levels_c, self.bound, pts if x_def is None else x_def,
                            xc, ws, rgb, sigma, d_rgb, d_sigma, d_extra, self.g_net, g_tabs, hash_ws=self._hash_scratch, overwrite=True, tables_ws=self._hash_scratch_tables, extra_in_place=True,
@@ -468,9 +400,7 @@ class DualHashEngine:
                 for k in (3, 0, 1, 2):                       # the order and sizes of the busy ranks' collectives
                     reduce(self.g_table(k))
             reduce(self.g_net)
-            for h in handles:
-                if h is not None:
-                    h.wait()
+            wait_all(handles)
         return loss[0]
 
     def _probe_regularisers(self, probes) -> None:
@@ -545,23 +475,19 @@ class DualHashEngine:
         """apply_gradients with the table groups sharded over the ranks: this rank's slice of TV + norm and of clip + AdamW, ONE
         scalar all-reduce for the squared norm (the networks' part is added by rank 0), the networks stepped on every rank"""
         import torch.distributed as dist
-        lib, st, sh = _lib.load(), ops._stream(), self.shard
+        sh = self.shard
         scale = 1.0 / self.world_size
         normsq = self._normsq_ws
         sh.accumulate_normsq(normsq, scale, first=True)         # the first piece stores the norm: no zeroing launch
         if sh.rank == 0:
-            _lib.check(lib.nerf_tv_normsq_codes(P(self.net), P(self.g_net), N_PARAMS, 1, 0.0, scale, P(normsq), 1 if sh.pieces else 0, None, st),
-                       "nerf_tv_normsq_codes")
+            normsq_flat(self.net, self.g_net, N_PARAMS, scale, normsq, first=not sh.pieces)
         if self.world_size > 1:
             dist.all_reduce(normsq[0:1], op=dist.ReduceOp.SUM)      # every rank: the same bits, hence the same clip coefficient
         lr_t, lr_n, lr_s = self.lr(2.0), self.lr(1.0), self.lr(5.0)
         self.step_count += 1
         step = self.step_count
         sh.adamw(normsq, step, lr_t, self.wd, self.max_norm, scale)
-        m, v = self.state["net"]
-        _lib.check(lib.nerf_adamw_clip_step_tv(P(self.net), P(self.g_net), P(m), P(v), N_PARAMS, step, lr_n, 0.9, 0.999, 1e-8, self.wd,
-                                               P(normsq), self.max_norm, scale, None, 0, 0.0, 0, 0.0, 0, SCALE, lr_s, None, st),
-                   "nerf_adamw_clip_step_tv")
+        clip_adamw_flat(self.net, self.g_net, self.state["net"], N_PARAMS, step, lr_n, self.wd, normsq, self.max_norm, scale, SCALE, lr_s)
         sh.exchange()                             # neighbours' edge elements (next step's TV terms), fp16 copy of every slice
         pack(self.net, self.packed)
 
@@ -584,7 +510,7 @@ class DualHashEngine:
                    "nerf_tv_normsq_codes")          # the first group STORES the norm (no zeroing launch), the others add
         _lib.check(lib.nerf_tv_normsq_codes(P(self.table(3)), P(self.g_table(3)), n_can, 1, self.tv_canon, scale, P(normsq), 1,
                                             P(codes[3 * n_def // 4:]), st), "nerf_tv_normsq_codes")
-        _lib.check(lib.nerf_tv_normsq_codes(P(self.net), P(self.g_net), N_PARAMS, 1, 0.0, scale, P(normsq), 1, None, st), "nerf_tv_normsq_codes")
+        normsq_flat(self.net, self.g_net, N_PARAMS, scale, normsq, first=False)
         lr_t, lr_n, lr_s = self.lr(2.0), self.lr(1.0), self.lr(5.0)      # the rates of THIS step: scheduler.step() follows optimizer.step()
         self.step_count += 1
         step = self.step_count
@@ -593,18 +519,11 @@ class DualHashEngine:
         _lib.check(lib.nerf_adamw_clip_step_tv(P(self.tables), P(self.g_tables), P(m), P(v), total, step, lr_t, 0.9, 0.999, 1e-8, self.wd,
                                                P(normsq), self.max_norm, scale, P(codes), 3 * n_def, self.tv_disp, n_def, self.tv_canon, n_can,
                                                0, 0.0, P(self.tables_h), st), "nerf_adamw_clip_step_tv")
-        m, v = self.state["net"]
-        _lib.check(lib.nerf_adamw_clip_step_tv(P(self.net), P(self.g_net), P(m), P(v), N_PARAMS, step, lr_n, 0.9, 0.999, 1e-8, self.wd,
-                                               P(normsq), self.max_norm, scale, None, 0, 0.0, 0, 0.0, 0, SCALE, lr_s, None, st),
-                   "nerf_adamw_clip_step_tv")
+        clip_adamw_flat(self.net, self.g_net, self.state["net"], N_PARAMS, step, lr_n, self.wd, normsq, self.max_norm, scale, SCALE, lr_s)
         pack(self.net, self.packed)
 
-    def train_step(self, rays_o, rays_d, target, times, n_samples, prepared=None, first_ray: int = 0, bg=None, sync_grads_async=None,
-                   probes=None) -> Tensor:
-        loss = self.compute_gradients(rays_o, rays_d, target, times, n_samples, prepared=prepared, first_ray=first_ray, bg=bg,
-                                      sync_grads_async=sync_grads_async, probes=probes, shard_grads=self.shard is not None)
-        self.apply_gradients()
-        return loss
+    def train_step(self, *args, **kwargs) -> Tensor:
+        return super().train_step(*args, shard_grads=self.shard is not None, **kwargs)
 
     # -- occupancy grid / rendering ----------------------------------------------------------------------------
     @torch.no_grad()
@@ -621,35 +540,10 @@ class DualHashEngine:
         """DensityGrid.update of mode part4 (reference src/renderer.py:65-86, 122-125): density on the lattice at the time
         anchors 0, 0.5, 1, element-wise maximum, running maximum against the decayed history."""
         res = self.grid.shape[0]
-        pts = ops.grid_lattice(self.bound, res, self.device)
+        lattice = self._lattice()
         sig = torch.zeros(res ** 3, device=self.device)
-        zeros = torch.zeros(2 ** 18, 3, device=self.device)
         for anchor in (0.0, 0.5, 1.0):
-            for i in range(0, pts.shape[0], 2 ** 18):
-                p = pts[i:i + 2 ** 18]
-                s = self.field(p, zeros[:p.shape[0]], torch.full((p.shape[0],), anchor, device=self.device))[1]
-                torch.maximum(sig[i:i + 2 ** 18], s, out=sig[i:i + 2 ** 18])
+            for i, s in self.lattice_density(lattice, anchor):
+                torch.maximum(sig[i:i + s.shape[0]], s, out=sig[i:i + s.shape[0]])
         self.binary_grid, ratio = ops.grid_threshold(sig.view(res, res, res), self.grid_threshold, prev=self.grid, decay=decay)
         return ratio
-
-    @torch.no_grad()
-    def render_rays(self, rays_o: Tensor, rays_d: Tensor, times: Tensor, n_samples: int, bg: Optional[Tensor] = None):
-        z, slots, pts, dirs = ops.sample_compact(rays_o, rays_d, self.near, self.far, n_samples, self.binary_grid, self.bound)
-        R = rays_o.shape[0]
-        bg = self.bg if bg is None else bg
-        if pts.shape[0] == 0:
-            return bg.expand(R, 3).clone(), torch.zeros(R, device=self.device), torch.zeros(R, device=self.device)
-        _, t_def = sample_inputs(slots, pts, times.expand(R, 1) if times.numel() == 1 else times, R, n_samples)
-        ws = self._workspace(pts.shape[0])
-        rgb, sigma, _, _ = forward_chain(self.packed, self.net, self._tables_for_forward(), self.levels_d, self.levels_c, self.bound, pts,
-                                         None, t_def, dirs, ws, False)
-        return ops.composite_indexed(rgb, sigma, slots, z, rays_d, bg)
-
-    @torch.no_grad()
-    def render_image(self, rays_o: Tensor, rays_d: Tensor, time: Tensor, n_samples: int, chunk: int = 65536) -> Tensor:
-        shape = rays_o.shape[:-1]
-        o, d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
-        out = torch.empty(o.shape[0], 3, device=self.device)
-        for i in range(0, o.shape[0], chunk):
-            out[i:i + chunk] = self.render_rays(o[i:i + chunk], d[i:i + chunk], time.reshape(1, 1).to(self.device), n_samples)[0]
-        return out.view(*shape, 3)
