@@ -189,7 +189,7 @@ def composite(rgb: Tensor, sigma: Tensor, z: Tensor, rays_d: Tensor,
     step = step * torch.norm(rays_d[:, None, :], dim=-1)
     alpha = 1.0 - torch.exp(-sigma * step)
     trans = torch.cumprod(
-        torch.cat([torch.ones((alpha.shape[0], 1)), 1.0 - alpha + 1e-10], dim=-1), dim=-1)[:, :-1]
+        torch.cat([torch.ones((alpha.shape[0], 1), dtype=alpha.dtype), 1.0 - alpha + 1e-10], dim=-1), dim=-1)[:, :-1]
     w = alpha * trans
     rgb_map = torch.sum(w[..., None] * rgb, dim=-2)
     depth = torch.sum(w * z, dim=-1)
@@ -201,6 +201,55 @@ def composite(rgb: Tensor, sigma: Tensor, z: Tensor, rays_d: Tensor,
     if return_weights:
         return rgb_map, depth, acc, w
     return rgb_map, depth, acc
+
+
+def composite_mse_reg(rgb: Tensor, sigma: Tensor, z: Tensor, rays_d: Tensor, bg: Optional[Tensor], target: Tensor,
+                      loss_weight: float, extra: Optional[Tensor] = None, reg_weight: float = 0.0,
+                      slots: Optional[Tensor] = None, dtype: torch.dtype = torch.float64) -> Dict[str, Tensor]:
+    """float64 restatement of the training step around the compositing: the compact rows rgb [n,3] / sigma [n] /
+    extra [n,3] are scattered through ``slots`` [R,S] (row of each sample, < 0: skipped) into zeros (reference
+    renderer.py:328-343; without a map the arrays are the dense [R,S] ones), composited, and
+    loss = loss_weight * sum (pixel - target)^2, reg = reg_weight * sum |m|^2 with m = sum_s w_s extra_s
+    (renderer.py:363-380, run.py:1838).  Returns pixel [R,3], m [R,3], loss, reg and, by autograd of loss + reg, d_rgb /
+    d_sigma / d_extra of the compact rows (zero where no sample maps to a row), ``mapped`` (rows some sample maps to) and
+    ``amax`` = max(|d_rgb rgb (1 - rgb)|, |d_sigma| where sigma > 0), the vanilla decoder's output-layer derivative.
+    ``dtype`` = torch.float32 gives the same statement in fp32: the yardstick of what fp32 can reach on these inputs."""
+    f = dtype
+    R, S = z.shape
+    rgb_c = rgb.detach().to(f).reshape(-1, 3).clone().requires_grad_(True)
+    sig_c = sigma.detach().to(f).reshape(-1).clone().requires_grad_(True)
+    ext_c = None if extra is None else extra.detach().to(f).reshape(-1, 3).clone().requires_grad_(True)
+    mapped = torch.ones(rgb_c.shape[0], dtype=torch.bool)
+    if slots is None:
+        rgb_d, sig_d, ext_d = rgb_c, sig_c, ext_c
+    else:
+        sl = slots.reshape(-1).long()
+        act = sl >= 0
+        mapped = torch.zeros(rgb_c.shape[0], dtype=torch.bool)
+        mapped[sl[act]] = True
+        rgb_d = torch.zeros(R * S, 3, dtype=f)
+        sig_d = torch.zeros(R * S, dtype=f)
+        rgb_d[act] = rgb_c[sl[act]]
+        sig_d[act] = sig_c[sl[act]]
+        if ext_c is not None:
+            ext_d = torch.zeros(R * S, 3, dtype=f)
+            ext_d[act] = ext_c[sl[act]]
+    bg64 = None if bg is None else bg.detach().to(f)
+    pixel, _, _, w = composite(rgb_d.view(R, S, 3), sig_d.view(R, S), z.detach().to(f), rays_d.detach().to(f), bg64,
+                               return_weights=True)
+    loss = loss_weight * ((pixel - target.detach().to(f)) ** 2).sum()
+    if ext_c is not None:
+        m = (w[..., None] * ext_d.view(R, S, 3)).sum(dim=1)
+        reg = reg_weight * (m ** 2).sum()
+    else:
+        m, reg = torch.zeros(R, 3, dtype=f), torch.zeros((), dtype=f)
+    (loss + reg).backward()
+    d_rgb, d_sigma = rgb_c.grad, sig_c.grad
+    d_extra = None if ext_c is None else (ext_c.grad if ext_c.grad is not None else torch.zeros_like(ext_c))
+    rgb0, sig0 = rgb_c.detach(), sig_c.detach()
+    amax = max(float((d_rgb * rgb0 * (1.0 - rgb0)).abs().max()), float((d_sigma.abs() * (sig0 > 0)).max()))
+    return {"pixel": pixel.detach(), "m": m.detach(), "loss": float(loss.detach()), "reg": float(reg.detach()), "d_rgb": d_rgb,
+            "d_sigma": d_sigma, "d_extra": d_extra, "mapped": mapped, "amax": amax}
 
 
 # ----------------------------------------------------------------------------
@@ -437,6 +486,51 @@ def adam_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float,
     bc2 = 1.0 - beta2 ** step
     denom = (v.sqrt() / math.sqrt(bc2)).add_(eps)
     p.addcdiv_(m, denom, value=-lr / bc1)
+
+
+def tv_clip_adamw(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float, beta1: float = 0.9,
+                  beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0,
+                  tables: Sequence[Tuple[int, int, float]] = (), grad_scale: float = 1.0, max_norm: float = 0.0,
+                  lr_split: int = 0, lr_hi: float = 0.0, normsq_total: Optional[float] = None,
+                  dtype: torch.dtype = torch.float64) -> Dict[str, Tensor]:
+    """float64 restatement of one step of TV-L1 + global-norm clip + AdamW over a flat vector (reference
+    run.py:611-630).  ``tables`` = [(offset, elems, tv_weight)]: each adds the gradient of
+    tv_weight * mean|t[1:] - t[:-1]| over its own elements, tv_weight / (elems - 1) * (s[i-1] - s[i]) with
+    s[i] = sign(t[i+1] - t[i]) and s = 0 outside the table (no pair across a seam).  The data gradient is scaled by
+    ``grad_scale``, the TV term is not.  ONE squared norm over the sum (or ``normsq_total`` when this vector is one of
+    several groups under one clip); coef = min(1, max_norm / (sqrt(normsq) + 1e-6)) (max_norm <= 0: no clip); then
+    ``adam_step`` with ``lr`` below ``lr_split`` and ``lr_hi`` from it on (lr_split <= 0: ``lr`` everywhere).
+    Returns new p / m / v, ``grad`` (g * grad_scale + TV, before the clip), this vector's ``normsq``, ``coef`` and
+    ``codes``: uint8 [(n + 3) // 4], element i's 1 + s[i] in bits 2 (i % 4) .. of byte i // 4, zero bits past n.
+    ``dtype`` = torch.float32: the same step in plain fp32, the yardstick of what fp32 can reach on these inputs."""
+    f = dtype
+    p, g, m, v = (t.detach().to(f).reshape(-1).clone() for t in (p, g, m, v))
+    n = p.numel()
+    s_cur = torch.zeros(n, dtype=f)
+    tv = torch.zeros(n, dtype=f)
+    for off, elems, w in tables:
+        if elems < 2:
+            continue
+        t = p[off:off + elems]
+        s = torch.sign(t[1:] - t[:-1])
+        zero = torch.zeros(1, dtype=f)
+        s_cur[off:off + elems] = torch.cat([s, zero])
+        tv[off:off + elems] = (w / (elems - 1)) * (torch.cat([zero, s]) - torch.cat([s, zero]))
+    grad = g * grad_scale + tv
+    normsq = float((grad * grad).sum())
+    coef = 1.0
+    if max_norm > 0.0:
+        coef = min(1.0, max_norm / (math.sqrt(normsq if normsq_total is None else normsq_total) + 1e-6))
+    clipped = grad * coef
+    cut = n if lr_split <= 0 else min(int(lr_split), n)
+    for a, b, rate in ((0, cut, lr), (cut, n, lr_hi)):
+        if b > a:
+            adam_step(p[a:b], clipped[a:b], m[a:b], v[a:b], step, rate, beta1, beta2, eps, weight_decay)
+    code = torch.zeros(4 * ((n + 3) // 4), dtype=torch.int64)
+    code[:n] = (s_cur + 1.0).to(torch.int64)
+    code = code.view(-1, 4)
+    codes = (code[:, 0] | (code[:, 1] << 2) | (code[:, 2] << 4) | (code[:, 3] << 6)).to(torch.uint8)
+    return {"p": p, "m": m, "v": v, "grad": grad, "normsq": normsq, "coef": coef, "codes": codes}
 
 
 def cosine_lr(base_lr: float, eta_min: float, step: int, t_max: int) -> float:

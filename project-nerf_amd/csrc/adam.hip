@@ -225,7 +225,10 @@ constexpr int kTvFastThreads = 1024;
 template <bool TV>
 __global__ void __launch_bounds__(kTvFastThreads)
 tv_normsq_codes_fast_kernel(const float* __restrict__ p, const float* __restrict__ g, int n4, float tv_scale, float grad_scale,
-                            float* __restrict__ normsq, int seg, uint8_t* __restrict__ codes, int halo, int accumulate) {
+                            float* __restrict__ normsq, int seam1, int seam2, int seam3, uint8_t* __restrict__ codes, int halo,
+                            int accumulate) {
+  // seam1..3: first element of the second, third and fourth table, -1 for a table that does not exist (computed on the host in
+  // 64 bits: 2 * seg and 3 * seg do not fit an int for one table of 2^30 elements or more)
   // halo (a PIECE of one table: the sharded optimiser's slice): bit 0 -- p[-1] belongs to the same table, bit 1 -- p[n] does; the
   // piece's first TV term then reaches back to p[-1] (its sign is also left in codes[-1] for the AdamW pass), its last one on to p[n]
   constexpr int kU = 4;
@@ -252,9 +255,9 @@ tv_normsq_codes_fast_kernel(const float* __restrict__ p, const float* __restrict
       if (q >= n4) break;
       float g0, g1, g2, g3;
       if (TV) {
-        const bool first = (e0 == 0 && !(halo & 1)) || e0 == seg || e0 == 2 * seg || e0 == 3 * seg;
+        const bool first = (e0 == 0 && !(halo & 1)) || e0 == seam1 || e0 == seam2 || e0 == seam3;
         const int e4 = e0 + 4;
-        const bool last = (e4 == n && !(halo & 2)) || (e4 != n && (e4 == seg || e4 == 2 * seg || e4 == 3 * seg));
+        const bool last = (e4 == n && !(halo & 2)) || (e4 != n && (e4 == seam1 || e4 == seam2 || e4 == seam3));
         const int s_in = first ? 0 : (int)sgn(a[u][0] - lo[u]), s0 = (int)sgn(a[u][1] - a[u][0]), s1 = (int)sgn(a[u][2] - a[u][1]),
                   s2 = (int)sgn(a[u][3] - a[u][2]), s3 = last ? 0 : (int)sgn(hi[u] - a[u][3]);
         g0 = b[u][0] * grad_scale + tv_scale * (float)(s_in - s0);
@@ -262,7 +265,10 @@ tv_normsq_codes_fast_kernel(const float* __restrict__ p, const float* __restrict
         g2 = b[u][2] * grad_scale + tv_scale * (float)(s1 - s2);
         g3 = b[u][3] * grad_scale + tv_scale * (float)(s2 - s3);
         codes[q] = (uint8_t)((s0 + 1) | ((s1 + 1) << 2) | ((s2 + 1) << 4) | ((s3 + 1) << 6));
-        if (q == 0 && (halo & 1)) codes[-1] = (uint8_t)((s_in + 1) << 6);      // the sign the AdamW pass reads as the piece's s[-1]
+        // the sign the AdamW pass reads as the piece's s[-1]: the top code of the byte before the piece.  Its other three codes are kept:
+        // where the pieces of one table share one code buffer they belong to the piece before (same stream: whichever ran last leaves the
+        // same top code)
+        if (q == 0 && (halo & 1)) codes[-1] = (uint8_t)((codes[-1] & 0x3Fu) | ((s_in + 1) << 6));
       } else {
         g0 = b[u][0] * grad_scale; g1 = b[u][1] * grad_scale; g2 = b[u][2] * grad_scale; g3 = b[u][3] * grad_scale;
       }
@@ -511,12 +517,14 @@ extern "C" int nerf_tv_normsq_codes(const float* params, const float* grads, int
   const int64_t fcap = nerf::options().tv_blocks > 0 && nerf::options().tv_blocks <= 4096 ? nerf::options().tv_blocks : n_cu;
   if (fblocks > fcap) fblocks = fcap;
   if (fblocks < 1) fblocks = 1;
+  int seam[3];                            // k * seg < n < 2^31 for every table k that exists
+  for (int k = 1; k <= 3; ++k) seam[k - 1] = k < n_tables ? (int)(k * seg) : -1;
   if (fast && tv_scale != 0.0f)
     hipLaunchKernelGGL(nerf::tv_normsq_codes_fast_kernel<true>, dim3((int)fblocks), dim3(nerf::kTvFastThreads), 0, nerf::as_stream(stream),
-                       params, grads, (int)(n / 4), tv_scale, grad_scale, normsq_dev, (int)seg, codes, 0, accumulate);
+                       params, grads, (int)(n / 4), tv_scale, grad_scale, normsq_dev, seam[0], seam[1], seam[2], codes, 0, accumulate);
   else if (fast)
     hipLaunchKernelGGL(nerf::tv_normsq_codes_fast_kernel<false>, dim3((int)fblocks), dim3(nerf::kTvFastThreads), 0, nerf::as_stream(stream),
-                       params, grads, (int)(n / 4), 0.0f, grad_scale, normsq_dev, (int)seg, codes, 0, accumulate);
+                       params, grads, (int)(n / 4), 0.0f, grad_scale, normsq_dev, seam[0], seam[1], seam[2], codes, 0, accumulate);
   else
     hipLaunchKernelGGL(nerf::tv_normsq_codes_kernel, dim3((int)blocks), dim3(256), 0, nerf::as_stream(stream), params, grads, n, tv_scale,
                        grad_scale, normsq_dev, seg, codes, accumulate);
@@ -551,7 +559,7 @@ extern "C" int nerf_adamw_clip_step_tv(float* params, const float* grads, float*
 // data-parallel engines: every rank steps its slice of the flat table buffer).  halo bit 0: params[-1] belongs to the same table and
 // holds its current value, bit 1: params[n] does -- the TV terms at the piece's ends then equal the whole-table pass.  tv_codes points
 // at the piece's first code byte inside a buffer that has at least one byte before it (codes[-1] receives the sign of
-// params[0] - params[-1]).  n a multiple of 4, 16-byte aligned pointers.
+// params[0] - params[-1] in its top two bits; its other bits are kept).  n a multiple of 4, 16-byte aligned pointers.
 extern "C" int nerf_tv_normsq_codes_piece(const float* params, const float* grads, int64_t n, int64_t table_elems, int halo, float tv_weight,
                                           float grad_scale, float* normsq_dev, int accumulate, void* tv_codes, nerf_stream_t stream) {
   NERF_REQUIRE(n >= 0 && normsq_dev && table_elems >= n && halo >= 0 && halo <= 3, "nerf_tv_normsq_codes_piece: bad arguments");
@@ -570,10 +578,10 @@ extern "C" int nerf_tv_normsq_codes_piece(const float* params, const float* grad
   if (fblocks > n_cu) fblocks = n_cu;
   if (tv_scale != 0.0f)
     hipLaunchKernelGGL(nerf::tv_normsq_codes_fast_kernel<true>, dim3((int)fblocks), dim3(nerf::kTvFastThreads), 0, nerf::as_stream(stream),
-                       params, grads, (int)(n / 4), tv_scale, grad_scale, normsq_dev, (int)n, static_cast<uint8_t*>(tv_codes), halo, accumulate);
+                       params, grads, (int)(n / 4), tv_scale, grad_scale, normsq_dev, -1, -1, -1, static_cast<uint8_t*>(tv_codes), halo, accumulate);
   else
     hipLaunchKernelGGL(nerf::tv_normsq_codes_fast_kernel<false>, dim3((int)fblocks), dim3(nerf::kTvFastThreads), 0, nerf::as_stream(stream),
-                       params, grads, (int)(n / 4), 0.0f, grad_scale, normsq_dev, (int)n, static_cast<uint8_t*>(tv_codes), 0, accumulate);
+                       params, grads, (int)(n / 4), 0.0f, grad_scale, normsq_dev, -1, -1, -1, static_cast<uint8_t*>(tv_codes), 0, accumulate);
   return nerf::check_launch("nerf_tv_normsq_codes_piece");
 }
 

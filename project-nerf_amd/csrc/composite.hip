@@ -532,5 +532,4 @@ extern "C" int nerf_composite_mse_reg_bwd(const float* rgb, const float* sigma, 
              reg_accum, extra_map, reinterpret_cast<unsigned*>(sum_ws));
   if (int rc = check_launch("nerf_composite_mse_reg_bwd"); rc != NERF_OK) return rc;
   return finish_sums(sum_ws, grid.x, loss_accum, reg_accum, nullptr, stream);
-  return check_launch("nerf_composite_mse_reg_bwd");
 }

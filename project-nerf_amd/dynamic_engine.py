@@ -35,7 +35,7 @@ def sample_inputs(slots: Optional[Tensor], pts: Tensor, times: Tensor, n_rays: i
 def composite_mse_reg_bwd(rgb: Tensor, sigma: Tensor, slots: Tensor, z: Tensor, rays_d: Tensor, bg: Tensor, target: Tensor, dx: Tensor,
                           reg_weight: float, n_rays: int, n_samples: int, loss: Tensor, reg: Tensor, sum_ws: Tensor):
     """Compositing of the indexed samples onto ``bg`` + MSE against ``target`` + reg_weight * mean(mean_delta_x^2) and their
-    backward in one kernel: the RGB loss and the regulariser (before its weight) go to the one-element ``loss`` / ``reg``
+    backward in one kernel: the RGB loss and the WEIGHTED regulariser (reg_weight * mean(mean_delta_x^2), as the header states) are ADDED to the one-element ``loss`` / ``reg``
     (``sum_ws``: ops.sum_ws of the engine's device, scratch of their ordered sums); returns (d_rgb [n,3], d_sigma [n], d_dx [n,3])."""
     d_rgb, d_sigma, d_dx = torch.empty_like(rgb), torch.empty_like(sigma), torch.empty_like(dx)
     _lib.check(_lib.load().nerf_composite_mse_reg_bwd(P(rgb), P(sigma), P(slots), P(z), P(rays_d), P(bg), 1, P(target), 1.0 / (3 * n_rays),

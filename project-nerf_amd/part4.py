@@ -368,7 +368,7 @@ class DualHashEngine(GridEngine):
         if slot % (ring // 2) == 0 and self._grad_calls > 0:
             self._loss_ring[slot:slot + ring // 2].zero_()
         loss, reg = self._loss_ring[slot, 0:1], self._loss_ring[slot, 1:2]
-        self.last_reg = reg[0]                 # displacement regulariser of this batch (before its weight), a view like the loss
+        self.last_reg = reg[0]                 # displacement regulariser of this batch (times its weight), a view like the loss
         handles = []
         reduce = (lambda view: handles.append(sync_grads_async(view))) if sync_grads_async is not None else (lambda view: None)
         if n == 0:

@@ -182,6 +182,13 @@ def test_composite_mse_bwd_equals_separate_kernels_and_torch_mse(ops, S, bg_kind
     np.testing.assert_allclose(d_rgb.cpu().numpy(), r1.grad.cpu().numpy(), rtol=1e-5, atol=1e-10)
     ref = s1.grad.cpu().numpy()
     assert np.max(np.abs(d_sigma.cpu().numpy() - ref) / (np.abs(ref).max(axis=1, keepdims=True) + 1e-20)) < 2e-5
+    # where the far sample's density is exactly zero (every second ray) its derivative is of order 1e9 (interval 1e10) and the
+    # scale above hides every other sample of that ray: the others again under their own maximum, the far sample by its own
+    # relative error (tests/test_gpu_step_tail.py has the float64 version of both)
+    got = d_sigma.cpu().numpy()
+    assert int((sig[:, -1] == 0).sum()) >= R // 4
+    assert np.max(np.abs(got[:, :-1] - ref[:, :-1]) / (np.abs(ref[:, :-1]).max(axis=1, keepdims=True) + 1e-20)) < 2e-5
+    assert np.max(np.abs(got[:, -1] - ref[:, -1]) / (np.abs(ref[:, -1]) + 1e-20)) < 2e-5
     g_out = torch.cat([(r1.grad * r1 * (1 - r1)).detach().abs().flatten(), (s1.grad * (s1 > 0)).detach().abs().flatten()])
     np.testing.assert_allclose(float(scal[1]), float(g_out.max()), rtol=1e-4)
 
