@@ -41,7 +41,8 @@ extern "C" {
  * nerf_composite_mse_bwd / nerf_composite_mse_reg_bwd gained `sum_ws`; the imlp / Part 4 workspaces grew (partial tiles);
  * option "deterministic" and nerf_sample_compact_ordered are new. */
 /* 4: the Part 3 canonical decoder entries nerf_p3_canon_* are new. */
-#define NERF_ABI_VERSION 4
+/* 5: the Part 1 image-fit chain entries nerf_p1_* are new. */
+#define NERF_ABI_VERSION 5
 
 typedef void* nerf_stream_t;
 
@@ -724,6 +725,32 @@ int nerf_p3_canon_fwd(const void* packed, void* workspace, const float* x, const
 int nerf_p3_canon_bwd(const void* packed, void* workspace, const float* x, const float* rgb, const float* sigma,
                       const float* d_rgb, const float* d_sigma, int64_t n, int time_dim, float* grads_f32, float* d_x,
                       nerf_stream_t stream);
+
+/* ---- Part 1 image-fit chain (csrc/p1fit.hip) ---------------------------------------------------------------------------
+ * Replaces, for mode part1_fourier, the field of NeuralField (reference src/core.py:25-34: FourierRepresentation of the 2-D
+ * coordinate, src/embeddings.py:22-32, into StandardMLP, src/decoders.py:6-26) and the loop body of run_part1 (reference
+ * run.py:178-190: nn.MSELoss, loss.backward()):
+ *   code(x) (2 + 4 L_embed columns; use_pe 0 or L_embed 0: the 2 raw ones) -> hidden (ReLU) x layers -> 3, sigmoid;
+ *   loss = mean((y - target)^2) over n * 3 values.
+ * Compiled: hidden 64 / 128 / 256, layers 1..8, L_embed 0..15; anything else returns NERF_ENOSYS (sizes: 0, count: -1).
+ * params_f32 [nerf_p1_param_count(...)] = decoder.net.{0,2,...}.{weight,bias} concatenated ([out,in] row-major).
+ * bf16 MFMA operands and training images, fp32 accumulation; the two raw coordinate columns enter as a hi + lo bf16 pair. */
+int64_t nerf_p1_param_count(int L_embed, int use_pe, int hidden, int layers);
+size_t nerf_p1_packed_bytes(int L_embed, int use_pe, int hidden, int layers);
+size_t nerf_p1_workspace_bytes(int64_t n, int L_embed, int use_pe, int hidden, int layers);
+int nerf_p1_pack(const float* params_f32, int L_embed, int use_pe, int hidden, int layers, void* packed, nerf_stream_t stream);
+/* inference: y [n,3] at coords [n,2] */
+int nerf_p1_fwd(const void* packed, const float* coords, int64_t n, int L_embed, int use_pe, int hidden, int layers, float* y,
+                nerf_stream_t stream);
+/* One training forward + loss + backward on rows idx [n] (int64; NULL: rows 0..n) of coords [N,2] / target [N,3]: the gradient of
+ * the mean squared error is WRITTEN to grads_f32 [nerf_p1_param_count(...)] and the loss to *loss_accum (device memory).  The
+ * workspace (nerf_p1_workspace_bytes(n, ...), 256-byte aligned) holds the training images, one loss partial per workgroup and
+ * the weight-gradient partial tiles.  No allocation, no host synchronisation; every sum is taken in a fixed order (partial tiles
+ * per chunk of samples, one reduction in chunk order; loss partials in workgroup order): the same bits on every run, with or
+ * without option "deterministic". */
+int nerf_p1_fwd_loss_bwd(const void* packed, void* workspace, const float* coords, const int64_t* idx, const float* target,
+                         int64_t n, int L_embed, int use_pe, int hidden, int layers, float* grads_f32, float* loss_accum,
+                         nerf_stream_t stream);
 
 #ifdef __cplusplus
 }

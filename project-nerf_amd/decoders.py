@@ -10,8 +10,10 @@ from .embeddings import ParamHolder
 
 class StandardMLP(BaseDecoder):
     """Part 1 image-fit MLP (reference src/decoders.py:6-26): Linear/ReLU x num_layers, Linear, Sigmoid.
-    Outside the volumetric hot path (SURVEY 8 scope): plain library GEMMs through torch.nn on the
-    device; only its Fourier features go through the HIP kernel."""
+    This module is the library-GEMM form (torch.nn on the device; only its Fourier features go through the HIP
+    kernel): inference, evaluation and any shape.  Training with ``engine: true`` runs the same network on the fused
+    HIP chain of part1.Part1Engine (csrc/p1fit.hip: hidden 64 / 128 / 256, 1..8 layers) and copies the weights back
+    into this module's state dict."""
 
     def __init__(self, input_dim, hidden_dim=256, output_dim=3, num_layers=3):
         super().__init__()

@@ -192,7 +192,27 @@ def run_part1(cfg, args):
         model.load_state_dict(torch.load(args.checkpoint, map_location=device)["model_state_dict"], strict=False)
     log_dir = os.path.join(cfg.get("log_dir", "output/"), "part1", os.path.splitext(os.path.basename(args.image))[0])
     os.makedirs(log_dir, exist_ok=True)
-    if not args.eval_only:
+    engine = None
+    if cfg.get("engine", False) and not args.eval_only:
+        # fused HIP training engine (project-nerf_amd/part1.py); a shape it is not compiled for keeps the module path
+        from project_nerf_amd import part1
+        why = part1.supported(cfg)
+        if why is None:
+            engine = part1.Part1Engine(cfg, device="cuda", lr=cfg["learning_rate"])
+            engine.load_from_model(model)
+            print(f">>> Part 1 on the fused HIP engine ({engine.params.numel()} parameters)")
+        else:
+            print(f">>> Part 1 engine not used: {why}; training on the module path")
+    if engine is not None:
+        bs = cfg.get("batch_size")
+        for epoch in range(1, cfg["epochs"] + 1):
+            idx = None if bs is None else torch.randint(0, coords.shape[0], (bs,), device=device)
+            loss = engine.train_step(coords, gt, idx)
+            if epoch % cfg.get("log_every", 100) == 0:
+                print(f">>> Epoch {epoch}/{cfg['epochs']} | Loss {loss.item():.6f} | PSNR {compute_psnr(loss.item()):.2f} dB")
+        engine.copy_to_model(model)
+        torch.save({"model_state_dict": model.state_dict(), "config": cfg}, os.path.join(log_dir, "model_final.pth"))
+    elif not args.eval_only:
         opt = torch.optim.Adam(model.parameters(), lr=cfg["learning_rate"])
         bs = cfg.get("batch_size")
         for epoch in range(1, cfg["epochs"] + 1):
@@ -205,7 +225,7 @@ def run_part1(cfg, args):
                 print(f">>> Epoch {epoch}/{cfg['epochs']} | Loss {loss.item():.6f} | PSNR {compute_psnr(loss.item()):.2f} dB")
         torch.save({"model_state_dict": model.state_dict(), "config": cfg}, os.path.join(log_dir, "model_final.pth"))
     with torch.no_grad():
-        pred = model(coords).clamp(0, 1)
+        pred = (engine.predict(coords) if engine is not None else model(coords)).clamp(0, 1)
     psnr = compute_psnr(torch.nn.functional.mse_loss(pred, gt).item())
     Image.fromarray((pred.cpu().numpy().reshape(h, w, 3) * 255 + 0.5).astype(np.uint8)).save(os.path.join(log_dir, "final.png"))
     print(f">>> Final PSNR: {psnr:.2f} dB")
