@@ -42,7 +42,8 @@ extern "C" {
  * option "deterministic" and nerf_sample_compact_ordered are new. */
 /* 4: the Part 3 canonical decoder entries nerf_p3_canon_* are new. */
 /* 5: the Part 1 image-fit chain entries nerf_p1_* are new. */
-#define NERF_ABI_VERSION 5
+/* 6: the vanilla NeRF decoder chain for non-default shapes, nerf_p2_*, is new. */
+#define NERF_ABI_VERSION 6
 
 typedef void* nerf_stream_t;
 
@@ -751,6 +752,40 @@ int nerf_p1_fwd(const void* packed, const float* coords, int64_t n, int L_embed,
 int nerf_p1_fwd_loss_bwd(const void* packed, void* workspace, const float* coords, const int64_t* idx, const float* target,
                          int64_t n, int L_embed, int use_pe, int hidden, int layers, float* grads_f32, float* loss_accum,
                          nerf_stream_t stream);
+
+/* ---- Vanilla NeRF decoder at non-default shapes (csrc/p2chain.hip) -------------------------------------------------------
+ * Replaces, for mode part2_nerf at a shape other than the default one (which keeps nerf_mlp_*), the field of NeuralField
+ * (reference src/core.py:36-55: FourierRepresentation of position and view direction, src/embeddings.py:22-32, into NeRFDecoder,
+ * src/decoders.py:29-87) and its part of loss.backward() (reference run.py:324-337):
+ *   pts_layers (ReLU; layer `skip` on [h | code(x)]) -> sigma_layer (ReLU) and feature_layer (linear) -> view_layer on
+ *   [f | code(v)] (ReLU) -> rgb_layer (sigmoid).
+ * Shape arguments, in this order: hidden, layers, skip, view, L_embed, L_dir.  Compiled: hidden 64 / 128 / 256, layers 2..8, skip
+ * 1..layers-1 or any value outside 0..layers-1 (no skip), view 64 / 128, L_embed 1..10, L_dir 0..4; anything else (skip 0
+ * included) returns NERF_ENOSYS with a nerf_last_error() text naming the key (sizes: 0, count: -1).
+ * params_f32 [nerf_p2_param_count(...)] = decoder.{pts_layers.0..layers-1, sigma_layer, feature_layer, view_layer,
+ * rgb_layer}.{weight,bias} concatenated ([out,in] row-major).  bf16 MFMA operands and training images, fp32 accumulation. */
+int64_t nerf_p2_param_count(int hidden, int layers, int skip, int view, int L_embed, int L_dir);
+size_t nerf_p2_packed_bytes(int hidden, int layers, int skip, int view, int L_embed, int L_dir);
+size_t nerf_p2_workspace_bytes(int64_t n, int hidden, int layers, int skip, int view, int L_embed, int L_dir);
+/* fp32 flat parameters -> bf16 fragment image + fp32 bias table (packed: nerf_p2_packed_bytes(...), 256-byte aligned) */
+int nerf_p2_pack(const float* params_f32, int hidden, int layers, int skip, int view, int L_embed, int L_dir, void* packed,
+                 nerf_stream_t stream);
+/* inference: rgb [n,3], sigma [n].  Ray mode (n_samples > 0, as nerf_mlp_fwd; reference src/renderer.py:288-299): rays_o / rays_d
+ * [n / n_samples, 3], z [n]: x = o + d z, v = d / |d| formed in registers.  Point mode (n_samples 0): rays_o = pts [n,3], rays_d =
+ * dirs [n,3], encoded as given; z is not read. */
+int nerf_p2_fwd(const void* packed, const float* rays_o, const float* rays_d, const float* z, int64_t n, int n_samples, int hidden,
+                int layers, int skip, int view, int L_embed, int L_dir, float* rgb, float* sigma, nerf_stream_t stream);
+/* the same forward (the same bits), keeping the layer images nerf_p2_bwd reads in the workspace (nerf_p2_workspace_bytes(n, ...),
+ * 256-byte aligned) */
+int nerf_p2_fwd_train(const void* packed, void* workspace, const float* rays_o, const float* rays_d, const float* z, int64_t n,
+                      int n_samples, int hidden, int layers, int skip, int view, int L_embed, int L_dir, float* rgb, float* sigma,
+                      nerf_stream_t stream);
+/* from d loss / d rgb [n,3], d sigma [n] (nerf_composite_mse_bwd) and the rgb / sigma of the last nerf_p2_fwd_train on this
+ * workspace: the gradient of every weight and bias WRITTEN to grads_f32 [nerf_p2_param_count(...)].  Transposed chain, then
+ * partial tiles per chunk of samples and one reduction in chunk order: no atomics, the same bits on every run.  Positions and
+ * directions are not learned: no gradient with respect to the codes. */
+int nerf_p2_bwd(const void* packed, void* workspace, const float* rgb, const float* sigma, const float* d_rgb, const float* d_sigma,
+                int64_t n, int hidden, int layers, int skip, int view, int L_embed, int L_dir, float* grads_f32, nerf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -136,6 +136,13 @@ PROTOTYPES = {
     "nerf_p1_pack": (i32, [c_ptr, i32, i32, i32, i32, c_ptr, c_ptr]),
     "nerf_p1_fwd": (i32, [c_ptr, c_ptr, i64, i32, i32, i32, i32, c_ptr, c_ptr]),
     "nerf_p1_fwd_loss_bwd": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, i64, i32, i32, i32, i32, c_ptr, c_ptr, c_ptr]),
+    "nerf_p2_param_count": (i64, [i32] * 6),
+    "nerf_p2_packed_bytes": (size_t, [i32] * 6),
+    "nerf_p2_workspace_bytes": (size_t, [i64] + [i32] * 6),
+    "nerf_p2_pack": (i32, [c_ptr] + [i32] * 6 + [c_ptr, c_ptr]),
+    "nerf_p2_fwd": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, i64, i32] + [i32] * 6 + [c_ptr, c_ptr, c_ptr]),
+    "nerf_p2_fwd_train": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, i64, i32] + [i32] * 6 + [c_ptr, c_ptr, c_ptr]),
+    "nerf_p2_bwd": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, i64] + [i32] * 6 + [c_ptr, c_ptr]),
     "nerf_tv_codes_bytes": (size_t, [i64]),
     "nerf_tv_normsq_codes": (i32, [c_ptr, c_ptr, i64, i32, f32, f32, c_ptr, i32, c_ptr, c_ptr]),
     "nerf_clip_adamw_small": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, i64, i32, f32, f32, f32, f32, f32, f32, f32, c_ptr, i32, c_ptr]),
@@ -148,7 +155,7 @@ PROTOTYPES = {
     "nerf_adamw_clip_step_shadow": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, i64, i32, f32, f32, f32, f32, f32, c_ptr, f32, f32, c_ptr, c_ptr]),
 }
 
-ABI_VERSION = 5      # the NERF_ABI_VERSION of include/nerf_hip.h this table was written against
+ABI_VERSION = 6      # the NERF_ABI_VERSION of include/nerf_hip.h this table was written against
 
 _lib = None
 

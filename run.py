@@ -79,6 +79,18 @@ def run_part2(cfg, args):
     dec = model.decoder
     use_engine = (not args.eval_only and cfg.get("engine", True) and getattr(dec, "fused", False)
                   and (dec.pos_dim, dec.dir_dim) == (63, 27))
+    # A non-default shape trains on the fused chain of project-nerf_amd/part2.py only when the YAML says `engine: true`
+    # explicitly (single rank, a shape the chain is compiled for); with the key absent it takes the module path.
+    p2_eng = None
+    if not use_engine and not args.eval_only and cfg.get("engine") is True:
+        from project_nerf_amd import part2
+        why = f"world size {world} (the engine is single-rank)" if world > 1 else part2.supported(cfg)
+        if why is None:
+            p2_eng = part2.Part2Engine(cfg, device=str(device), lr=lr, near=near, far=far, white_bkgd=white_bkgd)
+            p2_eng.load_from_model(model)
+            say(f">>> Part 2 on the fused HIP shape engine ({p2_eng.params.numel()} parameters)")
+        else:
+            say(f">>> Part 2 engine not used: {why}; training on the module path")
     if use_engine:
         from project_nerf_amd.engine import VanillaNerfEngine
         tb = TensorBoardLogger(os.path.join(log_dir, "tensorboard")) if main_rank else None
@@ -114,6 +126,34 @@ def run_part2(cfg, args):
         if main_rank:
             torch.save({"model_state_dict": model.state_dict(), "config": cfg}, os.path.join(ckpt_dir, "model_final.pth"))
             tb.close()
+    elif p2_eng is not None:
+        tb = TensorBoardLogger(os.path.join(log_dir, "tensorboard"))
+        eng = p2_eng
+
+        def sync_model():
+            eng.copy_to_model(model)
+
+        for step in range(1, train_iters + 1):
+            rays_o, rays_d, target, z = train_set.train_batch(local_batch, n_samples, near, far, eng.bg, seed=cfg.get("seed", 0),
+                                                              counter=step, first_ray=first_ray)
+            loss = eng.train_step(rays_o, rays_d, target, n_samples, z=z)
+            if step % log_every == 0:
+                loss_val = loss.item()
+                psnr = compute_psnr(loss_val)
+                say(f">>> Step {step}/{train_iters} | Loss {loss_val:.6f} | PSNR {psnr:.2f} dB")
+                if not bool((eng.grads != 0).any()):
+                    # the dead density head of the default engine's loop above
+                    say(">>> WARNING: all gradients are exactly zero -- every density of the batch is zero (dead ReLU density "
+                        "head); this run will not recover: restart with another `seed:` in the YAML")
+                tb.log_scalar("Train/Loss", loss_val, step)
+                tb.log_scalar("Train/PSNR", psnr, step)
+            if save_every and step % save_every == 0:
+                sync_model()
+                torch.save({"model_state_dict": model.state_dict(), "config": cfg},
+                           os.path.join(ckpt_dir, f"model_step_{step:06d}.pth"))
+        sync_model()
+        torch.save({"model_state_dict": model.state_dict(), "config": cfg}, os.path.join(ckpt_dir, "model_final.pth"))
+        tb.close()
     elif not args.eval_only:
         tb = TensorBoardLogger(os.path.join(log_dir, "tensorboard")) if main_rank else None
         optimizer = torch.optim.Adam(model.parameters(), lr=lr)
@@ -151,8 +191,11 @@ def run_part2(cfg, args):
         for idx in range(n_eval):
             rays_o, rays_d, target = test_set.get_image_rays(idx, device)
             # row bands over the ranks, gathered on rank 0 (one rank: the whole frame)
-            pred = parallel.render_row_bands(
-                lambda o, d: render_image_safe(render_image, model, o, d, near, far, render_n_samples, chunk, white_bkgd), rays_o, rays_d)
+            if p2_eng is not None:       # single rank: the whole frame through the engine's inference chain
+                pred = p2_eng.render_image(rays_o, rays_d, render_n_samples, chunk)
+            else:
+                pred = parallel.render_row_bands(
+                    lambda o, d: render_image_safe(render_image, model, o, d, near, far, render_n_samples, chunk, white_bkgd), rays_o, rays_d)
             if not main_rank:
                 continue
             pred = torch.clamp(pred, 0.0, 1.0)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Registers, LDS, scratch (spills) of every kernel in libnerf_hip.so, read from the code objects' metadata notes
-(no GPU needed):  python tools/kernel_resources.py [substring]"""
+(no GPU needed):  python tools/kernel_resources.py [substring | tag]
+Tags: p1 (csrc/p1fit.hip), p2 (csrc/p2chain.hip: the Part 2 chain for non-default decoder shapes), p3c (csrc/p3canon.hip)."""
 import os
 import re
 import struct
@@ -11,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "project-nerf_amd", "libnerf_hip.so")
 LLVM = "/opt/rocm/lib/llvm/bin"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+TAGS = {"p1": "nerf::p1::", "p2": "nerf::p2::", "p3c": "nerf::p3c::"}
 
 
 def code_objects(blob):
@@ -29,6 +31,7 @@ def code_objects(blob):
 
 def main():
     want = sys.argv[1] if len(sys.argv) > 1 else ""
+    want = TAGS.get(want, want)
     blob = open(LIB, "rb").read()
     for i, co in enumerate(code_objects(blob)):
         tmp = f"/tmp/nerf_co_{i}.o"
