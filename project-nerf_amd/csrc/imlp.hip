@@ -105,7 +105,7 @@ __device__ __forceinline__ void istep_run(const char* wbase, const bf16x8 (&b)[K
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    acc = mtile_mfma<KS>(wbase, st.frag0 + m * KS, b, acc);
+    acc = mtile<KS>(wbase, st.frag0 + m * KS, b, acc);
     epi(mc, acc);
   });
 }

@@ -11,6 +11,7 @@ namespace nerf {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -96,20 +97,41 @@ struct WeightRing {
 // sched_group_barrier sequence pins that software pipeline (hipcc otherwise serialises
 // ds_read -> wait -> mfma on one fragment register when VGPRs are tight).
 constexpr int kAhead = 3;
-template <int KS>
-__device__ __forceinline__ f32x16 mtile_mfma(const char* a_base, int frag_off, const bf16x8 (&b)[KS], f32x16 acc) {
-  // explicit rotating window of kAhead fragments, in program order: read k+kAhead, then MFMA k
-  constexpr int D = KS < kAhead ? KS : kAhead;
-  bf16x8 win[D];
+struct MfmaBf {
+  __device__ __forceinline__ f32x16 operator()(bf16x8 a, bf16x8 b, f32x16 c) const { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+struct Mfma16 {
+  __device__ __forceinline__ f32x16 operator()(f16x8 a, f16x8 b, f32x16 c) const { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
+// V: the operand vector (bf16x8 with MfmaBf, f16x8 with Mfma16); AHEAD: the read-ahead depth
+template <int KS, int AHEAD = kAhead, class V, class F = MfmaBf>
+__device__ __forceinline__ f32x16 mtile(const char* a_base, int frag_off, const V (&b)[KS], f32x16 acc, F mfma = F{}) {
+  // explicit rotating window of AHEAD fragments, in program order: read k+AHEAD, then MFMA k
+  constexpr int D = KS < AHEAD ? KS : AHEAD;
+  V win[D];
 #pragma unroll
-  for (int i = 0; i < D; ++i) win[i] = *reinterpret_cast<const bf16x8*>(a_base + (frag_off + i) * 1024);
+  for (int i = 0; i < D; ++i) win[i] = *reinterpret_cast<const V*>(a_base + (frag_off + i) * 1024);
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
-    const bf16x8 cur = win[ks % D];
-    if (ks + D < KS) win[ks % D] = *reinterpret_cast<const bf16x8*>(a_base + (frag_off + ks + D) * 1024);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cur, b[ks], acc, 0, 0, 0);
+    const V cur = win[ks % D];
+    if (ks + D < KS) win[ks % D] = *reinterpret_cast<const V*>(a_base + (frag_off + ks + D) * 1024);
+    acc = mfma(cur, b[ks], acc);
   }
   return acc;
+}
+
+// Packing a 1-KiB A fragment (32 rows x 16 k): lane (row & 31, h) holds 8 elements.  Column of element j of k-step ks_rel:
+// natural order (the operand is a code or a gradient read as stored) 16 ks + 8 h + j; accumulator order (the operand is the
+// previous step's accumulator tiles: register r of lane-half h is row 8 (r >> 2) + 4 h + (r & 3) of its 32)
+__host__ __device__ __forceinline__ int frag_column(int ks_rel, int h, int j, bool nat) {
+  return nat ? 16 * ks_rel + 8 * h + j : 32 * (ks_rel >> 1) + 16 * (ks_rel & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
+}
+// the lane's eight 16-bit elements (bf16 or fp16 bit patterns) -> bytes [16 lane, 16 lane + 16) of fragment `frag`
+__device__ __forceinline__ void store_fragment(char* packed, size_t frag, int lane, const unsigned short (&out)[8]) {
+  uint4 bits;
+  bits.x = out[0] | ((unsigned)out[1] << 16); bits.y = out[2] | ((unsigned)out[3] << 16);
+  bits.z = out[4] | ((unsigned)out[5] << 16); bits.w = out[6] | ((unsigned)out[7] << 16);
+  *reinterpret_cast<uint4*>(packed + frag * 1024 + lane * 16) = bits;
 }
 
 __device__ __forceinline__ unsigned lds_addr(const char* p) {

@@ -7,9 +7,10 @@
 //   y    = sigmoid(W_out h_last + b_out)                 H -> 3
 //   loss = mean((y - target)^2)                          over n * 3 values
 //
-// Compiled: H in {64, 128, 256}, 1..8 layers, L 0..15.  Same register chain as p3deform.hip / p4mlp.hip: 32 samples per wave on
-// the MFMA column (v_mfma_f32_32x32x16_bf16), accumulator tiles -> bf16 B fragments of the next layer, 8 waves (256 samples) per
-// workgroup pass.  All hidden layers have one shape, so the chain is a runtime loop over layers for a templated H.
+// Compiled: H in {64, 128, 256}, 1..8 layers, L 0..15.  The sample-major register chain of sample_chain.h (staging, tile loop, image
+// rows, the weight-gradient job and the host helpers live there): 32 samples per wave on the MFMA column
+// (v_mfma_f32_32x32x16_bf16), accumulator tiles -> bf16 B fragments of the next layer, 8 waves (256 samples) per workgroup pass.
+// All hidden layers have one shape, so the chain is a runtime loop over layers for a templated H.
 //
 // Where the weights live: ONE layer at a time is staged from the packed fragment image (L2) into LDS, for every H (H = 256: one
 // layer is 128 KiB of the 160; H = 64 / 128 could keep several resident, the one code path was preferred).  Biases initialise
@@ -35,16 +36,15 @@
 // Parameter vector (fp32, the module's state dict concatenated, [out, in] row-major): decoder.net.{0,2,...}.{weight,bias}
 //   W_1 [H, C] b_1 [H] | W_i [H, H] b_i [H] (i = 2..layers) | W_out [3, H] b_out [3]          C = 2 + 4 L
 #include <math.h>
-#include "mlp_chain.h"
+#include "sample_chain.h"
 
 namespace nerf {
 namespace p1 {
+using namespace sample_chain;
 
 constexpr int kThreads = 512, kWaves = kThreads / 64, kTile = kWaves * 32;
 constexpr int kCodeLd = 64, kCodeKs = kCodeLd / 16, kDpreLd = 8;
 constexpr int kMaxLayers = 8, kMaxL = 15;
-// weight gradients: chunk-partial tiles of every parameter, then one ordered sum
-constexpr int kMaxChunks = 64, kMinChunk = 1024, kSub = 32, kOBlock = 64;
 constexpr int kLossParts = 4096;
 
 // fragment plan (1-KiB fragments) and parameter offsets of one shape
@@ -84,7 +84,7 @@ __global__ void __launch_bounds__(256) pack_kernel(const float* __restrict__ par
     unsigned short out[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const int k = nat ? 16 * ks + 8 * h + j : 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
+      const int k = frag_column(ks, h, j, nat);
       int src = -1;
       switch (step) {
         case F1: {       // operand columns [x_hi y_hi | x_lo y_lo | code columns 2..C-1]
@@ -99,10 +99,7 @@ __global__ void __launch_bounds__(256) pack_kernel(const float* __restrict__ par
       }
       out[j] = __builtin_bit_cast(unsigned short, (__bf16)(src >= 0 ? params[src] : 0.0f));
     }
-    uint4 bits;
-    bits.x = out[0] | ((unsigned)out[1] << 16); bits.y = out[2] | ((unsigned)out[3] << 16);
-    bits.z = out[4] | ((unsigned)out[5] << 16); bits.w = out[6] | ((unsigned)out[7] << 16);
-    *reinterpret_cast<uint4*>(packed + (size_t)frag * 1024 + lane * 16) = bits;
+    store_fragment(packed, frag, lane, out);
   }
   if (blockIdx.x == 0) {
     float* bias = reinterpret_cast<float*>(packed + p.bias_bytes_off());        // b_1 .. b_layers [H] each | b_out padded to 32
@@ -125,77 +122,13 @@ struct Args {
   __bf16* code; __bf16* h; __bf16* dz; __bf16* dpre;     // training images; h / dz: [layers][n_pad][H]
 };
 
-// one layer's fragments: packed image -> LDS by direct-to-LDS loads (no data registers): one wave instruction moves one 1-KiB
-// fragment, lane l its bytes [16 l, 16 l + 16).  The first barrier: every wave is done with the previous layer.  Then every wave
-// waits for its OWN loads (vmcnt 0; the other counters at their maxima) before the second barrier, which makes all of them visible.
-constexpr int kWaitVm0 = (15 << 8) | (7 << 4);       // s_waitcnt immediate: vmcnt(0), expcnt and lgkmcnt not waited for
-template <int WAVES>
-__device__ __forceinline__ void stage(char* smem, const char* src, int frags) {
-  __syncthreads();
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int i = wave; i < frags; i += WAVES)
-    __builtin_amdgcn_global_load_lds((gptr_t)(src + (size_t)i * 1024 + lane * 16), (lptr_t)(smem + i * 1024), 16, 0, 0);
-  __builtin_amdgcn_s_waitcnt(kWaitVm0);
-  __syncthreads();
-}
-
-// mtile_mfma of mlp_chain.h with the read-ahead depth as a parameter: H = 256 holds two 64-register operand arrays and reads
-// 2 fragments ahead (3 spilled three registers)
-template <int KS, int AHEAD>
-__device__ __forceinline__ f32x16 mtile(const char* a_base, int frag_off, const bf16x8 (&b)[KS], f32x16 acc) {
-  constexpr int D = KS < AHEAD ? KS : AHEAD;
-  bf16x8 win[D];
-#pragma unroll
-  for (int i = 0; i < D; ++i) win[i] = *reinterpret_cast<const bf16x8*>(a_base + (frag_off + i) * 1024);
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    const bf16x8 cur = win[ks % D];
-    if (ks + D < KS) win[ks % D] = *reinterpret_cast<const bf16x8*>(a_base + (frag_off + ks + D) * 1024);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cur, b[ks], acc, 0, 0, 0);
-  }
-  return acc;
-}
-
-// every m-tile of one step: acc = bias (or 0) + A B, then epi(m, acc)
-template <int MT, int KS, class Epi>
-__device__ __forceinline__ void run(const char* wbase, const bf16x8 (&b)[KS], const float* bias, int half, Epi&& epi) {
-  static_for<MT>([&](auto mc) {
-    constexpr int m = decltype(mc)::value;
-    f32x16 acc;
-    if (bias != nullptr) acc = bias_tile(bias, 32 * m, half);
-    else {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    }
-    acc = mtile<KS, (MT == 8 ? 2 : kAhead)>(wbase, m * KS, b, acc);
-    epi(mc, acc);
-    __builtin_amdgcn_sched_barrier(0);       // one m-tile at a time: interleaved tiles cost registers (H = 256 spilled)
-  });
-}
-
-// the two operand fragments of an accumulator tile hold features 32 m + 8 g + 4 half + (0..3), g = 0..3: four runs of 4
-__device__ __forceinline__ void store_rows(__bf16* img, int H, int64_t n, int m, int half, const bf16x8& lo, const bf16x8& hi) {
-  __bf16* row = img + n * H + 32 * m + 4 * half;
-  *reinterpret_cast<bf16x4*>(row + 0) = bf16x4{lo[0], lo[1], lo[2], lo[3]};
-  *reinterpret_cast<bf16x4*>(row + 8) = bf16x4{lo[4], lo[5], lo[6], lo[7]};
-  *reinterpret_cast<bf16x4*>(row + 16) = bf16x4{hi[0], hi[1], hi[2], hi[3]};
-  *reinterpret_cast<bf16x4*>(row + 24) = bf16x4{hi[4], hi[5], hi[6], hi[7]};
-}
-__device__ __forceinline__ void load_rows(const __bf16* img, int H, int64_t n, int m, int half, float (&out)[16]) {
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const bf16x4 v = *reinterpret_cast<const bf16x4*>(img + n * H + 32 * m + 8 * g + 4 * half);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) out[4 * g + r] = (float)v[r];
-  }
-}
-
+// H = 256 holds two 64-register operand arrays and reads 2 fragments ahead (a depth of 3 spilled three registers)
+constexpr int ahead(int H) { return H == 256 ? 2 : kAhead; }
 // inference at H = 256 runs 4 waves per workgroup: two 64-register operand arrays + the row index did not fit 256 registers
+constexpr int fwd_waves(int H, bool train) { return (!train && H == 256) ? 4 : kWaves; }
 template <int H, bool TRAIN>
-constexpr int fwd_waves() { return (!TRAIN && H == 256) ? 4 : kWaves; }
-template <int H, bool TRAIN>
-__global__ void __launch_bounds__((64 * fwd_waves<H, TRAIN>())) fwd_kernel(const Args a) {
-  constexpr int MT = H / 32, KS = H / 16, WAVES = fwd_waves<H, TRAIN>();
+__global__ void __launch_bounds__((64 * fwd_waves(H, TRAIN))) fwd_kernel(const Args a) {
+  constexpr int MT = H / 32, KS = H / 16, WAVES = fwd_waves(H, TRAIN), AH = ahead(H);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
   const char* wbase = smem + lane * 16;
@@ -247,12 +180,12 @@ __global__ void __launch_bounds__((64 * fwd_waves<H, TRAIN>())) fwd_kernel(const
     };
     bf16x8 hc[KS];
     stage<WAVES>(smem, a.packed + (size_t)a.p.f1 * 1024, MT * kCodeKs);
-    run<MT, kCodeKs>(wbase, code, bias, half, relu_epi(hc, a.h));
+    run<0, MT, kCodeKs, AH>(wbase, code, bias, half, relu_epi(hc, a.h));
 #pragma unroll 1
     for (int l = 1; l < layers; ++l) {
       stage<WAVES>(smem, a.packed + ((size_t)a.p.hid0 + (size_t)(l - 1) * MT * KS) * 1024, MT * KS);
       bf16x8 hn[KS];
-      run<MT, KS>(wbase, hc, bias + l * H, half, relu_epi(hn, a.h + l * img));
+      run<0, MT, KS, AH>(wbase, hc, bias + l * H, half, relu_epi(hn, a.h + l * img));
 #pragma unroll
       for (int k = 0; k < KS; ++k) hc[k] = hn[k];
     }
@@ -278,7 +211,7 @@ __global__ void __launch_bounds__((64 * fwd_waves<H, TRAIN>())) fwd_kernel(const
       }
       if constexpr (TRAIN) *reinterpret_cast<bf16x8*>(a.dpre + n * kDpreLd) = d;
     };
-    run<1, KS>(wbase, hc, nullptr, half, out_epi);
+    run<0, 1, KS, kAhead>(wbase, hc, nullptr, half, out_epi);
   }
   if constexpr (TRAIN) {
     // this workgroup's squared-error sum: lanes by butterfly, waves in wave order
@@ -297,7 +230,7 @@ __global__ void __launch_bounds__((64 * fwd_waves<H, TRAIN>())) fwd_kernel(const
 
 template <int H>
 __global__ void __launch_bounds__(kThreads) dgrad_kernel(const Args a) {
-  constexpr int MT = H / 32, KS = H / 16;
+  constexpr int MT = H / 32, KS = H / 16, AH = ahead(H);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
   const char* wbase = smem + lane * 16;
@@ -324,124 +257,48 @@ __global__ void __launch_bounds__(kThreads) dgrad_kernel(const Args a) {
     };
     bf16x8 g[KS];
     stage<kWaves>(smem, a.packed + (size_t)a.p.bout_t * 1024, MT);
-    run<MT, 1>(wbase, small, nullptr, half, mask_epi(g, a.h + (layers - 1) * img, a.dz + (layers - 1) * img));
+    run<0, MT, 1, AH>(wbase, small, nullptr, half, mask_epi(g, a.h + (layers - 1) * img, a.dz + (layers - 1) * img));
 #pragma unroll 1
     for (int l = layers - 1; l >= 1; --l) {
       stage<kWaves>(smem, a.packed + ((size_t)a.p.hid_t0 + (size_t)(l - 1) * MT * KS) * 1024, MT * KS);
       bf16x8 gn[KS];
-      run<MT, KS>(wbase, g, nullptr, half, mask_epi(gn, a.h + (l - 1) * img, a.dz + (l - 1) * img));
+      run<0, MT, KS, AH>(wbase, g, nullptr, half, mask_epi(gn, a.h + (l - 1) * img, a.dz + (l - 1) * img));
 #pragma unroll
       for (int k = 0; k < KS; ++k) g[k] = gn[k];
     }
   }
 }
 
-// Weight gradients of one layer's block of 64 output features over one chunk of samples: dW[o][i] = sum_n A[n][o] B[n][i],
-// db[o] = sum_n A[n][o], with the SAMPLES on the MFMA k axis.  32 samples at a time are staged row-major in LDS (padded rows:
-// the two lane halves read rows 8 apart from disjoint banks) and read back transposed, element by element, into fragments.
-// Wave w owns input tiles w and w + 4 of both output tiles.  The chunk's tiles are STORED into its slab row.
-// blockIdx.x: chunk, blockIdx.y: job = layer * (H / 64) + block, last job: the output layer.
+// Weight gradients (sample_chain.h::wgrad_job).  blockIdx.x: chunk, blockIdx.y: job = layer * (H / 64) + block, last job: the
+// output layer.  Layer 1 contracts against the operand columns [H][64], kept after the parameter vector in the slab row.
 struct WgradArgs {
   Plan p;
   const __bf16* code; const __bf16* h; const __bf16* dz; const __bf16* dpre;
   int64_t n, n_pad, chunk;
   float* slab;               // [chunks][slab_stride]
 };
-constexpr int kALd = kOBlock + 4, kBLd = 256 + 4;
-__global__ void __launch_bounds__(256) wgrad_kernel(const WgradArgs a) {
-  __shared__ __attribute__((aligned(16))) __bf16 As[kSub * kALd];
-  __shared__ __attribute__((aligned(16))) __bf16 Bs[kSub * kBLd];
+__device__ __forceinline__ Job job_of(const WgradArgs& a, int job) {
   const Plan& p = a.p;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
-  const int H = p.H, blocks = H / kOBlock, job = blockIdx.y;
+  const int H = p.H, blocks = H / kOBlock;
   const size_t img = (size_t)a.n_pad * H;
-  const __bf16 *A, *B;
-  int a_ld, O, o0, b_ld, I, w_off, w_ld, b_off;
+  Job j{};
   if (job == p.layers * blocks) {
-    A = a.dpre; a_ld = kDpreLd; O = 3; o0 = 0; B = a.h + (p.layers - 1) * img; b_ld = H; I = H;
-    w_off = p.w_off(p.layers); w_ld = H; b_off = p.b_off(p.layers);
+    j.A = a.dpre; j.a_ld = kDpreLd; j.O = 3; j.o0 = 0;
+    j.B = a.h + (p.layers - 1) * img; j.b_ld = H; j.I = H;
+    j.w_off = p.w_off(p.layers); j.w_ld = H; j.b_off = p.b_off(p.layers);
   } else {
     const int l = job / blocks;
-    A = a.dz + l * img; a_ld = H; O = H; o0 = (job % blocks) * kOBlock;
-    B = l == 0 ? a.code : a.h + (l - 1) * img; b_ld = l == 0 ? kCodeLd : H; I = b_ld;
-    w_off = l == 0 ? p.n_params : p.w_off(l); w_ld = I; b_off = p.b_off(l);
+    j.A = a.dz + l * img; j.a_ld = H; j.O = H; j.o0 = (job % blocks) * kOBlock;
+    j.B = l == 0 ? a.code : a.h + (l - 1) * img; j.b_ld = l == 0 ? kCodeLd : H; j.I = j.b_ld;
+    j.w_off = l == 0 ? p.n_params : p.w_off(l); j.w_ld = j.I; j.b_off = p.b_off(l);
   }
+  return j;
+}
+__global__ void __launch_bounds__(256) wgrad_kernel(const WgradArgs a) {
+  const Job jb = job_of(a, blockIdx.y);
   const int64_t n0 = blockIdx.x * a.chunk;
   const int64_t n1 = n0 + a.chunk < a.n ? n0 + a.chunk : a.n;
-  float* out = a.slab + (size_t)blockIdx.x * p.slab_stride;
-  const int n_ot = o0 + 32 < O ? 2 : 1;
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[q >> 1][q & 1][r] = 0.0f;
-  float bsum = 0.0f;
-  for (int64_t s0 = n0; s0 < n1; s0 += kSub) {
-    __syncthreads();
-    {
-      const int s = tid >> 3, c = 8 * (tid & 7);
-      uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (s0 + s < n1 && o0 + c < a_ld) v = *reinterpret_cast<const uint4*>(A + (s0 + s) * a_ld + o0 + c);
-      uint2* dst = reinterpret_cast<uint2*>(As + s * kALd + c);
-      dst[0] = make_uint2(v.x, v.y); dst[1] = make_uint2(v.z, v.w);
-    }
-    const int groups = I >> 3;
-    for (int e = tid; e < kSub * groups; e += 256) {
-      const int s = e / groups, c = 8 * (e % groups);
-      uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (s0 + s < n1) v = *reinterpret_cast<const uint4*>(B + (s0 + s) * b_ld + c);
-      uint2* dst = reinterpret_cast<uint2*>(Bs + s * kBLd + c);
-      dst[0] = make_uint2(v.x, v.y); dst[1] = make_uint2(v.z, v.w);
-    }
-    __syncthreads();
-    if (tid < kOBlock) {
-      for (int s = 0; s < kSub; ++s) bsum += (float)As[s * kALd + tid];
-    }
-#pragma unroll
-    for (int kk = 0; kk < kSub / 16; ++kk) {
-      const int srow = 16 * kk + 8 * half;
-      bf16x8 fa[2], fb[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) fa[t][j] = As[(srow + j) * kALd + 32 * t + col];
-      }
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const int it = wave + 4 * t;
-        if (32 * it < I) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) fb[t][j] = Bs[(srow + j) * kBLd + 32 * it + col];
-        } else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) fb[t][j] = (__bf16)0.0f;
-        }
-      }
-#pragma unroll
-      for (int ot = 0; ot < 2; ++ot) {
-        if (ot < n_ot) {
-#pragma unroll
-          for (int t = 0; t < 2; ++t)
-            if (32 * (wave + 4 * t) < I) acc[ot][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ot], fb[t], acc[ot][t], 0, 0, 0);
-        }
-      }
-    }
-  }
-  // accumulator register r of lane (col, half): output feature 8 (r >> 2) + 4 half + (r & 3), input column col
-#pragma unroll
-  for (int ot = 0; ot < 2; ++ot) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int i = 32 * (wave + 4 * t) + col;
-      if (ot >= n_ot || i >= I) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int o = o0 + 32 * ot + 8 * (r >> 2) + 4 * half + (r & 3);
-        if (o < O) out[w_off + o * w_ld + i] = acc[ot][t][r];
-      }
-    }
-  }
-  if (tid < kOBlock && o0 + tid < O) out[b_off + o0 + tid] = bsum;
+  wgrad_job(jb, n0, n1, a.slab + (size_t)blockIdx.x * a.p.slab_stride);
 }
 
 // grads[q] = sum over chunks, in chunk order (W_1: operand columns folded back: hi + lo of the raw pair share a weight);
@@ -456,12 +313,7 @@ __global__ void __launch_bounds__(256) reduce_kernel(const float* __restrict__ s
       s0 = p.n_params + o * kCodeLd + (c < 2 ? c : c + 2);
       if (c < 2) s1 = s0 + 2;
     }
-    float s = 0.0f;
-    for (int c = 0; c < chunks; ++c) {
-      const float* row = slab + (size_t)c * p.slab_stride;
-      s += s1 >= 0 ? row[s0] + row[s1] : row[s0];
-    }
-    grads[q] = s;
+    grads[q] = ordered_sum(slab, chunks, p.slab_stride, s0, s1);
   }
   if (blockIdx.x == 0 && threadIdx.x < 64) {
     float s = 0.0f;
@@ -469,16 +321,6 @@ __global__ void __launch_bounds__(256) reduce_kernel(const float* __restrict__ s
     s = wave_sum(s);
     if (threadIdx.x == 0) *loss = s * inv_count;
   }
-}
-
-static void chunking(int64_t n, int64_t* chunk, int64_t* chunks) {
-  // chunks of at least kMinChunk samples (multiples of kSub), at most kMaxChunks of them
-  int64_t c = (n + kMinChunk - 1) / kMinChunk;
-  if (c > kMaxChunks) c = kMaxChunks;
-  int64_t len = (n + c - 1) / c;
-  len = (len + kSub - 1) / kSub * kSub;
-  *chunk = len;
-  *chunks = (n + len - 1) / len;
 }
 
 struct Layout {
@@ -490,43 +332,30 @@ static Layout layout(const Plan& p, int64_t n) {
   s.n_pad = (n + kTile - 1) / kTile * kTile;
   const size_t np = (size_t)s.n_pad;
   size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
   int64_t chunk, chunks;
   chunking(n, &chunk, &chunks);
-  s.code = take(np * kCodeLd * 2);
-  s.h = take(np * p.H * 2 * p.layers);
-  s.dz = take(np * p.H * 2 * p.layers);
-  s.dpre = take(np * kDpreLd * 2);
-  s.loss_part = take(kLossParts * 4);
-  s.slab = take((size_t)chunks * p.slab_stride * 4);
+  s.code = take(&o, np * kCodeLd * 2);
+  s.h = take(&o, np * p.H * 2 * p.layers);
+  s.dz = take(&o, np * p.H * 2 * p.layers);
+  s.dpre = take(&o, np * kDpreLd * 2);
+  s.loss_part = take(&o, kLossParts * 4);
+  s.slab = take(&o, (size_t)chunks * p.slab_stride * 4);
   s.total = o;
   return s;
 }
-static int grid_for(const Plan& p, int64_t tiles) {
-  int n_cu = 0;
-  if (device_cu_count(&n_cu) != NERF_OK) return -1;
-  int64_t cap = (int64_t)n_cu * (p.H == 256 ? 1 : 2);       // H = 256: one layer fills the LDS of a CU
-  if (cap > kLossParts) cap = kLossParts;
-  return (int)(tiles < cap ? tiles : cap);
-}
+// H = 256: one layer fills the LDS of a CU
+static int grid_for(const Plan& p, int64_t tiles) { return sample_chain::grid_for(tiles, p.H == 256 ? 1 : 2, kLossParts); }
 static int lds_bytes(const Plan& p) { return p.mt * (p.ks > kCodeKs ? p.ks : kCodeKs) * 1024; }
 
-template <int H>
-static int launch_fwd(const Args& a, bool train, int grid, nerf_stream_t stream, const char* what) {
-  const int lds = lds_bytes(a.p);
-  const void* kernel = train ? (const void*)fwd_kernel<H, true> : (const void*)fwd_kernel<H, false>;
-  if (int rc = ensure_dynamic_lds(kernel, lds, what); rc != NERF_OK) return rc;
-  if (train) hipLaunchKernelGGL((fwd_kernel<H, true>), dim3(grid), dim3(64 * fwd_waves<H, true>()), lds, as_stream(stream), a);
-  else hipLaunchKernelGGL((fwd_kernel<H, false>), dim3(grid), dim3(64 * fwd_waves<H, false>()), lds, as_stream(stream), a);
-  return check_launch(what);
+typedef void (*ChainKernel)(Args);
+static ChainKernel fwd_kernel_of(int H, bool train) {
+  switch (H) {
+    case 64: return train ? fwd_kernel<64, true> : fwd_kernel<64, false>;
+    case 128: return train ? fwd_kernel<128, true> : fwd_kernel<128, false>;
+    default: return train ? fwd_kernel<256, true> : fwd_kernel<256, false>;
+  }
 }
-template <int H>
-static int launch_dgrad(const Args& a, int grid, nerf_stream_t stream, const char* what) {
-  const int lds = lds_bytes(a.p);
-  if (int rc = ensure_dynamic_lds((const void*)dgrad_kernel<H>, lds, what); rc != NERF_OK) return rc;
-  hipLaunchKernelGGL((dgrad_kernel<H>), dim3(grid), dim3(kThreads), lds, as_stream(stream), a);
-  return check_launch(what);
-}
+static ChainKernel dgrad_kernel_of(int H) { return H == 64 ? dgrad_kernel<64> : (H == 128 ? dgrad_kernel<128> : dgrad_kernel<256>); }
 
 }  // namespace p1
 }  // namespace nerf
@@ -574,13 +403,10 @@ extern "C" int nerf_p1_fwd(const void* packed, const float* coords, int64_t n, i
   p1::Args a{};
   a.packed = static_cast<const char*>(packed); a.p = plan; a.coords = coords; a.y = y;
   a.n = n; a.n_pad = (n + p1::kTile - 1) / p1::kTile * p1::kTile;
-  const int grid = p1::grid_for(plan, a.n_pad / (hidden == 256 ? 32 * p1::fwd_waves<256, false>() : p1::kTile));
+  const int waves = p1::fwd_waves(hidden, false);
+  const int grid = p1::grid_for(plan, a.n_pad / (32 * waves));
   if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_p1_fwd: cannot query device");
-  switch (hidden) {
-    case 64: return p1::launch_fwd<64>(a, false, grid, stream, "nerf_p1_fwd");
-    case 128: return p1::launch_fwd<128>(a, false, grid, stream, "nerf_p1_fwd");
-    default: return p1::launch_fwd<256>(a, false, grid, stream, "nerf_p1_fwd");
-  }
+  return p1::launch_chain(p1::fwd_kernel_of(hidden, false), grid, 64 * waves, p1::lds_bytes(plan), stream, "nerf_p1_fwd", a);
 }
 
 extern "C" int nerf_p1_fwd_loss_bwd(const void* packed, void* workspace, const float* coords, const int64_t* idx, const float* target,
@@ -600,18 +426,10 @@ extern "C" int nerf_p1_fwd_loss_bwd(const void* packed, void* workspace, const f
   a.dz = reinterpret_cast<__bf16*>(w + l.dz); a.dpre = reinterpret_cast<__bf16*>(w + l.dpre);
   const int grid = p1::grid_for(plan, a.n_pad / p1::kTile);
   if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_p1_fwd_loss_bwd: cannot query device");
-  int rc;
-  switch (hidden) {
-    case 64: rc = p1::launch_fwd<64>(a, true, grid, stream, "nerf_p1_fwd_loss_bwd (forward)"); break;
-    case 128: rc = p1::launch_fwd<128>(a, true, grid, stream, "nerf_p1_fwd_loss_bwd (forward)"); break;
-    default: rc = p1::launch_fwd<256>(a, true, grid, stream, "nerf_p1_fwd_loss_bwd (forward)"); break;
-  }
+  const int lds = p1::lds_bytes(plan);
+  int rc = p1::launch_chain(p1::fwd_kernel_of(hidden, true), grid, p1::kThreads, lds, stream, "nerf_p1_fwd_loss_bwd (forward)", a);
   if (rc != NERF_OK) return rc;
-  switch (hidden) {
-    case 64: rc = p1::launch_dgrad<64>(a, grid, stream, "nerf_p1_fwd_loss_bwd (dgrad)"); break;
-    case 128: rc = p1::launch_dgrad<128>(a, grid, stream, "nerf_p1_fwd_loss_bwd (dgrad)"); break;
-    default: rc = p1::launch_dgrad<256>(a, grid, stream, "nerf_p1_fwd_loss_bwd (dgrad)"); break;
-  }
+  rc = p1::launch_chain(p1::dgrad_kernel_of(hidden), grid, p1::kThreads, lds, stream, "nerf_p1_fwd_loss_bwd (dgrad)", a);
   if (rc != NERF_OK) return rc;
   int64_t chunk, chunks;
   p1::chunking(n, &chunk, &chunks);

@@ -9,12 +9,13 @@
 //   h_v  = relu(W_v [f | code(v)] + b_v)                    H + D -> V        D = 3 + 6 L_embed_dir
 //   rgb  = sigmoid(W_c h_v + b_c)                           V -> 3
 //
-// Compiled: H in {64, 128, 256}, 2..8 layers (a runtime loop for a templated H, as p1fit.hip), skip_layer 1..layers-1 or none,
+// Compiled: H in {64, 128, 256}, 2..8 layers (a runtime loop for a templated H), skip_layer 1..layers-1 or none,
 // V in {64, 128}, L_embed 1..10 (one 64-column operand), L_embed_dir 0..4 (one 32-column operand).  The view layer always runs at
 // 128 rows: V = 64 pads W_v / b_v / W_c with zeros (relu(0) = 0, masks false: the pad rows carry nothing in either direction).
 //
-// The register chain of p1fit.hip: 32 samples per wave on the MFMA column (v_mfma_f32_32x32x16_bf16), accumulator tiles -> bf16
-// B fragments of the next layer, ONE layer's weights at a time staged from the packed fragment image into LDS (the skip layer in
+// The sample-major register chain of sample_chain.h (staging, tile loop, image rows, the weight-gradient job and the host helpers
+// live there): 32 samples per wave on the MFMA column (v_mfma_f32_32x32x16_bf16), accumulator tiles -> bf16 B fragments of the
+// next layer, ONE layer's weights at a time staged from the packed fragment image into LDS (the skip layer in
 // two halves of its output tiles: 8 x (16 + 4) fragments would fill all 160 KiB).  bf16 operands, fp32 accumulation, fp32 biases
 // as the accumulators' initial values: the rounding points of the vanilla chain (mlp_fwd.hip) and of p3canon.hip.  The codes are
 // formed in registers with the arithmetic of fourier.hip ((x * 2^band) * pi, both products rounded, full-range sine / cosine) and
@@ -24,24 +25,23 @@
 // [n_pad][128]; the relu masks are h > 0 of the stored values.  The dgrad kernel runs the transposed chain from d rgb, d sigma
 // (through sigmoid', the bare relu of sigma, the view layer, the linear feature layer, the trunk with the skip layer's hidden
 // columns only: positions and directions are not learned) and writes the pre-activation gradient images.  Weight and bias
-// gradients: chunk-partial tiles over the sample axis on bf16 MFMA (p1fit.hip's kernel with a job table for this decoder), then one
-// reduction in chunk order.  No float atomics anywhere: the same bits on every run.
+// gradients: chunk-partial tiles over the sample axis on bf16 MFMA (sample_chain.h::wgrad_job with this decoder's job table), then
+// one reduction in chunk order.  No float atomics anywhere: the same bits on every run.
 //
 // tools/kernel_resources.py p2:: lists the registers (scratch 0 and no spills in every kernel).
 //
 // Parameter vector (fp32, the module's state dict concatenated, [out, in] row-major):
 //   pts_layers.l.{weight,bias} l = 0..layers-1 | sigma_layer | feature_layer | view_layer | rgb_layer
 #include <math.h>
-#include "mlp_chain.h"
+#include "sample_chain.h"
 
 namespace nerf {
 namespace p2 {
+using namespace sample_chain;
 
 constexpr int kCodeLd = 64, kCodeKs = kCodeLd / 16, kDirLd = 32, kDirKs = kDirLd / 16, kSmallLd = 8;
 constexpr int kVPad = 128, kVT = kVPad / 32, kVKs = kVPad / 16;
 constexpr int kMaxLayers = 8, kMaxL = 10, kMaxLd = 4;
-// weight gradients: chunk-partial tiles of every parameter, then one ordered sum
-constexpr int kMaxChunks = 64, kMinChunk = 1024, kSub = 32, kOBlock = 64;
 constexpr int kPadRows = 256;      // images are padded to a multiple of every kernel's workgroup tile
 
 enum Kind { F0, HID, HEAD, VIEW, RGB, RGB_T, VIEW_T, HEAD_T, HID_T };
@@ -159,14 +159,11 @@ __global__ void __launch_bounds__(256) pack_kernel(const float* __restrict__ par
     unsigned short out[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const int k = nat ? 16 * (ks - k_acc) + 8 * h + j : 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
+      const int k = frag_column(nat ? ks - k_acc : ks, h, j, nat);
       const int src = src_index(p, kind, l, row, k, nat);
       out[j] = __builtin_bit_cast(unsigned short, (__bf16)(src >= 0 ? params[src] : 0.0f));
     }
-    uint4 bits;
-    bits.x = out[0] | ((unsigned)out[1] << 16); bits.y = out[2] | ((unsigned)out[3] << 16);
-    bits.z = out[4] | ((unsigned)out[5] << 16); bits.w = out[6] | ((unsigned)out[7] << 16);
-    *reinterpret_cast<uint4*>(packed + (size_t)frag * 1024 + lane * 16) = bits;
+    store_fragment(packed, frag, lane, out);
   }
   float* bias = reinterpret_cast<float*>(packed + p.bias_bytes_off());
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < p.bias_floats(); i += gridDim.x * blockDim.x) {
@@ -194,66 +191,6 @@ struct Args {
   __bf16* code; __bf16* dcode; __bf16* h; __bf16* feat; __bf16* hv;          // forward images; h: [layers][n_pad][H]
   __bf16* drgb; __bf16* dsig; __bf16* dzv; __bf16* dfeat; __bf16* dz;        // gradient images; dz: [layers][n_pad][H]
 };
-
-// one step's fragments: packed image -> LDS by direct-to-LDS loads (p1fit.hip::stage)
-constexpr int kWaitVm0 = (15 << 8) | (7 << 4);       // s_waitcnt immediate: vmcnt(0), expcnt and lgkmcnt not waited for
-template <int WAVES>
-__device__ __forceinline__ void stage(char* smem, const char* src, int frags) {
-  __syncthreads();
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int i = wave; i < frags; i += WAVES)
-    __builtin_amdgcn_global_load_lds((gptr_t)(src + (size_t)i * 1024 + lane * 16), (lptr_t)(smem + i * 1024), 16, 0, 0);
-  __builtin_amdgcn_s_waitcnt(kWaitVm0);
-  __syncthreads();
-}
-
-template <int KS, int AHEAD>
-__device__ __forceinline__ f32x16 mtile(const char* a_base, int frag_off, const bf16x8 (&b)[KS], f32x16 acc) {
-  constexpr int D = KS < AHEAD ? KS : AHEAD;
-  bf16x8 win[D];
-#pragma unroll
-  for (int i = 0; i < D; ++i) win[i] = *reinterpret_cast<const bf16x8*>(a_base + (frag_off + i) * 1024);
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    const bf16x8 cur = win[ks % D];
-    if (ks + D < KS) win[ks % D] = *reinterpret_cast<const bf16x8*>(a_base + (frag_off + ks + D) * 1024);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cur, b[ks], acc, 0, 0, 0);
-  }
-  return acc;
-}
-
-// output tiles M0..M1-1 of one step (tile M0's fragments first at wbase): acc = bias (or 0) + A B, then epi(m, acc)
-template <int M0, int M1, int KS, int AHEAD, class Epi>
-__device__ __forceinline__ void run(const char* wbase, const bf16x8 (&b)[KS], const float* bias, int half, Epi&& epi) {
-  static_for<M1 - M0>([&](auto ic) {
-    constexpr int i = decltype(ic)::value, m = M0 + i;
-    f32x16 acc;
-    if (bias != nullptr) acc = bias_tile(bias, 32 * m, half);
-    else {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    }
-    acc = mtile<KS, AHEAD>(wbase, i * KS, b, acc);
-    epi(std::integral_constant<int, m>{}, acc);
-    __builtin_amdgcn_sched_barrier(0);       // one tile at a time: interleaved tiles cost registers
-  });
-}
-
-__device__ __forceinline__ void store_rows(__bf16* img, int ld, int64_t n, int m, int half, const bf16x8& lo, const bf16x8& hi) {
-  __bf16* row = img + n * ld + 32 * m + 4 * half;
-  *reinterpret_cast<bf16x4*>(row + 0) = bf16x4{lo[0], lo[1], lo[2], lo[3]};
-  *reinterpret_cast<bf16x4*>(row + 8) = bf16x4{lo[4], lo[5], lo[6], lo[7]};
-  *reinterpret_cast<bf16x4*>(row + 16) = bf16x4{hi[0], hi[1], hi[2], hi[3]};
-  *reinterpret_cast<bf16x4*>(row + 24) = bf16x4{hi[4], hi[5], hi[6], hi[7]};
-}
-__device__ __forceinline__ void load_rows(const __bf16* img, int ld, int64_t n, int m, int half, float (&out)[16]) {
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const bf16x4 v = *reinterpret_cast<const bf16x4*>(img + n * ld + 32 * m + 8 * g + 4 * half);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) out[4 * g + r] = (float)v[r];
-  }
-}
 
 // KSN k-steps of the code of one triple, natural order: column f = 16 ks + 8 half + j of
 // [x(3) | sin(2^0 pi x)(3) | cos(2^0 pi x)(3) | sin(2^1 pi x)(3) | ...] (src/embeddings.py:28-32), zero from column 3 + 6 L on.
@@ -310,14 +247,12 @@ __device__ __forceinline__ void sample_inputs(const Args& a, int64_t nc, float (
 
 // H = 256 runs 4 waves per workgroup in the chain kernels: two 64-register operand arrays, the skip layer's code (forward) or the
 // extra sigma k-step (dgrad) and the sample do not fit 256 registers
-template <int H>
-constexpr int fwd_waves() { return H == 256 ? 4 : 8; }
-template <int H>
-constexpr int ahead() { return H == 256 ? 2 : kAhead; }
+constexpr int fwd_waves(int H) { return H == 256 ? 4 : 8; }
+constexpr int ahead(int H) { return H == 256 ? 2 : kAhead; }
 
 template <int H, bool TRAIN>
-__global__ void __launch_bounds__((64 * fwd_waves<H>())) fwd_kernel(const Args a) {
-  constexpr int MT = H / 32, KS = H / 16, WAVES = fwd_waves<H>(), AH = ahead<H>();
+__global__ void __launch_bounds__((64 * fwd_waves(H))) fwd_kernel(const Args a) {
+  constexpr int MT = H / 32, KS = H / 16, WAVES = fwd_waves(H), AH = ahead(H);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
   const char* wbase = smem + lane * 16;
@@ -407,8 +342,8 @@ __global__ void __launch_bounds__((64 * fwd_waves<H>())) fwd_kernel(const Args a
 }
 
 template <int H>
-__global__ void __launch_bounds__((64 * fwd_waves<H>())) dgrad_kernel(const Args a) {
-  constexpr int MT = H / 32, KS = H / 16, AH = ahead<H>(), kBwdWaves = fwd_waves<H>();
+__global__ void __launch_bounds__((64 * fwd_waves(H))) dgrad_kernel(const Args a) {
+  constexpr int MT = H / 32, KS = H / 16, AH = ahead(H), kBwdWaves = fwd_waves(H);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
   const char* wbase = smem + lane * 16;
@@ -468,15 +403,8 @@ __global__ void __launch_bounds__((64 * fwd_waves<H>())) dgrad_kernel(const Args
   }
 }
 
-// Weight gradients of one job's block of 64 output features over one chunk of samples (p1fit.hip::wgrad_kernel):
-// dW[o][i] = sum_n A[n][o] B[n][i], db[o] = sum_n A[n][o], the SAMPLES on the MFMA k axis; the chunk's tiles are STORED into its
-// slab row, which has the layout of the parameter vector.  blockIdx.x: chunk, blockIdx.y: job.
-struct Job {
-  const __bf16* A; const __bf16* B;
-  int a_ld, O, o0;           // A: row stride, valid output features, first feature of this block
-  int b_ld, I;               // B: row stride = columns staged (a multiple of 8), valid input columns
-  int w_off, w_ld, b_off;    // dW[o][i] -> slab[w_off + o * w_ld + i]; db -> slab[b_off + o] (b_off < 0: none)
-};
+// Weight gradients (sample_chain.h::wgrad_job); a chunk's slab row has the layout of the parameter vector.  blockIdx.x: chunk,
+// blockIdx.y: job.
 struct WgradArgs {
   Plan p;
   const __bf16* code; const __bf16* dcode; const __bf16* h; const __bf16* feat; const __bf16* hv;
@@ -540,110 +468,18 @@ __device__ __forceinline__ Job job_of(const WgradArgs& a, int job) {
   j.w_off = p.w_rgb; j.w_ld = p.V; j.b_off = p.b_rgb;
   return j;
 }
-constexpr int kALd = kOBlock + 4, kBLd = 256 + 4;
 __global__ void __launch_bounds__(256) wgrad_kernel(const WgradArgs a) {
-  __shared__ __attribute__((aligned(16))) __bf16 As[kSub * kALd];
-  __shared__ __attribute__((aligned(16))) __bf16 Bs[kSub * kBLd];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
   const Job jb = job_of(a, blockIdx.y);
-  const __bf16 *A = jb.A, *B = jb.B;
-  const int a_ld = jb.a_ld, O = jb.O, o0 = jb.o0, b_ld = jb.b_ld, I = jb.I;
   const int64_t n0 = blockIdx.x * a.chunk;
   const int64_t n1 = n0 + a.chunk < a.n ? n0 + a.chunk : a.n;
-  float* out = a.slab + (size_t)blockIdx.x * a.p.slab_stride;
-  const int n_ot = o0 + 32 < O ? 2 : 1;
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[q >> 1][q & 1][r] = 0.0f;
-  float bsum = 0.0f;
-  for (int64_t s0 = n0; s0 < n1; s0 += kSub) {
-    __syncthreads();
-    {
-      const int s = tid >> 3, c = 8 * (tid & 7);
-      uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (s0 + s < n1 && o0 + c < a_ld) v = *reinterpret_cast<const uint4*>(A + (s0 + s) * a_ld + o0 + c);
-      uint2* dst = reinterpret_cast<uint2*>(As + s * kALd + c);
-      dst[0] = make_uint2(v.x, v.y); dst[1] = make_uint2(v.z, v.w);
-    }
-    const int groups = b_ld >> 3;
-    for (int e = tid; e < kSub * groups; e += 256) {
-      const int s = e / groups, c = 8 * (e % groups);
-      uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (s0 + s < n1) v = *reinterpret_cast<const uint4*>(B + (s0 + s) * b_ld + c);
-      uint2* dst = reinterpret_cast<uint2*>(Bs + s * kBLd + c);
-      dst[0] = make_uint2(v.x, v.y); dst[1] = make_uint2(v.z, v.w);
-    }
-    __syncthreads();
-    if (tid < kOBlock) {
-      for (int s = 0; s < kSub; ++s) bsum += (float)As[s * kALd + tid];
-    }
-#pragma unroll
-    for (int kk = 0; kk < kSub / 16; ++kk) {
-      const int srow = 16 * kk + 8 * half;
-      bf16x8 fa[2], fb[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) fa[t][j] = As[(srow + j) * kALd + 32 * t + col];
-      }
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const int it = wave + 4 * t;
-        if (32 * it < b_ld) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) fb[t][j] = Bs[(srow + j) * kBLd + 32 * it + col];
-        } else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) fb[t][j] = (__bf16)0.0f;
-        }
-      }
-#pragma unroll
-      for (int ot = 0; ot < 2; ++ot) {
-        if (ot < n_ot) {
-#pragma unroll
-          for (int t = 0; t < 2; ++t)
-            if (32 * (wave + 4 * t) < b_ld) acc[ot][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ot], fb[t], acc[ot][t], 0, 0, 0);
-        }
-      }
-    }
-  }
-  // accumulator register r of lane (col, half): output feature 8 (r >> 2) + 4 half + (r & 3), input column col
-#pragma unroll
-  for (int ot = 0; ot < 2; ++ot) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int i = 32 * (wave + 4 * t) + col;
-      if (ot >= n_ot || i >= I) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int o = o0 + 32 * ot + 8 * (r >> 2) + 4 * half + (r & 3);
-        if (o < O) out[jb.w_off + o * jb.w_ld + i] = acc[ot][t][r];
-      }
-    }
-  }
-  if (jb.b_off >= 0 && tid < kOBlock && o0 + tid < O) out[jb.b_off + o0 + tid] = bsum;
+  wgrad_job(jb, n0, n1, a.slab + (size_t)blockIdx.x * a.p.slab_stride);
 }
 
 // grads[q] = sum over chunks, in chunk order
 __global__ void __launch_bounds__(256) reduce_kernel(const float* __restrict__ slab, int chunks, int stride, int n_params,
                                                     float* __restrict__ grads) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= n_params) return;
-  float s = 0.0f;
-  for (int c = 0; c < chunks; ++c) s += slab[(size_t)c * stride + q];
-  grads[q] = s;
-}
-
-static void chunking(int64_t n, int64_t* chunk, int64_t* chunks) {
-  // chunks of at least kMinChunk samples (multiples of kSub), at most kMaxChunks of them
-  int64_t c = (n + kMinChunk - 1) / kMinChunk;
-  if (c > kMaxChunks) c = kMaxChunks;
-  int64_t len = (n + c - 1) / c;
-  len = (len + kSub - 1) / kSub * kSub;
-  *chunk = len;
-  *chunks = (n + len - 1) / len;
+  if (q < n_params) grads[q] = ordered_sum(slab, chunks, stride, q);
 }
 
 struct Layout {
@@ -655,50 +491,39 @@ static Layout layout(const Plan& p, int64_t n) {
   s.n_pad = (n + kPadRows - 1) / kPadRows * kPadRows;
   const size_t np = (size_t)s.n_pad;
   size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
   int64_t chunk, chunks;
   chunking(n, &chunk, &chunks);
-  s.code = take(np * kCodeLd * 2);
-  s.dcode = take(np * kDirLd * 2);
-  s.h = take(np * p.H * 2 * p.layers);
-  s.feat = take(np * p.H * 2);
-  s.hv = take(np * kVPad * 2);
-  s.drgb = take(np * kSmallLd * 2);
-  s.dsig = take(np * kSmallLd * 2);
-  s.dzv = take(np * kVPad * 2);
-  s.dfeat = take(np * p.H * 2);
-  s.dz = take(np * p.H * 2 * p.layers);
-  s.slab = take((size_t)chunks * p.slab_stride * 4);
+  s.code = take(&o, np * kCodeLd * 2);
+  s.dcode = take(&o, np * kDirLd * 2);
+  s.h = take(&o, np * p.H * 2 * p.layers);
+  s.feat = take(&o, np * p.H * 2);
+  s.hv = take(&o, np * kVPad * 2);
+  s.drgb = take(&o, np * kSmallLd * 2);
+  s.dsig = take(&o, np * kSmallLd * 2);
+  s.dzv = take(&o, np * kVPad * 2);
+  s.dfeat = take(&o, np * p.H * 2);
+  s.dz = take(&o, np * p.H * 2 * p.layers);
+  s.slab = take(&o, (size_t)chunks * p.slab_stride * 4);
   s.total = o;
   return s;
 }
-static int grid_for(const Plan& p, int64_t tiles) {
-  int n_cu = 0;
-  if (device_cu_count(&n_cu) != NERF_OK) return -1;
-  const int64_t cap = (int64_t)n_cu * (p.H == 256 ? 1 : 2);       // H = 256: one step fills the LDS of a CU
-  return (int)(tiles < cap ? tiles : cap);
-}
 static int lds_bytes(const Plan& p) { return p.lds_frags * 1024; }
 
-template <int H>
-static int launch_fwd(const Args& a, bool train, nerf_stream_t stream, const char* what) {
-  const int lds = lds_bytes(a.p), threads = 64 * fwd_waves<H>();
-  const int grid = grid_for(a.p, a.n_pad / (32 * fwd_waves<H>()));
-  if (grid <= 0) return fail(NERF_ELAUNCH, "%s: cannot query device", what);
-  const void* kernel = train ? (const void*)fwd_kernel<H, true> : (const void*)fwd_kernel<H, false>;
-  if (int rc = ensure_dynamic_lds(kernel, lds, what); rc != NERF_OK) return rc;
-  if (train) hipLaunchKernelGGL((fwd_kernel<H, true>), dim3(grid), dim3(threads), lds, as_stream(stream), a);
-  else hipLaunchKernelGGL((fwd_kernel<H, false>), dim3(grid), dim3(threads), lds, as_stream(stream), a);
-  return check_launch(what);
+typedef void (*ChainKernel)(Args);
+static ChainKernel fwd_kernel_of(int H, bool train) {
+  switch (H) {
+    case 64: return train ? fwd_kernel<64, true> : fwd_kernel<64, false>;
+    case 128: return train ? fwd_kernel<128, true> : fwd_kernel<128, false>;
+    default: return train ? fwd_kernel<256, true> : fwd_kernel<256, false>;
+  }
 }
-template <int H>
-static int launch_dgrad(const Args& a, nerf_stream_t stream, const char* what) {
-  const int lds = lds_bytes(a.p);
-  const int grid = grid_for(a.p, a.n_pad / (32 * fwd_waves<H>()));
+static ChainKernel dgrad_kernel_of(int H) { return H == 64 ? dgrad_kernel<64> : (H == 128 ? dgrad_kernel<128> : dgrad_kernel<256>); }
+// forward and dgrad run the same geometry; H = 256: one step fills the LDS of a CU
+static int launch(ChainKernel kernel, const Args& a, nerf_stream_t stream, const char* what) {
+  const int waves = fwd_waves(a.p.H);
+  const int grid = grid_for(a.n_pad / (32 * waves), a.p.H == 256 ? 1 : 2);
   if (grid <= 0) return fail(NERF_ELAUNCH, "%s: cannot query device", what);
-  if (int rc = ensure_dynamic_lds((const void*)dgrad_kernel<H>, lds, what); rc != NERF_OK) return rc;
-  hipLaunchKernelGGL((dgrad_kernel<H>), dim3(grid), dim3(64 * fwd_waves<H>()), lds, as_stream(stream), a);
-  return check_launch(what);
+  return launch_chain(kernel, grid, 64 * waves, lds_bytes(a.p), stream, what, a);
 }
 
 static int forward(const char* what, const void* packed, void* workspace, const float* rays_o, const float* rays_d, const float* z,
@@ -717,11 +542,7 @@ static int forward(const char* what, const void* packed, void* workspace, const 
     a.code = reinterpret_cast<__bf16*>(w + l.code); a.dcode = reinterpret_cast<__bf16*>(w + l.dcode);
     a.h = reinterpret_cast<__bf16*>(w + l.h); a.feat = reinterpret_cast<__bf16*>(w + l.feat); a.hv = reinterpret_cast<__bf16*>(w + l.hv);
   }
-  switch (plan.H) {
-    case 64: return launch_fwd<64>(a, train, stream, what);
-    case 128: return launch_fwd<128>(a, train, stream, what);
-    default: return launch_fwd<256>(a, train, stream, what);
-  }
+  return launch(fwd_kernel_of(plan.H, train), a, stream, what);
 }
 
 }  // namespace p2
@@ -791,12 +612,7 @@ extern "C" int nerf_p2_bwd(const void* packed, void* workspace, const float* rgb
   a.rgb = const_cast<float*>(rgb); a.sigma = const_cast<float*>(sigma); a.d_rgb = d_rgb; a.d_sigma = d_sigma;
   a.h = img(l.h); a.hv = img(l.hv);
   a.drgb = img(l.drgb); a.dsig = img(l.dsig); a.dzv = img(l.dzv); a.dfeat = img(l.dfeat); a.dz = img(l.dz);
-  int rc;
-  switch (hidden) {
-    case 64: rc = p2::launch_dgrad<64>(a, stream, "nerf_p2_bwd (dgrad)"); break;
-    case 128: rc = p2::launch_dgrad<128>(a, stream, "nerf_p2_bwd (dgrad)"); break;
-    default: rc = p2::launch_dgrad<256>(a, stream, "nerf_p2_bwd (dgrad)"); break;
-  }
+  int rc = p2::launch(p2::dgrad_kernel_of(hidden), a, stream, "nerf_p2_bwd (dgrad)");
   if (rc != NERF_OK) return rc;
   int64_t chunk, chunks;
   p2::chunking(n, &chunk, &chunks);

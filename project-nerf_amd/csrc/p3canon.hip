@@ -88,7 +88,7 @@ __device__ __forceinline__ void fwd_step(CanonRing& ring, const char*& a_base, b
     if constexpr (ch.group_first[g])
       a_base = ring.template advance<ch.group_chunk[g], STASH ? prev_chunk_stores(g) : 0>(more_passes);
     f32x16 acc = bias_tile(bias_lds, plan::bias_off(KIND) + 32 * m, half);
-    acc = mtile_mfma<KS>(a_base, ch.group_off[g], b, acc);
+    acc = mtile<KS>(a_base, ch.group_off[g], b, acc);
     epi(mc, acc);
   });
 }

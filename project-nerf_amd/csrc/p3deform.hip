@@ -95,28 +95,6 @@ __global__ void __launch_bounds__(256) pack_kernel(const float* __restrict__ par
   }
 }
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-template <int KS, class V, class F>
-__device__ __forceinline__ f32x16 mtile(const char* a_base, int frag_off, const V (&b)[KS], f32x16 acc, F mfma) {
-  constexpr int D = KS < kAhead ? KS : kAhead;
-  V win[D];
-#pragma unroll
-  for (int i = 0; i < D; ++i) win[i] = *reinterpret_cast<const V*>(a_base + (frag_off + i) * 1024);
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    const V cur = win[ks % D];
-    if (ks + D < KS) win[ks % D] = *reinterpret_cast<const V*>(a_base + (frag_off + ks + D) * 1024);
-    acc = mfma(cur, b[ks], acc);
-  }
-  return acc;
-}
-struct Mfma16 {
-  __device__ __forceinline__ f32x16 operator()(f16x8 a, f16x8 b, f32x16 c) const { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-struct MfmaBf {
-  __device__ __forceinline__ f32x16 operator()(bf16x8 a, bf16x8 b, f32x16 c) const { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
 // every m-tile of STEP: acc = bias (or 0) + A B, then epi(m, acc)
 template <int STEP, int KS, class V, class F, class Epi>
 __device__ __forceinline__ void run(const char* wbase, const V (&b)[KS], const float* bias_lds, F mfma, Epi&& epi) {

@@ -122,8 +122,6 @@ __global__ void __launch_bounds__(256) pack_kernel(const float* __restrict__ par
   if (blockIdx.x == 0 && threadIdx.x < 64) reinterpret_cast<float*>(packed + kPackBiasOff)[threadIdx.x] = params[kT2b + threadIdx.x];
 }
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 // 1-D Fourier code of the time stamp, element f of [t | sin(2^0 pi t) | cos(2^0 pi t) | sin(2^1 pi t) | ...] (21 columns);
 // ONE: column 21 = 1 (bias column of the time-modulation layer), else 0.  v[ks][j] = column 16 ks + 8 half + j.
 template <int KS, bool ONE>
@@ -161,21 +159,6 @@ __device__ __forceinline__ void cast_values(const float (&v)[KS][8], f16x8 (&h)[
     for (int j = 0; j < 8; ++j) { h[ks][j] = (_Float16)v[ks][j]; b[ks][j] = (__bf16)v[ks][j]; }
 }
 
-// forward m-tile on fp16 operands (the same rotating fragment window as mlp_chain.h::mtile_mfma)
-template <int KS>
-__device__ __forceinline__ f32x16 mtile_mfma16(const char* a_base, int frag_off, const f16x8 (&b)[KS], f32x16 acc) {
-  constexpr int D = KS < kAhead ? KS : kAhead;
-  f16x8 win[D];
-#pragma unroll
-  for (int i = 0; i < D; ++i) win[i] = *reinterpret_cast<const f16x8*>(a_base + (frag_off + i) * 1024);
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    const f16x8 cur = win[ks % D];
-    if (ks + D < KS) win[ks % D] = *reinterpret_cast<const f16x8*>(a_base + (frag_off + ks + D) * 1024);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur, b[ks], acc, 0, 0, 0);
-  }
-  return acc;
-}
 template <int STEP, int KS, class Epi>
 __device__ __forceinline__ void run16(const char* wbase, const f16x8 (&b)[KS], Epi&& epi) {
   constexpr Step st = step_of(STEP);
@@ -185,7 +168,7 @@ __device__ __forceinline__ void run16(const char* wbase, const f16x8 (&b)[KS], E
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    acc = mtile_mfma16<KS>(wbase, st.frag0 + m * KS, b, acc);
+    acc = mtile<KS>(wbase, st.frag0 + m * KS, b, acc, Mfma16{});
     epi(mc, acc);
   });
 }
@@ -206,7 +189,7 @@ __device__ __forceinline__ void run(const char* wbase, const bf16x8 (&b)[KS], Ep
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    acc = mtile_mfma<KS>(wbase, st.frag0 + m * KS, b, acc);
+    acc = mtile<KS>(wbase, st.frag0 + m * KS, b, acc);
     epi(mc, acc);
   });
 }
