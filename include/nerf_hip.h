@@ -43,7 +43,8 @@ extern "C" {
 /* 4: the Part 3 canonical decoder entries nerf_p3_canon_* are new. */
 /* 5: the Part 1 image-fit chain entries nerf_p1_* are new. */
 /* 6: the vanilla NeRF decoder chain for non-default shapes, nerf_p2_*, is new. */
-#define NERF_ABI_VERSION 6
+/* 7: the Instant-NGP tiny-MLP chain for non-default shapes, nerf_imlp_shape_*, is new. */
+#define NERF_ABI_VERSION 7
 
 typedef void* nerf_stream_t;
 
@@ -786,6 +787,43 @@ int nerf_p2_fwd_train(const void* packed, void* workspace, const float* rays_o, 
  * directions are not learned: no gradient with respect to the codes. */
 int nerf_p2_bwd(const void* packed, void* workspace, const float* rgb, const float* sigma, const float* d_rgb, const float* d_sigma,
                 int64_t n, int hidden, int layers, int skip, int view, int L_embed, int L_dir, float* grads_f32, nerf_stream_t stream);
+
+/* ---- Instant-NGP tiny MLPs at non-default shapes (csrc/imlp_shapes.hip) ---------------------------------------------------
+ * Replaces, for mode part2_instant at a shape other than the default one (which keeps nerf_imlp_*), the two tinycudann
+ * FullyFusedMLP networks of InstantNeRFDecoder (reference src/decoders.py:100-162) and their part of loss.backward():
+ *   sigma-net 2 n_levels -> hidden_dim (ReLU) -> 16, sigma = softplus(h[0] - 5);
+ *   colour-net [h (16) | direction code (3 + 6 L_embed_dir)] -> hidden_dim (ReLU) -> hidden_dim (ReLU) -> 3 (sigmoid).
+ * Shape arguments, in this order: n_levels, hidden_dim, L_embed_dir.  Compiled: n_levels 1..16 (2 features per level),
+ * hidden_dim 32 / 64 / 128, L_embed_dir 0..4 (the default shape 16, 64, 4 included); anything else returns NERF_EINVAL with a
+ * nerf_last_error() text naming the key (sizes: 0, count: -1).
+ * params_f32 [nerf_imlp_shape_param_count(...)] = decoder.sigma_net.params | decoder.color_net.params (reference
+ * src/decoders.py:100-134; this build's layout, [out,in] row-major, in / out widths padded to 16):
+ *   [hidden_dim, pad16(2 n_levels)] | [16, hidden_dim] | [hidden_dim, pad16(16 + 3 + 6 L_embed_dir)] | [hidden_dim, hidden_dim] |
+ *   [16, hidden_dim]; at (16, 64, 4) this is the nerf_imlp_* vector.  bf16 MFMA operands and images, fp32 accumulation. */
+/* reference src/decoders.py:100-162 */
+int64_t nerf_imlp_shape_param_count(int n_levels, int hidden_dim, int L_embed_dir);
+/* reference src/decoders.py:100-162 */
+size_t nerf_imlp_shape_packed_bytes(int n_levels, int hidden_dim, int L_embed_dir);
+/* reference src/decoders.py:100-162: the workspace (256-byte aligned) holds the hash operand image, the training images and
+ * the weight-gradient partial tiles of n points */
+size_t nerf_imlp_shape_workspace_bytes(int64_t n, int n_levels, int hidden_dim, int L_embed_dir);
+/* reference src/decoders.py:100-162: where nerf_hash_encode_fwd's operand image (nat, bf16) goes in that workspace */
+size_t nerf_imlp_shape_hash_operand_offset(int64_t n, int n_levels, int hidden_dim, int L_embed_dir);
+/* reference src/decoders.py:100-162: fp32 flat parameters -> bf16 fragment image (packed: nerf_imlp_shape_packed_bytes(...),
+ * 256-byte aligned) */
+int nerf_imlp_shape_pack(const float* params_f32, int n_levels, int hidden_dim, int L_embed_dir, void* packed, nerf_stream_t stream);
+/* reference src/decoders.py:100-162 (forward, :136-162): rgb [n,3], sigma [n] from the hash operand image in the workspace and
+ * the unit view directions dirs [n,3] (their code is formed in registers).  The image's columns past 2 n_levels are never read
+ * as values.  train != 0: the same bits, and the layer images and ReLU masks nerf_imlp_shape_bwd reads are kept. */
+int nerf_imlp_shape_fwd(const void* packed, void* workspace, const float* dirs, int64_t n, int n_levels, int hidden_dim,
+                        int L_embed_dir, float* rgb, float* sigma, int train, nerf_stream_t stream);
+/* reference src/decoders.py:100-162 under loss.backward(): from d loss / d rgb [n,3], d sigma [n] and the rgb / sigma of the last
+ * training forward on this workspace, the gradient of every weight WRITTEN to grads_f32 [nerf_imlp_shape_param_count(...)] (pad
+ * rows and columns: exact zeros) and d_feat [n, 2 n_levels] fp32 row-major (8-byte aligned; what nerf_hash_encode_bwd_ws_store
+ * reads).  Partial tiles per chunk of samples and one reduction in chunk order: no atomics, the same bits on every run. */
+int nerf_imlp_shape_bwd(const void* packed, void* workspace, const float* rgb, const float* sigma, const float* d_rgb,
+                        const float* d_sigma, int64_t n, int n_levels, int hidden_dim, int L_embed_dir, float* grads_f32,
+                        float* d_feat, nerf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -143,6 +143,13 @@ PROTOTYPES = {
     "nerf_p2_fwd": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, i64, i32] + [i32] * 6 + [c_ptr, c_ptr, c_ptr]),
     "nerf_p2_fwd_train": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, i64, i32] + [i32] * 6 + [c_ptr, c_ptr, c_ptr]),
     "nerf_p2_bwd": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, i64] + [i32] * 6 + [c_ptr, c_ptr]),
+    "nerf_imlp_shape_param_count": (i64, [i32] * 3),
+    "nerf_imlp_shape_packed_bytes": (size_t, [i32] * 3),
+    "nerf_imlp_shape_workspace_bytes": (size_t, [i64] + [i32] * 3),
+    "nerf_imlp_shape_hash_operand_offset": (size_t, [i64] + [i32] * 3),
+    "nerf_imlp_shape_pack": (i32, [c_ptr] + [i32] * 3 + [c_ptr, c_ptr]),
+    "nerf_imlp_shape_fwd": (i32, [c_ptr, c_ptr, c_ptr, i64] + [i32] * 3 + [c_ptr, c_ptr, i32, c_ptr]),
+    "nerf_imlp_shape_bwd": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, i64] + [i32] * 3 + [c_ptr, c_ptr, c_ptr]),
     "nerf_tv_codes_bytes": (size_t, [i64]),
     "nerf_tv_normsq_codes": (i32, [c_ptr, c_ptr, i64, i32, f32, f32, c_ptr, i32, c_ptr, c_ptr]),
     "nerf_clip_adamw_small": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, i64, i32, f32, f32, f32, f32, f32, f32, f32, c_ptr, i32, c_ptr]),
@@ -155,7 +162,7 @@ PROTOTYPES = {
     "nerf_adamw_clip_step_shadow": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, i64, i32, f32, f32, f32, f32, f32, c_ptr, f32, f32, c_ptr, c_ptr]),
 }
 
-ABI_VERSION = 6      # the NERF_ABI_VERSION of include/nerf_hip.h this table was written against
+ABI_VERSION = 7      # the NERF_ABI_VERSION of include/nerf_hip.h this table was written against
 
 _lib = None
 

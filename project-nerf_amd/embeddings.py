@@ -71,20 +71,31 @@ class HashRepresentation(BaseRepresentation):
     def __init__(self, n_levels=16, n_features_per_level=2, log2_hashmap_size=19, base_resolution=16,
                  per_level_scale=1.5, bound=1.0):
         super().__init__()
-        if n_features_per_level != 2 or not 1 <= n_levels <= 16:
-            raise NotImplementedError("libnerf_hip's hash-grid kernels are compiled for 2 features per level and up to 16 levels")
+        if n_features_per_level not in (2, 4, 8) or not 1 <= n_levels <= 16:
+            raise NotImplementedError("libnerf_hip's hash-grid kernels are compiled for 2 features per level (4 and 8: two and four "
+                                      "passes of them) and up to 16 levels")
         self.bound = bound
+        self.n_features = n_features_per_level
         self.levels = ops.HashLevelTable(n_levels, log2_hashmap_size, base_resolution, per_level_scale)
-        init = (torch.rand(self.levels.entries * 2) * 2 - 1) * 1e-4
+        init = (torch.rand(self.levels.entries * n_features_per_level) * 2 - 1) * 1e-4
         self.encoding = ParamHolder(init, n_output_dims=n_levels * n_features_per_level)
         self._out_dim = self.encoding.n_output_dims
 
     def table(self):
+        if self.n_features != 2:
+            raise NotImplementedError("HashRepresentation.table(): the fused field kernels read a table of 2 features per level")
         return self.encoding.params.view(-1, 2)
 
     def forward(self, x):
-        """reference src/embeddings.py:75-89 (normalise to [0,1], clamp, encode); differentiable w.r.t. the table."""
-        return ops.hash_encode(self.table(), x, self.levels, self.bound)
+        """reference src/embeddings.py:75-89 (normalise to [0,1], clamp, encode); differentiable w.r.t. the table.
+        4 or 8 features per level (tinycudann's n_features_per_level, an entry's features adjacent in ``params``): the 2-feature
+        kernels once per feature pair of every entry, the pairs joined level by level."""
+        if self.n_features == 2:
+            return ops.hash_encode(self.table(), x, self.levels, self.bound)
+        t = self.encoding.params.view(-1, self.n_features)
+        n, L = x.shape[0], self.levels.n_levels
+        pairs = [ops.hash_encode(t[:, k:k + 2].contiguous(), x, self.levels, self.bound).view(n, L, 2) for k in range(0, self.n_features, 2)]
+        return torch.cat(pairs, dim=-1).reshape(n, L * self.n_features)
 
     @property
     def out_dim(self):

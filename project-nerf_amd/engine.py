@@ -229,9 +229,7 @@ class InstantNgpEngine:
         self.device = torch.device(device)
         self.seed = int(seed)
         self.bound = float(cfg.get("scene_bound", 1.5))
-        if cfg.get("n_levels", 16) != 16 or cfg.get("n_features_per_level", 2) != 2 or cfg.get("hidden_dim", 64) != 64:
-            raise NotImplementedError("libnerf_hip's tiny-MLP kernels are compiled for 16 levels x 2 features (32 hash "
-                                      "channels) and 64 hidden units")
+        self._check_shape(cfg)
         self.levels = ops.HashLevelTable(cfg.get("n_levels", 16), cfg.get("log2_hashmap_size", 19),
                                          cfg.get("base_resolution", 16), cfg.get("per_level_scale", 1.5))
         g = torch.Generator().manual_seed(seed)
@@ -244,15 +242,7 @@ class InstantNgpEngine:
         self._table_buf[:n_tab] = ((torch.rand(n_tab, generator=g) * 2 - 1) * 1e-4).to(self.device)
         self.table = self._table_buf[:n_tab]
         self.shard = None
-
-        def xavier(rows, cols, fi, fo):
-            return (torch.rand(rows, cols, generator=g) * 2 - 1) * (6.0 / (fi + fo)) ** 0.5
-        w1 = xavier(64, 48, 43, 64)
-        w1[:, 43:] = 0
-        w3 = xavier(16, 64, 64, 3)
-        w3[3:] = 0
-        self.net = torch.cat([xavier(64, 32, 32, 64).reshape(-1), xavier(16, 64, 64, 16).reshape(-1), w1.reshape(-1),
-                              xavier(64, 64, 64, 64).reshape(-1), w3.reshape(-1)]).to(self.device)
+        self.net = self._init_net(g).to(self.device)
         self._m_buf, self._v_buf = torch.zeros(n_pad, device=self.device), torch.zeros(n_pad, device=self.device)
         self.state = {"table": (self._m_buf[:n_tab], self._v_buf[:n_tab]), "net": (torch.zeros_like(self.net), torch.zeros_like(self.net))}
         self._g_table_buf = torch.zeros(n_pad, device=self.device)
@@ -277,7 +267,8 @@ class InstantNgpEngine:
         self._table_h_buf = torch.zeros(n_pad, device=self.device, dtype=torch.float16) if self.half_table else None
         self.table_h = self._table_h_buf[:n_tab] if self.half_table else None
         self._table_version = None
-        self.packed = ops.imlp_pack(self.net)
+        self.packed = None
+        self._pack()
         self.near, self.far = float(cfg.get("near", 2.0)), float(cfg.get("far", 6.0))
         self.lr0, self.eta_min = float(cfg.get("learning_rate", 1e-2)), float(cfg.get("eta_min", 1e-4))
         self.t_max = int(cfg.get("train_iters", 2000))
@@ -292,6 +283,30 @@ class InstantNgpEngine:
         self._scratch = ops.normsq_ws(self.device)
         self._net_scratch = ops.normsq_ws(self.device)
         self._loss_ring = torch.zeros(65536, device=self.device)      # a step's loss is a VIEW of its slot: valid for the next 32768 steps
+
+    # the decoder's shape-specific pieces (instant_shapes.InstantShapeEngine overrides them and _field)
+    def _check_shape(self, cfg: dict) -> None:
+        if cfg.get("n_levels", 16) != 16 or cfg.get("n_features_per_level", 2) != 2 or cfg.get("hidden_dim", 64) != 64:
+            raise NotImplementedError("libnerf_hip's tiny-MLP kernels are compiled for 16 levels x 2 features (32 hash "
+                                      "channels) and 64 hidden units")
+
+    def _init_net(self, g: torch.Generator) -> Tensor:
+        def xavier(rows, cols, fi, fo):
+            return (torch.rand(rows, cols, generator=g) * 2 - 1) * (6.0 / (fi + fo)) ** 0.5
+        w1 = xavier(64, 48, 43, 64)
+        w1[:, 43:] = 0
+        w3 = xavier(16, 64, 64, 3)
+        w3[3:] = 0
+        return torch.cat([xavier(64, 32, 32, 64).reshape(-1), xavier(16, 64, 64, 16).reshape(-1), w1.reshape(-1),
+                          xavier(64, 64, 64, 64).reshape(-1), w3.reshape(-1)])
+
+    def _pack(self) -> None:
+        self.packed = ops.imlp_pack(self.net, self.packed)
+
+    def _decoder_bwd(self, ws: Tensor, rgb: Tensor, sigma: Tensor, d_rgb: Tensor, d_sigma: Tensor, n: int, d_feat: Tensor) -> None:
+        P = lambda t: t.data_ptr()
+        ops._lib.check(ops._lib.load().nerf_imlp_bwd(P(self.packed), P(ws), P(rgb), P(sigma), P(d_rgb), P(d_sigma), n,
+                                                     P(self.g_net), P(d_feat), ops._stream()), "nerf_imlp_bwd")
 
     def lr(self) -> float:
         import math
@@ -450,8 +465,7 @@ class InstantNgpEngine:
                     self.spec.counted(hws, grid_id, n)
                 return loss[0]
             d_feat = torch.empty(n, 2 * self.levels.n_levels, device=self.device)
-            ops._lib.check(lib.nerf_imlp_bwd(P(self.packed), P(ws), P(rgb), P(sigma), P(d_rgb), P(d_sigma), n,
-                                             P(self.g_net), P(d_feat), ops._stream()), "nerf_imlp_bwd")
+            self._decoder_bwd(ws, rgb, sigma, d_rgb, d_sigma, n, d_feat)
             reduce(self.g_net)
             # overwrite form: the table gradient is stored slice by slice -- no 52 MB memset, no read-back
             if sync_grads_async is None:
@@ -517,7 +531,7 @@ class InstantNgpEngine:
                                    weight_decay=self.wd, grad_scale=scale, scratch=self._net_scratch)
             self.shard.exchange()
             self._table_version = self.table._version      # the fp16 copy is current (all-gathered); the fp32 master only in this slice
-            ops.imlp_pack(self.net, self.packed)
+            self._pack()
             return
         if getattr(self, "_tv_codes", None) is None:
             self._tv_codes = torch.empty((self.table.numel() + 3) // 4, dtype=torch.uint8, device=self.device)
@@ -526,7 +540,7 @@ class InstantNgpEngine:
                                shadow_f16=self.table_h if self._table_version == self.table._version else None)
         ops.tv_clip_adamw_step(self.net, self.g_net, *self.state["net"], self.step_count, lr, max_norm=1.0,
                                weight_decay=self.wd, grad_scale=scale, scratch=self._scratch)
-        ops.imlp_pack(self.net, self.packed)
+        self._pack()
 
     def train_step(self, rays_o: Tensor, rays_d: Tensor, target: Tensor, n_samples: int = 128,
                    u: Optional[Tensor] = None, sync_grads=None, sync_grads_async=None, reduce_dtype=None, prepared=None) -> Tensor:

@@ -28,6 +28,8 @@ def build_instant_field(field, config):
 
     def _instant_forward(x, d):
         rep, dec = field.representation, field.decoder
+        if not dec.fused or rep.n_features != 2:   # another shape: the stand-alone operators composed (library GEMMs + autograd)
+            return dec(rep(x), field.dir_representation(d))
         rgb, sigma = ops.instant_field(rep.table(), dec.flat_parameters(), dec.packed_weights(), x, d, rep.levels, rep.bound)
         return rgb, sigma.unsqueeze(-1)
     field._instant_forward = _instant_forward
@@ -103,8 +105,23 @@ def run_instant(cfg, args):
     # and evaluation.  `engine: false` in the YAML or another shape: NeuralField + torch.optim.AdamW below.
     use_engine = (not args.eval_only and cfg.get("engine", True) and grid is not None and model.decoder.fused
                   and cfg.get("n_levels", 16) == 16 and cfg.get("n_features_per_level", 2) == 2)
-    if use_engine:
+    # Another hash / tiny-MLP shape with an explicit `engine: true`: the same step on the shape-generic chain
+    # (instant_shapes.InstantShapeEngine, csrc/imlp_shapes.hip), one rank; otherwise the module path below, with the reason.
+    shape_engine = False
+    if (not use_engine and not args.eval_only and cfg.get("engine") is True
+            and (cfg.get("n_levels", 16), cfg.get("n_features_per_level", 2), cfg.get("hidden_dim", 64), cfg.get("L_embed_dir", 4)) != (16, 2, 64, 4)):
+        from . import instant_shapes
+        why = instant_shapes.supported(cfg) if world == 1 else f"world_size={world} (compiled: 1)"
+        shape_engine = why is None
+        if shape_engine:
+            say(f">>> Part 2 Instant on the fused HIP shape engine (n_levels {cfg.get('n_levels', 16)}, hidden_dim "
+                f"{cfg.get('hidden_dim', 64)}, L_embed_dir {cfg.get('L_embed_dir', 4)})")
+        else:
+            say(f">>> Part 2 Instant shape engine not used: {why}; training on the module path")
+    if use_engine or shape_engine:
         from .engine import InstantNgpEngine
+        if shape_engine:
+            InstantNgpEngine = instant_shapes.InstantShapeEngine
         eng = InstantNgpEngine({**cfg, "scene_bound": cfg.get("scene_bound", 1.5), "grid_threshold": grid.threshold,
                                 "grid_resolution": grid.resolution, "train_iters": iters, "learning_rate": lr}, device=str(device),
                                seed=int(cfg.get("seed", 0) or 0), world_size=world)
@@ -118,13 +135,13 @@ def run_instant(cfg, args):
         with torch.no_grad():                               # start from the NeuralField's weights (its init or the checkpoint)
             eng.table.copy_(model.representation.encoding.params)
             eng.net.copy_(model.decoder.flat_parameters())
-            eng.packed = ops.imlp_pack(eng.net)
+            eng._pack()
             eng.grid.copy_(grid.grid)
             eng.binary_grid.copy_(grid.binary_grid)
         # replicas start from rank 0's values whatever the seeds did (then stay equal: identical all-reduced gradients, a
         # squared norm summed in a fixed order, replicated occupancy-grid updates)
         parallel.broadcast_([eng.table, eng.net, eng.grid, eng.binary_grid])
-        eng.packed = ops.imlp_pack(eng.net)
+        eng._pack()
         sharded = world > 1 and cfg.get("dp_sharded_optimizer", True) and eng.half_table
         if sharded:
             # reduce-scatter of the table gradient, every rank steps its 1/N slice of the table (TV + norm + AdamW),

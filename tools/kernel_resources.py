@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Registers, LDS, scratch (spills) of every kernel in libnerf_hip.so, read from the code objects' metadata notes
 (no GPU needed):  python tools/kernel_resources.py [substring | tag]
-Tags: p1 (csrc/p1fit.hip), p2 (csrc/p2chain.hip: the Part 2 chain for non-default decoder shapes), p3c (csrc/p3canon.hip)."""
+Tags: p1 (csrc/p1fit.hip), p2 (csrc/p2chain.hip: the Part 2 chain for non-default decoder shapes), p3c (csrc/p3canon.hip),
+ishape (csrc/imlp_shapes.hip: the Instant-NGP tiny MLPs for non-default hash and hidden shapes)."""
 import os
 import re
 import struct
@@ -12,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "project-nerf_amd", "libnerf_hip.so")
 LLVM = "/opt/rocm/lib/llvm/bin"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
-TAGS = {"p1": "nerf::p1::", "p2": "nerf::p2::", "p3c": "nerf::p3c::"}
+TAGS = {"p1": "nerf::p1::", "p2": "nerf::p2::", "p3c": "nerf::p3c::", "ishape": "nerf::ishape::"}
 
 
 def code_objects(blob):
