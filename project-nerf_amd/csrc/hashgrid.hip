@@ -1046,15 +1046,131 @@ hash_bin_overflow_kernel(BinHeader* __restrict__ header, const BinRecord* __rest
   atomicExch(&h[threadIdx.x], 0u);
 }
 
-static int fill_levels(HashLevels& L, int n_levels, const float* scale, const unsigned* res, const unsigned* size,
-                       const unsigned* offset, const unsigned* dense, float bound) {
-  if (n_levels < 1 || n_levels > kMaxLevels) return fail(NERF_EINVAL, "hash grid: n_levels=%d (1..16)", n_levels);
-  L.n_levels = n_levels;
-  L.bound = bound;
-  for (int i = 0; i < n_levels; ++i) {
-    L.scale[i] = scale[i]; L.res[i] = res[i]; L.size[i] = size[i]; L.offset[i] = offset[i]; L.dense[i] = dense[i];
-    if (size[i] == 0) return fail(NERF_EINVAL, "hash grid: level %d has size 0", i);
+// The level description every extern "C" entry receives as seven arguments of these names (host arrays of n_levels elements each).
+#define LEVEL_ARGS LevelArgs{n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound}
+struct LevelArgs {
+  int n_levels;
+  const float* scale;
+  const unsigned *res, *size, *offset, *dense;
+  float bound;
+  unsigned entries() const {            // of one table: max(offset + size)
+    unsigned e = 0;
+    for (int i = 0; i < n_levels; ++i) e = offset[i] + size[i] > e ? offset[i] + size[i] : e;
+    return e;
   }
+};
+
+static int fill_levels(HashLevels& L, const LevelArgs& lv) {
+  if (lv.n_levels < 1 || lv.n_levels > kMaxLevels) return fail(NERF_EINVAL, "hash grid: n_levels=%d (1..16)", lv.n_levels);
+  L.n_levels = lv.n_levels;
+  L.bound = lv.bound;
+  for (int i = 0; i < lv.n_levels; ++i) {
+    L.scale[i] = lv.scale[i]; L.res[i] = lv.res[i]; L.size[i] = lv.size[i]; L.offset[i] = lv.offset[i]; L.dense[i] = lv.dense[i];
+    if (lv.size[i] == 0) return fail(NERF_EINVAL, "hash grid: level %d has size 0", i);
+  }
+  return NERF_OK;
+}
+
+// Who sized the bins and found the largest |gradient|: the call's own count pass; the forward (nerf_hash_encode_fwd_f16_hist) with the
+// decoder's backward (nerf_imlp_bwd_lm); nobody -- speculative: capacities from the true counts of the last call on the workspace.
+enum class BinForm { kCounted, kPrecounted, kSpeculative };
+enum class BinCountPass { kNone, kPointMajor, kPerLevel };
+
+// One call of the binned table-gradient pipeline (run_binned): memset -> count -> plan -> staged / direct scatter -> reduce ->
+// stage-convert -> overflow.  "1 table": as hash_bwd_impl sets the field, "k tables": as hash_bwd_tables_impl does.
+struct BinnedCall {
+  HashLevels L;
+  BinPlan plan;
+  bool any_staged, any_direct;   // a level of at most / more than kStagedBins slices (plan_bins)
+  BinWorkspace w;
+  int carve_levels;              // w is carved, and its record capacity sized, for: 1 table n_levels whatever the level range; k tables plan.count
+  BinForm form;                  // not kCounted: the plan pass folds the producer's amax slots; kPrecounted (1 table only): every point is live
+  BinCountPass count;            // kNone unless kCounted; 1 table: point-major up to kPmBins bins, per level beyond; k tables: point-major
+  bool overwrite;                // d_table is stored, not added to (the convert launch accumulates otherwise); k tables: always
+  bool write_est;                // the true counts stay in est[] for a later speculative call: 1 table on all levels only; k tables: always
+  bool staged_base_always;       // the staged scatter's overflow_base (read beside spec_start only): the capacity in every form (1 table) or
+                                 // 0 unless kSpeculative (k tables)
+  const float* d_feat;           // row-major gradients; NULL: the producer wrote the level-major copy
+  const float2* grad_lm;         // w.grad_lm where the scatter reads the level-major copy (point-major count pass, or producer), else NULL
+  unsigned table_entries;        // the reduce / convert passes' bound: 1 table max(offset + size); k tables (n_tables - 1) * table_stride + that
+  unsigned long long* istage;    // det_stage
+  unsigned dense_entries, chunk;
+  unsigned* status_host;         // kSpeculative: host-mapped copy of the status words, or NULL
+  const char* name;              // in error strings
+};
+
+// bin0[] of the plan's virtual levels (ceil(size / kSlice) slices each) and any_staged / any_direct.  Returns the first virtual level of
+// more than kMaxSlices slices, -1: none.
+static int plan_bins(BinnedCall& c, const LevelArgs& lv) {
+  int too_large = -1;
+  c.plan.bin0[0] = 0;
+  c.any_staged = c.any_direct = false;
+  for (int i = 0; i < c.plan.count; ++i) {
+    const unsigned slices = (lv.size[(c.plan.first + i) % lv.n_levels] + kSlice - 1) / kSlice;
+    if (slices > kMaxSlices && too_large < 0) too_large = c.plan.first + i;
+    c.plan.bin0[i + 1] = c.plan.bin0[i] + slices;
+    (slices <= kStagedBins ? c.any_staged : c.any_direct) = true;
+  }
+  return too_large;
+}
+
+// option "deterministic": the integer staging array of the cut bins (kFlushInt) lives in the slack of the record area -- a counted call
+// writes at most n * 8 * levels records of a capacity 1.25 x that + 64 per bin.  dense_entries: entries of the leading dense levels
+// (the only levels whose bins are cut then).  No room, or no dense level: istage NULL and chunk 0xffffffff, no bin is cut at all.
+static void det_stage(BinnedCall& c, int64_t n, const LevelArgs& lv) {
+  c.istage = nullptr; c.dense_entries = 0; c.chunk = kChunk;     // chunk: records per work item
+  if (!options().deterministic) return;
+  unsigned dense = 0;
+  for (int i = 0; i < lv.n_levels && lv.dense[i]; ++i) dense += lv.size[i];
+  const size_t used = (size_t)n * 8 * (size_t)c.carve_levels, cap = bin_record_capacity(n, c.carve_levels);
+  const size_t need = (size_t)c.plan.n_tables * dense * 2;     // 64-bit words, one BinRecord's size each
+  static_assert(sizeof(BinRecord) == sizeof(unsigned long long), "staging words");
+  if (dense == 0 || used + need > cap) c.chunk = 0xffffffffu;
+  else { c.istage = reinterpret_cast<unsigned long long*>(c.w.records + used); c.dense_entries = dense; }
+}
+
+// The only place that launches the hash_bin_* kernels.  The caller has checked its arguments and calls check_launch afterwards.
+static int run_binned(const BinnedCall& c, const float* pts, int64_t n, float* d_table, hipStream_t stream) {
+  const BinWorkspace& w = c.w;
+  const BinPlan& plan = c.plan;
+  const unsigned n_bins = plan.bin0[plan.count], capacity = (unsigned)bin_record_capacity(n, c.carve_levels);
+  const bool spec = c.form == BinForm::kSpeculative;
+  if (c.form == BinForm::kCounted && hipMemsetAsync(w.header, 0, 256 + sizeof(unsigned) * n_bins, stream) != hipSuccess)   // header + counts
+    return fail(NERF_ELAUNCH, "%s: memset failed", c.name);
+  const int64_t bx = (n + 511) / 512, bx_count = bx > 256 ? 256 : bx, bx_scatter = bx > 128 ? 128 : bx;
+  if (c.count == BinCountPass::kPointMajor) {
+    int64_t bpm = (n + 255) / 256;
+    if (bpm > 1024) bpm = 1024;
+    const int per_row = pm_levels_per_row(n, plan.count);
+    hipLaunchKernelGGL(hash_bin_count_pm_kernel, dim3((int)bpm, (plan.count + per_row - 1) / per_row), dim3(256), 0, stream, pts, n, c.L, plan,
+                       c.d_feat, w.count, w.header, w.grad_lm, per_row);
+  } else if (c.count == BinCountPass::kPerLevel)
+    hipLaunchKernelGGL(hash_bin_count_kernel, dim3((int)bx_count, plan.count), dim3(512), 0, stream, pts, n, c.L, plan, c.d_feat, w.count,
+                       w.header);
+  hipLaunchKernelGGL(hash_bin_plan_kernel, dim3(1), dim3(1024), 0, stream, c.L, plan, w.count, w.cursor, w.items, w.header, c.overwrite ? 1 : 0,
+                     c.chunk, c.write_est ? w.est : nullptr, spec ? w.start : nullptr, spec ? capacity : 0u, c.form != BinForm::kCounted ? 1 : 0,
+                     c.dense_entries, c.istage != nullptr);
+  float* zero_table = c.overwrite ? d_table : nullptr;
+  const unsigned* spec_start = spec ? w.start : nullptr;
+  const int all_live = c.form == BinForm::kPrecounted ? 1 : 0;
+  if (c.any_staged)
+    hipLaunchKernelGGL(hash_bin_scatter_kernel<true>, dim3((int)bx_scatter, plan.count), dim3(512), 0, stream, pts, n, c.L, plan, c.d_feat,
+                       w.cursor, w.records, w.header, c.grad_lm, w.count, zero_table, all_live, c.chunk, spec_start, w.overflow_bin, w.header,
+                       c.staged_base_always || spec ? capacity : 0u, c.istage, c.dense_entries);
+  if (c.any_direct)                        // never speculative (the callers refuse it)
+    hipLaunchKernelGGL(hash_bin_scatter_kernel<false>, dim3((int)bx_scatter, plan.count), dim3(512), 0, stream, pts, n, c.L, plan, c.d_feat,
+                       w.cursor, w.records, w.header, c.grad_lm, w.count, zero_table, all_live, c.chunk, (const unsigned*)nullptr, w.overflow_bin,
+                       w.header, 0u, c.istage, c.dense_entries);
+  size_t grid = (size_t)n * 8 * plan.count / kChunk + n_bins;
+  if (grid > 4096) grid = 4096;             // persistent beyond that: items are taken round-robin
+  hipLaunchKernelGGL(hash_bin_reduce_kernel, dim3((unsigned)grid), dim3(512), 0, stream, w.header, w.items, w.records, d_table,
+                     c.table_entries, spec ? w.cursor : (const unsigned*)nullptr, spec_start, w.est, c.istage);
+  if (c.istage != nullptr)
+    hipLaunchKernelGGL(hash_bin_stage_convert_kernel, dim3(256), dim3(256), 0, stream, w.header, w.items, c.istage, d_table, c.table_entries,
+                       c.overwrite ? 0 : 1);
+  if (spec)
+    hipLaunchKernelGGL(hash_bin_overflow_kernel, dim3(64), dim3(256), 0, stream, w.header, w.records + capacity, w.overflow_bin, c.L, plan,
+                       d_table, c.status_host);
   return NERF_OK;
 }
 
@@ -1062,82 +1178,22 @@ static int fill_levels(HashLevels& L, int n_levels, const float* scale, const un
 
 using namespace nerf;
 
-static int hash_fwd_impl(const float* pts, int64_t n, const float* table, const void* table_f16, int n_levels,
-                         const float* scale_host, const unsigned* res_host, const unsigned* size_host,
-                         const unsigned* offset_host, const unsigned* dense_host, float bound,
-                         float* out_f32, void* out_nat_bf16, unsigned* idx_out, nerf_stream_t stream, int nat_f16 = 0,
-                         void* bwd_workspace = nullptr, size_t bwd_workspace_bytes = 0, TableSet ts = TableSet{1, 0, 0});
+struct FwdExtras {                      // what only some forward entries ask for
+  int nat_f16 = 0;                      // the operand image in fp16 instead of bf16
+  void* bwd_workspace = nullptr;        // also count the corners per (level, slice) into the binned backward's workspace
+  size_t bwd_workspace_bytes = 0;
+  TableSet ts{1, 0, 0};                 // several tables of one level structure: operand images only
+};
 
-extern "C" int nerf_hash_encode_fwd(const float* pts, int64_t n, const float* table, int n_levels,
-                                    const float* scale_host, const unsigned* res_host, const unsigned* size_host,
-                                    const unsigned* offset_host, const unsigned* dense_host, float bound,
-                                    float* out_f32, void* out_nat_bf16, unsigned* idx_out, nerf_stream_t stream) {
-  return hash_fwd_impl(pts, n, table, nullptr, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound, out_f32,
-                       out_nat_bf16, idx_out, stream);
-}
-
-extern "C" int nerf_hash_encode_fwd_f16(const float* pts, int64_t n, const void* table_f16, int n_levels,
-                                        const float* scale_host, const unsigned* res_host, const unsigned* size_host,
-                                        const unsigned* offset_host, const unsigned* dense_host, float bound,
-                                        float* out_f32, void* out_nat_bf16, nerf_stream_t stream) {
-  NERF_REQUIRE(table_f16 != nullptr || n == 0, "nerf_hash_encode_fwd_f16: NULL table");
-  return hash_fwd_impl(pts, n, nullptr, table_f16, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound, out_f32,
-                       out_nat_bf16, nullptr, stream);
-}
-
-extern "C" int nerf_hash_encode_fwd_nat(const float* pts, int64_t n, const float* table_f32, const void* table_f16, int n_levels,
-                                        const float* scale_host, const unsigned* res_host, const unsigned* size_host,
-                                        const unsigned* offset_host, const unsigned* dense_host, float bound,
-                                        void* out_nat, int nat_dtype, nerf_stream_t stream) {
-  NERF_REQUIRE((table_f32 == nullptr) != (table_f16 == nullptr), "nerf_hash_encode_fwd_nat: exactly one of table_f32 / table_f16");
-  NERF_REQUIRE(nat_dtype == 0 || nat_dtype == 1, "nerf_hash_encode_fwd_nat: nat_dtype=%d (0 bf16, 1 fp16)", nat_dtype);
-  NERF_REQUIRE(n == 0 || out_nat != nullptr, "nerf_hash_encode_fwd_nat: out_nat is NULL");
-  return hash_fwd_impl(pts, n, table_f32, table_f16, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound,
-                       nullptr, out_nat, nullptr, stream, nat_dtype);
-}
-
-extern "C" int nerf_hash_encode_fwd_nat_tables(const float* pts, int64_t n, const void* tables_f16, int n_tables, int64_t table_stride,
-                                               int n_levels, const float* scale_host, const unsigned* res_host,
-                                               const unsigned* size_host, const unsigned* offset_host, const unsigned* dense_host,
-                                               float bound, void* out_nat, int64_t out_stride_bytes, int nat_dtype, nerf_stream_t stream) {
-  NERF_REQUIRE(n_tables >= 1 && n_tables <= 8 && table_stride >= 0 && out_stride_bytes >= 0 && out_stride_bytes % 2 == 0,
-               "nerf_hash_encode_fwd_nat_tables: n_tables=%d", n_tables);
-  NERF_REQUIRE(nat_dtype == 0 || nat_dtype == 1, "nerf_hash_encode_fwd_nat_tables: nat_dtype=%d (0 bf16, 1 fp16)", nat_dtype);
-  NERF_REQUIRE(n == 0 || (tables_f16 != nullptr && out_nat != nullptr), "nerf_hash_encode_fwd_nat_tables: NULL pointer");
-  return hash_fwd_impl(pts, n, nullptr, tables_f16, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound,
-                       nullptr, out_nat, nullptr, stream, nat_dtype, nullptr, 0, TableSet{n_tables, table_stride, out_stride_bytes / 2});
-}
-
-extern "C" int nerf_hash_encode_fwd_f16_hist(const float* pts, int64_t n, const void* table_f16, int n_levels,
-                                             const float* scale_host, const unsigned* res_host, const unsigned* size_host,
-                                             const unsigned* offset_host, const unsigned* dense_host, float bound,
-                                             void* out_nat_bf16, void* bwd_workspace, size_t bwd_workspace_bytes, nerf_stream_t stream) {
-  NERF_REQUIRE(n == 0 || (table_f16 && out_nat_bf16 && bwd_workspace), "nerf_hash_encode_fwd_f16_hist: NULL pointer");
-  return hash_fwd_impl(pts, n, nullptr, table_f16, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound, nullptr,
-                       out_nat_bf16, nullptr, stream, 0, bwd_workspace, bwd_workspace_bytes);
-}
-
-extern "C" int nerf_hash_encode_bwd_ws_slots(void* workspace, int64_t n, int n_levels, void** amax_bits_out, void** grad_lm_out) {
-  NERF_REQUIRE(workspace && n > 0 && n_levels >= 1 && n_levels <= kMaxPlanLevels && amax_bits_out && grad_lm_out, "nerf_hash_encode_bwd_ws_slots: bad arguments");
-  const BinWorkspace w = carve(workspace, n, n_levels);
-  *amax_bits_out = reinterpret_cast<unsigned*>(w.header) + kAmaxSlotWord;       // kAmaxSlots words (common.h::publish_amax_slots)
-  *grad_lm_out = w.grad_lm;
-  return NERF_OK;
-}
-
-static int hash_fwd_impl(const float* pts, int64_t n, const float* table, const void* table_f16, int n_levels,
-                         const float* scale_host, const unsigned* res_host, const unsigned* size_host,
-                         const unsigned* offset_host, const unsigned* dense_host, float bound,
-                         float* out_f32, void* out_nat_bf16, unsigned* idx_out, nerf_stream_t stream, int nat_f16,
-                         void* bwd_workspace, size_t bwd_workspace_bytes, TableSet ts) {
+static int hash_fwd_impl(const float* pts, int64_t n, const float* table, const void* table_f16, const LevelArgs& lv, float* out_f32,
+                         void* out_nat_bf16, unsigned* idx_out, nerf_stream_t stream, const FwdExtras& x = FwdExtras{}) {
   NERF_REQUIRE(n >= 0, "nerf_hash_encode_fwd: n=%lld", (long long)n);
   if (n == 0) return NERF_OK;
-  NERF_REQUIRE(pts && (table || table_f16) && scale_host && res_host && size_host && offset_host && dense_host,
-               "nerf_hash_encode_fwd: NULL pointer");
+  NERF_REQUIRE(pts && (table || table_f16) && lv.scale && lv.res && lv.size && lv.offset && lv.dense, "nerf_hash_encode_fwd: NULL pointer");
   NERF_REQUIRE(out_f32 || out_nat_bf16, "nerf_hash_encode_fwd: no output requested");
+  const int n_levels = lv.n_levels;
   HashLevels L;
-  int rc = fill_levels(L, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound);
-  if (rc != NERF_OK) return rc;
+  if (int rc = fill_levels(L, lv); rc != NERF_OK) return rc;
   const int64_t n_pad = (n + 127) / 128 * 128;
   int64_t blocks = (n_pad + 255) / 256;
   if (blocks > 2048) blocks = 2048;
@@ -1150,162 +1206,143 @@ static int hash_fwd_impl(const float* pts, int64_t n, const float* table, const 
   // counts are zeroed here), so that nerf_hash_encode_bwd_ws_store_precounted can skip its count pass
   unsigned* hist_count = nullptr;
   LevelBins lb{};
-  if (bwd_workspace != nullptr) {
-    NERF_REQUIRE(bwd_workspace_bytes >= bin_workspace_bytes(n, n_levels), "nerf_hash_encode_fwd_hist: workspace of %zu bytes, need %zu",
-                 bwd_workspace_bytes, bin_workspace_bytes(n, n_levels));
+  if (x.bwd_workspace != nullptr) {
+    NERF_REQUIRE(x.bwd_workspace_bytes >= bin_workspace_bytes(n, n_levels), "nerf_hash_encode_fwd_hist: workspace of %zu bytes, need %zu",
+                 x.bwd_workspace_bytes, bin_workspace_bytes(n, n_levels));
     unsigned max_slices = 0;
     for (int i = 0; i < n_levels; ++i) {
-      const unsigned slices = (size_host[i] + kSlice - 1) / kSlice;
+      const unsigned slices = (lv.size[i] + kSlice - 1) / kSlice;
       NERF_REQUIRE(slices <= kMaxSlices, "nerf_hash_encode_fwd_hist: level %d has %u slices (max %u)", i, slices, kMaxSlices);
       max_slices = slices > max_slices ? slices : max_slices;
       lb.bin0[i + 1] = lb.bin0[i] + slices;
     }
     NERF_REQUIRE(lb.bin0[n_levels] <= (unsigned)kMaxBins, "nerf_hash_encode_fwd_hist: %u bins (max %d)", lb.bin0[n_levels], kMaxBins);
-    const BinWorkspace w = carve(bwd_workspace, n, n_levels);
+    const BinWorkspace w = carve(x.bwd_workspace, n, n_levels);
     if (hipMemsetAsync(w.header, 0, 256 + sizeof(unsigned) * lb.bin0[n_levels], as_stream(stream)) != hipSuccess)
       return fail(NERF_ELAUNCH, "nerf_hash_encode_fwd_hist: memset failed");
     hist_count = w.count;
     if (lds < (int)(max_slices * sizeof(unsigned))) lds = (int)(max_slices * sizeof(unsigned));
   }
   const bool xcd = options().hash_xcd != 0;
-  NERF_REQUIRE(ts.n >= 1 && (ts.n == 1 || (out_f32 == nullptr && idx_out == nullptr && bwd_workspace == nullptr && out_nat_bf16 != nullptr)),
+  NERF_REQUIRE(x.ts.n >= 1 && (x.ts.n == 1 || (out_f32 == nullptr && idx_out == nullptr && x.bwd_workspace == nullptr && out_nat_bf16 != nullptr)),
                "nerf_hash_encode_fwd_nat_tables: several tables write operand images only");
-  const dim3 grid = level_chunk_grid(n_levels * ts.n, blocks, xcd);
+  const dim3 grid = level_chunk_grid(n_levels * x.ts.n, blocks, xcd);
   const int n_chunks = xcd ? (int)blocks : 0;
   if (table_f16 != nullptr)
     hipLaunchKernelGGL(hash_fwd_kernel<half2_t>, grid, dim3(256), lds, as_stream(stream), pts, n, n_pad,
-                       static_cast<const half2_t*>(table_f16), L, out_f32, static_cast<__bf16*>(out_nat_bf16), idx_out, nat_f16,
-                       hist_count, lb, n_chunks, ts);
+                       static_cast<const half2_t*>(table_f16), L, out_f32, static_cast<__bf16*>(out_nat_bf16), idx_out, x.nat_f16,
+                       hist_count, lb, n_chunks, x.ts);
   else
     hipLaunchKernelGGL(hash_fwd_kernel<float2>, grid, dim3(256), lds, as_stream(stream), pts, n, n_pad,
-                       reinterpret_cast<const float2*>(table), L, out_f32, static_cast<__bf16*>(out_nat_bf16), idx_out, nat_f16,
-                       hist_count, lb, n_chunks, ts);
+                       reinterpret_cast<const float2*>(table), L, out_f32, static_cast<__bf16*>(out_nat_bf16), idx_out, x.nat_f16,
+                       hist_count, lb, n_chunks, x.ts);
   return check_launch("nerf_hash_encode_fwd");
 }
 
-// option "deterministic": the integer staging array of the cut bins (kFlushInt) lives in the slack of the record area -- a counted call
-// writes at most n * 8 * levels records of a capacity 1.25 x that + 64 per bin.  dense_entries: entries of the leading dense levels
-// (the only levels whose bins are cut then).  ptr NULL: no room (or no dense level): no bin is cut at all, as before.
-struct DetStage { unsigned long long* ptr; unsigned dense_entries; };
-static DetStage det_stage(const BinWorkspace& w, int64_t n, int plan_levels, int n_levels, int n_tables, const unsigned* size_host,
-                          const unsigned* dense_host) {
-  DetStage d{nullptr, 0};
-  if (!options().deterministic) return d;
-  unsigned dense = 0;
-  for (int i = 0; i < n_levels && dense_host[i]; ++i) dense += size_host[i];
-  const size_t used = (size_t)n * 8 * (size_t)plan_levels, cap = bin_record_capacity(n, plan_levels);
-  const size_t need = (size_t)n_tables * dense * 2;            // 64-bit words, one BinRecord's size each
-  if (dense == 0 || used + need > cap) return d;
-  static_assert(sizeof(BinRecord) == sizeof(unsigned long long), "staging words");
-  d.ptr = reinterpret_cast<unsigned long long*>(w.records + used);
-  d.dense_entries = dense;
-  return d;
+extern "C" int nerf_hash_encode_fwd(const float* pts, int64_t n, const float* table, int n_levels,
+                                    const float* scale_host, const unsigned* res_host, const unsigned* size_host,
+                                    const unsigned* offset_host, const unsigned* dense_host, float bound,
+                                    float* out_f32, void* out_nat_bf16, unsigned* idx_out, nerf_stream_t stream) {
+  return hash_fwd_impl(pts, n, table, nullptr, LEVEL_ARGS, out_f32, out_nat_bf16, idx_out, stream);
 }
 
-static int hash_bwd_impl(const float* pts, int64_t n, int n_levels, const float* scale_host,
-                         const unsigned* res_host, const unsigned* size_host, const unsigned* offset_host,
-                         const unsigned* dense_host, float bound, const float* d_feat, float* d_table,
-                         int level0, int level1, nerf_stream_t stream, void* workspace = nullptr, size_t workspace_bytes = 0,
-                         bool overwrite = false, int precounted = 0, void* status_host = nullptr) {
-  // precounted: 0 the count pass runs here; 1 counts by the forward (nerf_hash_encode_fwd_f16_hist); 2 speculative: no counts at all
-  // (capacities from the last call's true counts).  1 and 2: largest |gradient| and level-major gradients by nerf_imlp_bwd_lm
-  const bool spec = precounted == 2;
+extern "C" int nerf_hash_encode_fwd_f16(const float* pts, int64_t n, const void* table_f16, int n_levels,
+                                        const float* scale_host, const unsigned* res_host, const unsigned* size_host,
+                                        const unsigned* offset_host, const unsigned* dense_host, float bound,
+                                        float* out_f32, void* out_nat_bf16, nerf_stream_t stream) {
+  NERF_REQUIRE(table_f16 != nullptr || n == 0, "nerf_hash_encode_fwd_f16: NULL table");
+  return hash_fwd_impl(pts, n, nullptr, table_f16, LEVEL_ARGS, out_f32, out_nat_bf16, nullptr, stream);
+}
+
+extern "C" int nerf_hash_encode_fwd_nat(const float* pts, int64_t n, const float* table_f32, const void* table_f16, int n_levels,
+                                        const float* scale_host, const unsigned* res_host, const unsigned* size_host,
+                                        const unsigned* offset_host, const unsigned* dense_host, float bound,
+                                        void* out_nat, int nat_dtype, nerf_stream_t stream) {
+  NERF_REQUIRE((table_f32 == nullptr) != (table_f16 == nullptr), "nerf_hash_encode_fwd_nat: exactly one of table_f32 / table_f16");
+  NERF_REQUIRE(nat_dtype == 0 || nat_dtype == 1, "nerf_hash_encode_fwd_nat: nat_dtype=%d (0 bf16, 1 fp16)", nat_dtype);
+  NERF_REQUIRE(n == 0 || out_nat != nullptr, "nerf_hash_encode_fwd_nat: out_nat is NULL");
+  FwdExtras x; x.nat_f16 = nat_dtype;
+  return hash_fwd_impl(pts, n, table_f32, table_f16, LEVEL_ARGS, nullptr, out_nat, nullptr, stream, x);
+}
+
+extern "C" int nerf_hash_encode_fwd_nat_tables(const float* pts, int64_t n, const void* tables_f16, int n_tables, int64_t table_stride,
+                                               int n_levels, const float* scale_host, const unsigned* res_host,
+                                               const unsigned* size_host, const unsigned* offset_host, const unsigned* dense_host,
+                                               float bound, void* out_nat, int64_t out_stride_bytes, int nat_dtype, nerf_stream_t stream) {
+  NERF_REQUIRE(n_tables >= 1 && n_tables <= 8 && table_stride >= 0 && out_stride_bytes >= 0 && out_stride_bytes % 2 == 0,
+               "nerf_hash_encode_fwd_nat_tables: n_tables=%d", n_tables);
+  NERF_REQUIRE(nat_dtype == 0 || nat_dtype == 1, "nerf_hash_encode_fwd_nat_tables: nat_dtype=%d (0 bf16, 1 fp16)", nat_dtype);
+  NERF_REQUIRE(n == 0 || (tables_f16 != nullptr && out_nat != nullptr), "nerf_hash_encode_fwd_nat_tables: NULL pointer");
+  FwdExtras x;
+  x.nat_f16 = nat_dtype; x.ts = TableSet{n_tables, table_stride, out_stride_bytes / 2};
+  return hash_fwd_impl(pts, n, nullptr, tables_f16, LEVEL_ARGS, nullptr, out_nat, nullptr, stream, x);
+}
+
+extern "C" int nerf_hash_encode_fwd_f16_hist(const float* pts, int64_t n, const void* table_f16, int n_levels,
+                                             const float* scale_host, const unsigned* res_host, const unsigned* size_host,
+                                             const unsigned* offset_host, const unsigned* dense_host, float bound,
+                                             void* out_nat_bf16, void* bwd_workspace, size_t bwd_workspace_bytes, nerf_stream_t stream) {
+  NERF_REQUIRE(n == 0 || (table_f16 && out_nat_bf16 && bwd_workspace), "nerf_hash_encode_fwd_f16_hist: NULL pointer");
+  FwdExtras x; x.bwd_workspace = bwd_workspace; x.bwd_workspace_bytes = bwd_workspace_bytes;
+  return hash_fwd_impl(pts, n, nullptr, table_f16, LEVEL_ARGS, nullptr, out_nat_bf16, nullptr, stream, x);
+}
+
+struct BwdWorkspace {                   // the workspace forms of hash_bwd_impl (ptr NULL: the LDS / atomic kernels)
+  void* ptr = nullptr;
+  size_t bytes = 0;
+  bool overwrite = false;               // d_table's level range is stored, not added to
+  BinForm form = BinForm::kCounted;     // kPrecounted, kSpeculative: largest |gradient| and level-major gradients by nerf_imlp_bwd_lm
+  void* status_host = nullptr;          // kSpeculative
+};
+
+static int hash_bwd_impl(const float* pts, int64_t n, const LevelArgs& lv, const float* d_feat, float* d_table, int level0, int level1,
+                         nerf_stream_t stream, const BwdWorkspace& ws = BwdWorkspace{}) {
+  const int n_levels = lv.n_levels;
+  const bool counted = ws.form == BinForm::kCounted, spec = ws.form == BinForm::kSpeculative;
   NERF_REQUIRE(level0 >= 0 && level0 <= level1 && level1 <= n_levels, "nerf_hash_encode_bwd: levels [%d, %d) of %d", level0, level1, n_levels);
   NERF_REQUIRE(n >= 0, "nerf_hash_encode_bwd: n=%lld", (long long)n);
   if (n == 0) return NERF_OK;
-  NERF_REQUIRE(pts && (d_feat || precounted) && d_table && scale_host && res_host && size_host && offset_host && dense_host,
-               "nerf_hash_encode_bwd: NULL pointer");
-  HashLevels L;
-  int rc = fill_levels(L, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound);
-  if (rc != NERF_OK) return rc;
-  rc = ensure_dynamic_lds((const void*)hash_bwd_kernel<true>, kLdsEntries * 8, "nerf_hash_encode_bwd");
-  if (rc != NERF_OK) return rc;
+  NERF_REQUIRE(pts && (d_feat || !counted) && d_table && lv.scale && lv.res && lv.size && lv.offset && lv.dense, "nerf_hash_encode_bwd: NULL pointer");
+  BinnedCall c;
+  if (int rc = fill_levels(c.L, lv); rc != NERF_OK) return rc;
+  if (int rc = ensure_dynamic_lds((const void*)hash_bwd_kernel<true>, kLdsEntries * 8, "nerf_hash_encode_bwd"); rc != NERF_OK) return rc;
   int n_small = 0;                      // leading levels whose table fits in LDS
-  while (n_small < n_levels && size_host[n_small] <= (unsigned)kLdsEntries) ++n_small;
-  // the workspace form bins EVERY level (the small dense ones too: their LDS pass is ds_add_f32-bound)
-  const int first_big = level0;
-  bool binned = workspace != nullptr && first_big < level1 && options().hash_bwd_only_level < 0 && !options().hash_bwd_atomic;
-  BinPlan plan;
+  while (n_small < n_levels && lv.size[n_small] <= (unsigned)kLdsEntries) ++n_small;
+  // the workspace form bins EVERY level of the range (the small dense ones too: their LDS pass is ds_add_f32-bound)
+  bool binned = ws.ptr != nullptr && level0 < level1 && options().hash_bwd_only_level < 0 && !options().hash_bwd_atomic;
   if (binned) {
-    plan.first = first_big;
-    plan.count = level1 - first_big;
-    plan.n_tables = 1;
-    plan.table_stride = 0;
-    plan.dfeat_stride = 0;
-    plan.bin0[0] = 0;
-    unsigned table_entries = 0;
-    for (int i = 0; i < n_levels; ++i) table_entries = offset_host[i] + size_host[i] > table_entries ? offset_host[i] + size_host[i] : table_entries;
-    for (int i = 0; i < plan.count; ++i) {
-      const unsigned slices = (size_host[first_big + i] + kSlice - 1) / kSlice;
-      if (slices > kMaxSlices) binned = false;
-      plan.bin0[i + 1] = plan.bin0[i] + slices;
-    }
-    if (binned && plan.bin0[plan.count] > (unsigned)kMaxBins) binned = false;
-    if (binned) {
-      NERF_REQUIRE(workspace_bytes >= bin_workspace_bytes(n, n_levels), "nerf_hash_encode_bwd_ws: workspace of %zu bytes, need %zu",
-                   workspace_bytes, bin_workspace_bytes(n, n_levels));
-      NERF_REQUIRE(bin_record_capacity(n, n_levels) < 0xffffffffull, "nerf_hash_encode_bwd_ws: n=%lld too large for 32-bit record offsets", (long long)n);
-      const BinWorkspace w = carve(workspace, n, n_levels);
-      const unsigned n_bins = plan.bin0[plan.count];
-      const bool whole = level0 == 0 && level1 == n_levels;      // the bins of a level range are numbered from 0: est[] only for whole calls
-      NERF_REQUIRE(!spec || (whole && overwrite), "nerf_hash_encode_bwd_ws_store_spec: all levels, overwrite form");
-      if (precounted == 0 && hipMemsetAsync(w.header, 0, 256 + sizeof(unsigned) * n_bins, as_stream(stream)) != hipSuccess)   // header + counts
-        return fail(NERF_ELAUNCH, "nerf_hash_encode_bwd_ws: memset failed");
-      int64_t bx = (n + 511) / 512;
-      const int64_t bx_count = bx > 256 ? 256 : bx, bx_scatter = bx > 128 ? 128 : bx;
-      // level-major gradients: written by the count pass here, or by nerf_imlp_bwd_lm (precounted forms called without d_feat)
-      const bool point_major = precounted != 0 ? d_feat == nullptr : n_bins <= kPmBins;
-      if (precounted != 0) {
-        // counts by the forward (nerf_hash_encode_fwd_f16_hist), largest |gradient| and level-major gradients by the
-        // decoder's backward (nerf_imlp_bwd_lm): nothing to do here
-      } else if (point_major) {
-        int64_t bpm = (n + 255) / 256;
-        if (bpm > 1024) bpm = 1024;
-        const int per_row = pm_levels_per_row(n, plan.count);
-        hipLaunchKernelGGL(hash_bin_count_pm_kernel, dim3((int)bpm, (plan.count + per_row - 1) / per_row), dim3(256), 0, as_stream(stream),
-                           pts, n, L, plan, d_feat, w.count, w.header, w.grad_lm, per_row);
-      } else
-        hipLaunchKernelGGL(hash_bin_count_kernel, dim3((int)bx_count, plan.count), dim3(512), 0, as_stream(stream), pts, n, L, plan, d_feat,
-                           w.count, w.header);
-      const float2* grad_lm = point_major ? w.grad_lm : nullptr;
-      const DetStage ds = det_stage(w, n, n_levels, n_levels, 1, size_host, dense_host);
-      const unsigned chunk = (options().deterministic && ds.ptr == nullptr) ? 0xffffffffu : kChunk;
-      bool any_staged = false, any_direct = false;
-      for (int i = 0; i < plan.count; ++i) (plan.bin0[i + 1] - plan.bin0[i] <= kStagedBins ? any_staged : any_direct) = true;
-      NERF_REQUIRE(!spec || !any_direct, "nerf_hash_encode_bwd_ws_store_spec: a level with more than %u slices", kStagedBins);
-      hipLaunchKernelGGL(hash_bin_plan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), L, plan, w.count, w.cursor, w.items, w.header,
-                         overwrite ? 1 : 0, chunk, whole ? w.est : nullptr, spec ? w.start : nullptr,
-                         spec ? (unsigned)bin_record_capacity(n, n_levels) : 0u, precounted != 0 ? 1 : 0, ds.dense_entries, ds.ptr != nullptr);
-      float* zero_table = overwrite ? d_table : nullptr;
-      const unsigned* spec_start = spec ? w.start : nullptr;
-      if (any_staged)
-        hipLaunchKernelGGL(hash_bin_scatter_kernel<true>, dim3((int)bx_scatter, plan.count), dim3(512), 0, as_stream(stream), pts, n, L,
-                           plan, d_feat, w.cursor, w.records, w.header, grad_lm, w.count, zero_table, precounted == 1 ? 1 : 0, chunk,
-                           spec_start, w.overflow_bin, w.header, (unsigned)bin_record_capacity(n, n_levels), ds.ptr, ds.dense_entries);
-      if (any_direct)
-        hipLaunchKernelGGL(hash_bin_scatter_kernel<false>, dim3((int)bx_scatter, plan.count), dim3(512), 0, as_stream(stream), pts, n, L,
-                           plan, d_feat, w.cursor, w.records, w.header, grad_lm, w.count, zero_table, precounted == 1 ? 1 : 0, chunk,
-                           (const unsigned*)nullptr, w.overflow_bin, w.header, 0u, ds.ptr, ds.dense_entries);
-      size_t grid = (size_t)n * 8 * plan.count / kChunk + n_bins;
-      if (grid > 4096) grid = 4096;             // persistent beyond that: items are taken round-robin
-      hipLaunchKernelGGL(hash_bin_reduce_kernel, dim3((unsigned)grid), dim3(512), 0, as_stream(stream), w.header, w.items, w.records,
-                         d_table, table_entries, spec ? w.cursor : (const unsigned*)nullptr, spec_start, w.est, ds.ptr);
-      if (ds.ptr != nullptr)
-        hipLaunchKernelGGL(hash_bin_stage_convert_kernel, dim3(256), dim3(256), 0, as_stream(stream), w.header, w.items, ds.ptr, d_table,
-                           table_entries, overwrite ? 0 : 1);
-      if (spec)
-        hipLaunchKernelGGL(hash_bin_overflow_kernel, dim3(64), dim3(256), 0, as_stream(stream), w.header,
-                           w.records + bin_record_capacity(n, n_levels), w.overflow_bin, L, plan, d_table, static_cast<unsigned*>(status_host));
-    }
+    c.plan.first = level0; c.plan.count = level1 - level0;
+    c.plan.n_tables = 1; c.plan.table_stride = 0; c.plan.dfeat_stride = 0;
+    binned = plan_bins(c, lv) < 0 && c.plan.bin0[c.plan.count] <= (unsigned)kMaxBins;      // else: the LDS / atomic kernels below
+  }
+  if (binned) {
+    NERF_REQUIRE(ws.bytes >= bin_workspace_bytes(n, n_levels), "nerf_hash_encode_bwd_ws: workspace of %zu bytes, need %zu", ws.bytes,
+                 bin_workspace_bytes(n, n_levels));
+    // this caller's 32-bit guard: the whole record CAPACITY of all levels (the several-table caller bounds the records of a counted call)
+    NERF_REQUIRE(bin_record_capacity(n, n_levels) < 0xffffffffull, "nerf_hash_encode_bwd_ws: n=%lld too large for 32-bit record offsets", (long long)n);
+    c.carve_levels = n_levels; c.w = carve(ws.ptr, n, n_levels);
+    const bool whole = level0 == 0 && level1 == n_levels;
+    NERF_REQUIRE(!spec || (whole && ws.overwrite), "nerf_hash_encode_bwd_ws_store_spec: all levels, overwrite form");
+    NERF_REQUIRE(!spec || !c.any_direct, "nerf_hash_encode_bwd_ws_store_spec: a level with more than %u slices", kStagedBins);
+    // level-major gradients: written by the count pass here, or by nerf_imlp_bwd_lm (the other forms called without d_feat)
+    const bool point_major = counted ? c.plan.bin0[c.plan.count] <= kPmBins : d_feat == nullptr;
+    c.form = ws.form;
+    c.count = !counted ? BinCountPass::kNone : (point_major ? BinCountPass::kPointMajor : BinCountPass::kPerLevel);
+    c.overwrite = ws.overwrite; c.write_est = whole; c.staged_base_always = true;
+    c.d_feat = d_feat; c.grad_lm = point_major ? c.w.grad_lm : nullptr;
+    c.table_entries = lv.entries();
+    det_stage(c, n, lv);
+    c.status_host = static_cast<unsigned*>(ws.status_host); c.name = "nerf_hash_encode_bwd_ws";
+    if (int rc = run_binned(c, pts, n, d_table, as_stream(stream)); rc != NERF_OK) return rc;
   }
   if (options().deterministic && !binned && level0 < level1)
     return fail(NERF_EINVAL, "nerf_hash_encode_bwd: option \"deterministic\" needs the workspace form (nerf_hash_encode_bwd_ws*) -- the "
                              "other forms end in float atomics");
-  if (precounted != 0 && !binned)
+  if (!counted && !binned)
     return fail(NERF_EINVAL, "nerf_hash_encode_bwd_ws_store_precounted: the binned form is not available for this table shape / option set");
-  if (overwrite && !binned && level0 < level1) {
+  if (ws.overwrite && !binned && level0 < level1) {
     // the atomic forms accumulate: give them the zeroed range the overwrite contract promises
-    const size_t e0 = offset_host[level0], e1 = offset_host[level1 - 1] + size_host[level1 - 1];
+    const size_t e0 = lv.offset[level0], e1 = lv.offset[level1 - 1] + lv.size[level1 - 1];
     if (hipMemsetAsync(d_table + 2 * e0, 0, sizeof(float) * 2 * (e1 - e0), as_stream(stream)) != hipSuccess)
       return fail(NERF_ELAUNCH, "nerf_hash_encode_bwd_ws_store: memset failed");
   }
@@ -1313,7 +1350,7 @@ static int hash_bwd_impl(const float* pts, int64_t n, int n_levels, const float*
     const int hi = level1 < n_small ? level1 : n_small;
     int64_t bx = (n + 511) / 512;
     if (bx > 128) bx = 128;             // each workgroup flushes its whole LDS table once
-    hipLaunchKernelGGL(hash_bwd_kernel<true>, dim3((int)bx, hi - level0), dim3(512), kLdsEntries * 8, as_stream(stream), pts, n, L,
+    hipLaunchKernelGGL(hash_bwd_kernel<true>, dim3((int)bx, hi - level0), dim3(512), kLdsEntries * 8, as_stream(stream), pts, n, c.L,
                        level0, d_feat, d_table);
   }
   if (n_small < level1 && !binned) {
@@ -1325,7 +1362,7 @@ static int hash_bwd_impl(const float* pts, int64_t n, int n_levels, const float*
       count = 1;
       if (first < n_small || first >= level1) return check_launch("nerf_hash_encode_bwd");
     }
-    hipLaunchKernelGGL(hash_bwd_kernel<false>, dim3((int)bx, count), dim3(512), 0, as_stream(stream), pts, n, L,
+    hipLaunchKernelGGL(hash_bwd_kernel<false>, dim3((int)bx, count), dim3(512), 0, as_stream(stream), pts, n, c.L,
                        first, d_feat, d_table);
   }
   return check_launch("nerf_hash_encode_bwd");
@@ -1335,21 +1372,14 @@ extern "C" int nerf_hash_encode_bwd(const float* pts, int64_t n, int n_levels, c
                                     const unsigned* res_host, const unsigned* size_host, const unsigned* offset_host,
                                     const unsigned* dense_host, float bound, const float* d_feat, float* d_table,
                                     nerf_stream_t stream) {
-  return hash_bwd_impl(pts, n, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound, d_feat, d_table, 0,
-                       n_levels, stream);
+  return hash_bwd_impl(pts, n, LEVEL_ARGS, d_feat, d_table, 0, n_levels, stream);
 }
 
 extern "C" int nerf_hash_encode_bwd_levels(const float* pts, int64_t n, int n_levels, const float* scale_host,
                                            const unsigned* res_host, const unsigned* size_host, const unsigned* offset_host,
                                            const unsigned* dense_host, float bound, const float* d_feat, float* d_table,
                                            int first_level, int end_level, nerf_stream_t stream) {
-  return hash_bwd_impl(pts, n, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound, d_feat, d_table,
-                       first_level, end_level, stream);
-}
-
-extern "C" size_t nerf_hash_encode_bwd_workspace_bytes(int64_t n, int n_levels) {
-  if (n <= 0 || n_levels < 1 || n_levels > kMaxLevels) return 0;
-  return bin_workspace_bytes(n, n_levels);
+  return hash_bwd_impl(pts, n, LEVEL_ARGS, d_feat, d_table, first_level, end_level, stream);
 }
 
 extern "C" int nerf_hash_encode_bwd_ws(const float* pts, int64_t n, int n_levels, const float* scale_host,
@@ -1357,8 +1387,8 @@ extern "C" int nerf_hash_encode_bwd_ws(const float* pts, int64_t n, int n_levels
                                        const unsigned* dense_host, float bound, const float* d_feat, float* d_table,
                                        int first_level, int end_level, void* workspace, size_t workspace_bytes,
                                        nerf_stream_t stream) {
-  return hash_bwd_impl(pts, n, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound, d_feat, d_table,
-                       first_level, end_level, stream, workspace, workspace_bytes);
+  BwdWorkspace ws; ws.ptr = workspace; ws.bytes = workspace_bytes;
+  return hash_bwd_impl(pts, n, LEVEL_ARGS, d_feat, d_table, first_level, end_level, stream, ws);
 }
 
 extern "C" int nerf_hash_encode_bwd_ws_store(const float* pts, int64_t n, int n_levels, const float* scale_host,
@@ -1375,128 +1405,8 @@ extern "C" int nerf_hash_encode_bwd_ws_store(const float* pts, int64_t n, int n_
       return fail(NERF_ELAUNCH, "nerf_hash_encode_bwd_ws_store: memset failed");
     return NERF_OK;
   }
-  return hash_bwd_impl(pts, n, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound, d_feat, d_table,
-                       first_level, end_level, stream, workspace, workspace_bytes, true);
-}
-
-extern "C" size_t nerf_hash_encode_bwd_tables_workspace_bytes(int64_t n, int n_levels, int n_tables) {
-  if (n <= 0 || n_levels < 1 || n_levels > kMaxLevels || n_tables < 1 || n_levels * n_tables > kMaxPlanLevels) return 0;
-  return bin_workspace_bytes(n, n_levels * n_tables);
-}
-
-// The overwrite-form scatter for n_tables tables of ONE level structure from the same points in one pass of count / plan /
-// scatter / reduce launches (Part 4's three deformation grids: three passes of four small launches otherwise).
-static int hash_bwd_tables_impl(const float* pts, int64_t n, int n_tables, int64_t table_stride, int n_levels,
-                                const float* scale_host, const unsigned* res_host, const unsigned* size_host,
-                                const unsigned* offset_host, const unsigned* dense_host, float bound,
-                                const float* d_feat, int64_t dfeat_stride, float* d_table, void* workspace,
-                                size_t workspace_bytes, nerf_stream_t stream, bool spec, void* status_host) {
-  NERF_REQUIRE(n >= 0 && n_tables >= 1 && n_levels >= 1 && n_levels * n_tables <= kMaxPlanLevels && table_stride >= 0 && dfeat_stride >= 0,
-               "nerf_hash_encode_bwd_ws_store_tables: n=%lld, %d tables of %d levels (at most %d virtual levels)", (long long)n, n_tables,
-               n_levels, kMaxPlanLevels);
-  NERF_REQUIRE(d_table && size_host && offset_host, "nerf_hash_encode_bwd_ws_store_tables: NULL pointer");
-  unsigned entries = 0;
-  for (int i = 0; i < n_levels; ++i) entries = offset_host[i] + size_host[i] > entries ? offset_host[i] + size_host[i] : entries;
-  NERF_REQUIRE(n_tables == 1 || (uint64_t)table_stride >= entries, "nerf_hash_encode_bwd_ws_store_tables: table_stride %lld < %u entries",
-               (long long)table_stride, entries);
-  NERF_REQUIRE(((uint64_t)(n_tables - 1) * (uint64_t)table_stride + entries) < 0xffffffffull, "nerf_hash_encode_bwd_ws_store_tables: tables too large");
-  if (n == 0) {                                      // nothing to scatter: every table is still OVERWRITTEN (with zeros)
-    for (int t = 0; t < n_tables; ++t)
-      if (hipMemsetAsync(d_table + 2 * (size_t)t * table_stride, 0, sizeof(float) * 2 * entries, as_stream(stream)) != hipSuccess)
-        return fail(NERF_ELAUNCH, "nerf_hash_encode_bwd_ws_store_tables: memset failed");
-    return NERF_OK;
-  }
-  NERF_REQUIRE(pts && (d_feat || spec) && workspace && scale_host && res_host && dense_host, "nerf_hash_encode_bwd_ws_store_tables: NULL pointer");
-  HashLevels L;
-  if (int rc = fill_levels(L, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound); rc != NERF_OK) return rc;
-  BinPlan plan;
-  plan.first = 0;
-  plan.count = n_levels * n_tables;
-  plan.n_tables = n_tables;
-  plan.table_stride = (unsigned)table_stride;
-  plan.dfeat_stride = dfeat_stride;
-  plan.bin0[0] = 0;
-  bool any_staged = false, any_direct = false;
-  for (int v = 0; v < plan.count; ++v) {
-    const unsigned slices = (size_host[v % n_levels] + kSlice - 1) / kSlice;
-    NERF_REQUIRE(slices <= kMaxSlices, "nerf_hash_encode_bwd_ws_store_tables: level %d has %u slices (max %u)", v % n_levels, slices, kMaxSlices);
-    plan.bin0[v + 1] = plan.bin0[v] + slices;
-    (slices <= kStagedBins ? any_staged : any_direct) = true;
-  }
-  const unsigned n_bins = plan.bin0[plan.count];
-  NERF_REQUIRE(n_bins <= kPmBins, "nerf_hash_encode_bwd_ws_store_tables: %u bins (this form holds all histograms in LDS: max %u)", n_bins, kPmBins);
-  NERF_REQUIRE(workspace_bytes >= bin_workspace_bytes(n, plan.count), "nerf_hash_encode_bwd_ws_store_tables: workspace of %zu bytes, need %zu",
-               workspace_bytes, bin_workspace_bytes(n, plan.count));
-  NERF_REQUIRE((size_t)n * 8 * (size_t)plan.count < 0xffffffffull, "nerf_hash_encode_bwd_ws_store_tables: n=%lld too large for 32-bit record offsets",
-               (long long)n);
-  const BinWorkspace w = carve(workspace, n, plan.count);
-  const DetStage ds = det_stage(w, n, plan.count, n_levels, n_tables, size_host, dense_host);
-  const unsigned chunk = (options().deterministic && ds.ptr == nullptr) ? 0xffffffffu : kChunk;
-  const unsigned capacity = (unsigned)bin_record_capacity(n, plan.count);
-  const float2* grad_lm = w.grad_lm;
-  if (spec) {
-    // no count pass: capacities from the true counts the previous call on this workspace left in est[]; the chain's backward has
-    // max-accumulated the largest |gradient| into the header (nerf_hash_encode_bwd_ws_slots) and hands d_feat over row-major
-    NERF_REQUIRE(!any_direct && !options().deterministic, "nerf_hash_encode_bwd_ws_store_tables_spec: levels of at most %u slices, not with "
-                 "option \"deterministic\"", kStagedBins);
-    grad_lm = d_feat == nullptr ? w.grad_lm : nullptr;       // NULL d_feat: the producer wrote the level-major copy into the workspace
-  } else {
-    if (hipMemsetAsync(w.header, 0, 256 + sizeof(unsigned) * n_bins, as_stream(stream)) != hipSuccess)
-      return fail(NERF_ELAUNCH, "nerf_hash_encode_bwd_ws_store_tables: memset failed");
-    int64_t bpm = (n + 255) / 256;
-    if (bpm > 1024) bpm = 1024;
-    const int per_row = pm_levels_per_row(n, plan.count);
-    hipLaunchKernelGGL(hash_bin_count_pm_kernel, dim3((int)bpm, (plan.count + per_row - 1) / per_row), dim3(256), 0, as_stream(stream), pts, n,
-                       L, plan, d_feat, w.count, w.header, w.grad_lm, per_row);
-  }
-  // (the counted call leaves the bins' true counts in est[] for a later speculative one)
-  hipLaunchKernelGGL(hash_bin_plan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), L, plan, w.count, w.cursor, w.items, w.header, 1, chunk,
-                     w.est, spec ? w.start : (unsigned*)nullptr, spec ? capacity : 0u, spec ? 1 : 0, ds.dense_entries, ds.ptr != nullptr);
-  const unsigned* spec_start = spec ? w.start : nullptr;
-  int64_t bx = (n + 511) / 512;
-  const int64_t bx_scatter = bx > 128 ? 128 : bx;
-  if (any_staged)
-    hipLaunchKernelGGL(hash_bin_scatter_kernel<true>, dim3((int)bx_scatter, plan.count), dim3(512), 0, as_stream(stream), pts, n, L, plan,
-                       d_feat, w.cursor, w.records, w.header, grad_lm, w.count, d_table, 0, chunk, spec_start, w.overflow_bin, w.header,
-                       spec ? capacity : 0u, ds.ptr, ds.dense_entries);
-  if (any_direct)
-    hipLaunchKernelGGL(hash_bin_scatter_kernel<false>, dim3((int)bx_scatter, plan.count), dim3(512), 0, as_stream(stream), pts, n, L, plan,
-                       d_feat, w.cursor, w.records, w.header, grad_lm, w.count, d_table, 0, chunk, (const unsigned*)nullptr, w.overflow_bin, w.header, 0u,
-                       ds.ptr, ds.dense_entries);
-  size_t grid = (size_t)n * 8 * plan.count / kChunk + n_bins;
-  if (grid > 4096) grid = 4096;
-  hipLaunchKernelGGL(hash_bin_reduce_kernel, dim3((unsigned)grid), dim3(512), 0, as_stream(stream), w.header, w.items, w.records, d_table,
-                     (unsigned)((uint64_t)(n_tables - 1) * (uint64_t)table_stride + entries), spec ? w.cursor : (const unsigned*)nullptr, spec_start,
-                     w.est, ds.ptr);
-  if (ds.ptr != nullptr)
-    hipLaunchKernelGGL(hash_bin_stage_convert_kernel, dim3(256), dim3(256), 0, as_stream(stream), w.header, w.items, ds.ptr, d_table,
-                       (unsigned)((uint64_t)(n_tables - 1) * (uint64_t)table_stride + entries), 0);
-  if (spec)
-    hipLaunchKernelGGL(hash_bin_overflow_kernel, dim3(64), dim3(256), 0, as_stream(stream), w.header, w.records + capacity, w.overflow_bin, L,
-                       plan, d_table, static_cast<unsigned*>(status_host));
-  return check_launch("nerf_hash_encode_bwd_ws_store_tables");
-}
-
-extern "C" int nerf_hash_encode_bwd_ws_store_tables(const float* pts, int64_t n, int n_tables, int64_t table_stride, int n_levels,
-                                                    const float* scale_host, const unsigned* res_host, const unsigned* size_host,
-                                                    const unsigned* offset_host, const unsigned* dense_host, float bound,
-                                                    const float* d_feat, int64_t dfeat_stride, float* d_table, void* workspace,
-                                                    size_t workspace_bytes, nerf_stream_t stream) {
-  return hash_bwd_tables_impl(pts, n, n_tables, table_stride, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound, d_feat,
-                              dfeat_stride, d_table, workspace, workspace_bytes, stream, false, nullptr);
-}
-
-// ... its speculative form (see nerf_hash_encode_bwd_ws_store_spec): no count pass, capacities from the previous call's true counts
-// on this workspace; d_feat row-major, its largest magnitude max-accumulated into the slot nerf_hash_encode_bwd_ws_slots(workspace, n,
-// n_levels * n_tables, ...) names by the producer (nerf_p4_deform_bwd)
-extern "C" int nerf_hash_encode_bwd_ws_store_tables_spec(const float* pts, int64_t n, int n_tables, int64_t table_stride, int n_levels,
-                                                         const float* scale_host, const unsigned* res_host, const unsigned* size_host,
-                                                         const unsigned* offset_host, const unsigned* dense_host, float bound,
-                                                         const float* d_feat, int64_t dfeat_stride, float* d_table, void* workspace,
-                                                         size_t workspace_bytes, void* status_host, nerf_stream_t stream) {
-  NERF_REQUIRE(n > 0, "nerf_hash_encode_bwd_ws_store_tables_spec: n=%lld", (long long)n);
-  return hash_bwd_tables_impl(pts, n, n_tables, table_stride, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound, d_feat,
-                              dfeat_stride, d_table, workspace, workspace_bytes, stream, true, status_host);
+  BwdWorkspace ws; ws.ptr = workspace; ws.bytes = workspace_bytes; ws.overwrite = true;
+  return hash_bwd_impl(pts, n, LEVEL_ARGS, d_feat, d_table, first_level, end_level, stream, ws);
 }
 
 extern "C" int nerf_hash_encode_bwd_ws_store_precounted(const float* pts, int64_t n, int n_levels, const float* scale_host,
@@ -1504,8 +1414,8 @@ extern "C" int nerf_hash_encode_bwd_ws_store_precounted(const float* pts, int64_
                                                         const unsigned* offset_host, const unsigned* dense_host, float bound,
                                                         float* d_table, void* workspace, size_t workspace_bytes, nerf_stream_t stream) {
   NERF_REQUIRE(n > 0 && workspace != nullptr, "nerf_hash_encode_bwd_ws_store_precounted: n=%lld, workspace %p", (long long)n, workspace);
-  return hash_bwd_impl(pts, n, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound, nullptr, d_table, 0, n_levels,
-                       stream, workspace, workspace_bytes, true, 1);
+  BwdWorkspace ws; ws.ptr = workspace; ws.bytes = workspace_bytes; ws.overwrite = true; ws.form = BinForm::kPrecounted;
+  return hash_bwd_impl(pts, n, LEVEL_ARGS, nullptr, d_table, 0, n_levels, stream, ws);
 }
 
 // The speculative form: NO count pass -- bin capacities from the true counts the previous call (counted or speculative, all levels,
@@ -1526,8 +1436,27 @@ extern "C" int nerf_hash_encode_bwd_ws_store_spec(const float* pts, int64_t n, i
                                                   void* workspace, size_t workspace_bytes, void* status_host, nerf_stream_t stream) {
   NERF_REQUIRE(n > 0 && workspace != nullptr, "nerf_hash_encode_bwd_ws_store_spec: n=%lld, workspace %p", (long long)n, workspace);
   NERF_REQUIRE(!options().deterministic, "nerf_hash_encode_bwd_ws_store_spec: overflow records end in float atomics (option \"deterministic\" is set)");
-  return hash_bwd_impl(pts, n, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound, d_feat, d_table, 0, n_levels,
-                       stream, workspace, workspace_bytes, true, 2, status_host);
+  BwdWorkspace ws; ws.ptr = workspace; ws.bytes = workspace_bytes; ws.overwrite = true;
+  ws.form = BinForm::kSpeculative; ws.status_host = status_host;
+  return hash_bwd_impl(pts, n, LEVEL_ARGS, d_feat, d_table, 0, n_levels, stream, ws);
+}
+
+extern "C" size_t nerf_hash_encode_bwd_workspace_bytes(int64_t n, int n_levels) {
+  if (n <= 0 || n_levels < 1 || n_levels > kMaxLevels) return 0;
+  return bin_workspace_bytes(n, n_levels);
+}
+
+extern "C" size_t nerf_hash_encode_bwd_tables_workspace_bytes(int64_t n, int n_levels, int n_tables) {
+  if (n <= 0 || n_levels < 1 || n_levels > kMaxLevels || n_tables < 1 || n_levels * n_tables > kMaxPlanLevels) return 0;
+  return bin_workspace_bytes(n, n_levels * n_tables);
+}
+
+extern "C" int nerf_hash_encode_bwd_ws_slots(void* workspace, int64_t n, int n_levels, void** amax_bits_out, void** grad_lm_out) {
+  NERF_REQUIRE(workspace && n > 0 && n_levels >= 1 && n_levels <= kMaxPlanLevels && amax_bits_out && grad_lm_out, "nerf_hash_encode_bwd_ws_slots: bad arguments");
+  const BinWorkspace w = carve(workspace, n, n_levels);
+  *amax_bits_out = reinterpret_cast<unsigned*>(w.header) + kAmaxSlotWord;       // kAmaxSlots words (common.h::publish_amax_slots)
+  *grad_lm_out = w.grad_lm;
+  return NERF_OK;
 }
 
 // device address of the 8-word status block the LAST speculative call published: [0] items, [1] record capacity planned, [2] largest
@@ -1538,18 +1467,87 @@ extern "C" const void* nerf_hash_encode_bwd_spec_status(const void* workspace) {
   return workspace == nullptr ? nullptr : static_cast<const char*>(workspace) + sizeof(unsigned) * kSpecStatusWord;
 }
 
-static int hash_bwd_input_impl(const float* pts, int64_t n, const float* table, const void* table_f16, int n_levels,
-                               const float* scale_host, const unsigned* res_host, const unsigned* size_host,
-                               const unsigned* offset_host, const unsigned* dense_host, float bound,
+// The overwrite-form scatter for n_tables tables of ONE level structure from the same points in one pass of count / plan /
+// scatter / reduce launches (Part 4's three deformation grids: three passes of four small launches otherwise).
+static int hash_bwd_tables_impl(const float* pts, int64_t n, int n_tables, int64_t table_stride, const LevelArgs& lv, const float* d_feat,
+                                int64_t dfeat_stride, float* d_table, void* workspace, size_t workspace_bytes, nerf_stream_t stream,
+                                bool spec, void* status_host) {
+  const int n_levels = lv.n_levels;
+  NERF_REQUIRE(n >= 0 && n_tables >= 1 && n_levels >= 1 && n_levels * n_tables <= kMaxPlanLevels && table_stride >= 0 && dfeat_stride >= 0,
+               "nerf_hash_encode_bwd_ws_store_tables: n=%lld, %d tables of %d levels (at most %d virtual levels)", (long long)n, n_tables,
+               n_levels, kMaxPlanLevels);
+  NERF_REQUIRE(d_table && lv.size && lv.offset, "nerf_hash_encode_bwd_ws_store_tables: NULL pointer");
+  const unsigned entries = lv.entries();
+  NERF_REQUIRE(n_tables == 1 || (uint64_t)table_stride >= entries, "nerf_hash_encode_bwd_ws_store_tables: table_stride %lld < %u entries",
+               (long long)table_stride, entries);
+  NERF_REQUIRE(((uint64_t)(n_tables - 1) * (uint64_t)table_stride + entries) < 0xffffffffull, "nerf_hash_encode_bwd_ws_store_tables: tables too large");
+  if (n == 0) {                                      // nothing to scatter: every table is still OVERWRITTEN (with zeros)
+    for (int t = 0; t < n_tables; ++t)
+      if (hipMemsetAsync(d_table + 2 * (size_t)t * table_stride, 0, sizeof(float) * 2 * entries, as_stream(stream)) != hipSuccess)
+        return fail(NERF_ELAUNCH, "nerf_hash_encode_bwd_ws_store_tables: memset failed");
+    return NERF_OK;
+  }
+  NERF_REQUIRE(pts && (d_feat || spec) && workspace && lv.scale && lv.res && lv.dense, "nerf_hash_encode_bwd_ws_store_tables: NULL pointer");
+  BinnedCall c;
+  if (int rc = fill_levels(c.L, lv); rc != NERF_OK) return rc;
+  c.plan.first = 0; c.plan.count = n_levels * n_tables;
+  c.plan.n_tables = n_tables; c.plan.table_stride = (unsigned)table_stride; c.plan.dfeat_stride = dfeat_stride;
+  const int v = plan_bins(c, lv);
+  NERF_REQUIRE(v < 0, "nerf_hash_encode_bwd_ws_store_tables: level %d has %u slices (max %u)", v % n_levels,
+               (lv.size[v % n_levels] + kSlice - 1) / kSlice, kMaxSlices);
+  const unsigned n_bins = c.plan.bin0[c.plan.count];
+  NERF_REQUIRE(n_bins <= kPmBins, "nerf_hash_encode_bwd_ws_store_tables: %u bins (this form holds all histograms in LDS: max %u)", n_bins, kPmBins);
+  NERF_REQUIRE(workspace_bytes >= bin_workspace_bytes(n, c.plan.count), "nerf_hash_encode_bwd_ws_store_tables: workspace of %zu bytes, need %zu",
+               workspace_bytes, bin_workspace_bytes(n, c.plan.count));
+  // this caller's 32-bit guard: the RECORDS of a counted call (the single-table caller bounds the whole capacity)
+  NERF_REQUIRE((size_t)n * 8 * (size_t)c.plan.count < 0xffffffffull, "nerf_hash_encode_bwd_ws_store_tables: n=%lld too large for 32-bit record offsets",
+               (long long)n);
+  c.carve_levels = c.plan.count; c.w = carve(workspace, n, c.plan.count);
+  det_stage(c, n, lv);
+  // speculative: capacities from the true counts the previous call on this workspace left in est[]; the chain's backward has max-accumulated the
+  // largest |gradient| into the header (nerf_hash_encode_bwd_ws_slots) and hands d_feat over row-major, or (NULL) has written the level-major copy
+  NERF_REQUIRE(!spec || (!c.any_direct && !options().deterministic), "nerf_hash_encode_bwd_ws_store_tables_spec: levels of at most %u slices, not with "
+               "option \"deterministic\"", kStagedBins);
+  c.form = spec ? BinForm::kSpeculative : BinForm::kCounted;
+  c.count = spec ? BinCountPass::kNone : BinCountPass::kPointMajor;
+  c.overwrite = true; c.write_est = true; c.staged_base_always = false;
+  c.d_feat = d_feat; c.grad_lm = spec && d_feat != nullptr ? nullptr : c.w.grad_lm;
+  c.table_entries = (unsigned)((uint64_t)(n_tables - 1) * (uint64_t)table_stride + entries);
+  c.status_host = static_cast<unsigned*>(status_host); c.name = "nerf_hash_encode_bwd_ws_store_tables";
+  if (int rc = run_binned(c, pts, n, d_table, as_stream(stream)); rc != NERF_OK) return rc;
+  return check_launch("nerf_hash_encode_bwd_ws_store_tables");
+}
+
+extern "C" int nerf_hash_encode_bwd_ws_store_tables(const float* pts, int64_t n, int n_tables, int64_t table_stride, int n_levels,
+                                                    const float* scale_host, const unsigned* res_host, const unsigned* size_host,
+                                                    const unsigned* offset_host, const unsigned* dense_host, float bound,
+                                                    const float* d_feat, int64_t dfeat_stride, float* d_table, void* workspace,
+                                                    size_t workspace_bytes, nerf_stream_t stream) {
+  return hash_bwd_tables_impl(pts, n, n_tables, table_stride, LEVEL_ARGS, d_feat, dfeat_stride, d_table, workspace, workspace_bytes, stream, false,
+                              nullptr);
+}
+
+// ... its speculative form (see nerf_hash_encode_bwd_ws_store_spec): no count pass, capacities from the previous call's true counts
+// on this workspace; d_feat row-major, its largest magnitude max-accumulated into the slot nerf_hash_encode_bwd_ws_slots(workspace, n,
+// n_levels * n_tables, ...) names by the producer (nerf_p4_deform_bwd)
+extern "C" int nerf_hash_encode_bwd_ws_store_tables_spec(const float* pts, int64_t n, int n_tables, int64_t table_stride, int n_levels,
+                                                         const float* scale_host, const unsigned* res_host, const unsigned* size_host,
+                                                         const unsigned* offset_host, const unsigned* dense_host, float bound,
+                                                         const float* d_feat, int64_t dfeat_stride, float* d_table, void* workspace,
+                                                         size_t workspace_bytes, void* status_host, nerf_stream_t stream) {
+  NERF_REQUIRE(n > 0, "nerf_hash_encode_bwd_ws_store_tables_spec: n=%lld", (long long)n);
+  return hash_bwd_tables_impl(pts, n, n_tables, table_stride, LEVEL_ARGS, d_feat, dfeat_stride, d_table, workspace, workspace_bytes, stream, true,
+                              status_host);
+}
+
+static int hash_bwd_input_impl(const float* pts, int64_t n, const float* table, const void* table_f16, const LevelArgs& lv,
                                const float* d_feat, float* d_pts, nerf_stream_t stream, int accumulate = 0,
                                const float2* grad_lm = nullptr) {
   NERF_REQUIRE(n >= 0, "nerf_hash_encode_bwd_input: n=%lld", (long long)n);
   if (n == 0) return NERF_OK;
-  NERF_REQUIRE(pts && (table || table_f16) && (d_feat || grad_lm) && d_pts && scale_host && res_host && size_host && offset_host && dense_host,
-               "nerf_hash_encode_bwd_input: NULL pointer");
+  NERF_REQUIRE(pts && (table || table_f16) && (d_feat || grad_lm) && d_pts && lv.scale && lv.res && lv.size && lv.offset && lv.dense, "nerf_hash_encode_bwd_input: NULL pointer");
   HashLevels L;
-  int rc = fill_levels(L, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound);
-  if (rc != NERF_OK) return rc;
+  if (int rc = fill_levels(L, lv); rc != NERF_OK) return rc;
   int64_t blocks = (n + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   NERF_REQUIRE(!(options().deterministic && grad_lm != nullptr), "nerf_hash_encode_bwd_input_lm: not with option \"deterministic\"");
@@ -1565,7 +1563,7 @@ static int hash_bwd_input_impl(const float* pts, int64_t n, const float* table, 
   if (!accumulate && hipMemsetAsync(d_pts, 0, sizeof(float) * 3 * (size_t)n, as_stream(stream)) != hipSuccess)
     return fail(NERF_ELAUNCH, "nerf_hash_encode_bwd_input: memset failed");
   const bool xcd = options().hash_xcd != 0;
-  const dim3 grid = level_chunk_grid(n_levels, blocks, xcd);
+  const dim3 grid = level_chunk_grid(lv.n_levels, blocks, xcd);
   if (table_f16 != nullptr)
     hipLaunchKernelGGL(hash_bwd_input_kernel<half2_t>, grid, dim3(256), 0, as_stream(stream), pts, n,
                        static_cast<const half2_t*>(table_f16), L, d_feat, d_pts, xcd ? (int)blocks : 0, grad_lm);
@@ -1579,8 +1577,7 @@ extern "C" int nerf_hash_encode_bwd_input(const float* pts, int64_t n, const flo
                                           const float* scale_host, const unsigned* res_host, const unsigned* size_host,
                                           const unsigned* offset_host, const unsigned* dense_host, float bound,
                                           const float* d_feat, float* d_pts, nerf_stream_t stream) {
-  return hash_bwd_input_impl(pts, n, table, nullptr, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound, d_feat,
-                             d_pts, stream);
+  return hash_bwd_input_impl(pts, n, table, nullptr, LEVEL_ARGS, d_feat, d_pts, stream);
 }
 
 // the same, ADDED to d_pts (a gradient that reaches the positions by another path as well -- Part 4: the displacement regulariser's --
@@ -1589,8 +1586,7 @@ extern "C" int nerf_hash_encode_bwd_input_f16_accum(const float* pts, int64_t n,
                                                     const float* scale_host, const unsigned* res_host, const unsigned* size_host,
                                                     const unsigned* offset_host, const unsigned* dense_host, float bound,
                                                     const float* d_feat, float* d_pts, nerf_stream_t stream) {
-  return hash_bwd_input_impl(pts, n, nullptr, table_f16, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound,
-                             d_feat, d_pts, stream, 1);
+  return hash_bwd_input_impl(pts, n, nullptr, table_f16, LEVEL_ARGS, d_feat, d_pts, stream, 1);
 }
 
 // ... from LEVEL-MAJOR feature gradients [n_levels][n] float2 (what a producer writes into the hash backward's workspace for the
@@ -1600,14 +1596,12 @@ extern "C" int nerf_hash_encode_bwd_input_lm_f16(const float* pts, int64_t n, co
                                                  const unsigned* offset_host, const unsigned* dense_host, float bound,
                                                  const void* grad_lm, float* d_pts, int accumulate, nerf_stream_t stream) {
   NERF_REQUIRE(n == 0 || grad_lm != nullptr, "nerf_hash_encode_bwd_input_lm_f16: grad_lm is NULL");
-  return hash_bwd_input_impl(pts, n, nullptr, table_f16, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound,
-                             nullptr, d_pts, stream, accumulate, static_cast<const float2*>(grad_lm));
+  return hash_bwd_input_impl(pts, n, nullptr, table_f16, LEVEL_ARGS, nullptr, d_pts, stream, accumulate, static_cast<const float2*>(grad_lm));
 }
 
 extern "C" int nerf_hash_encode_bwd_input_f16(const float* pts, int64_t n, const void* table_f16, int n_levels,
                                               const float* scale_host, const unsigned* res_host, const unsigned* size_host,
                                               const unsigned* offset_host, const unsigned* dense_host, float bound,
                                               const float* d_feat, float* d_pts, nerf_stream_t stream) {
-  return hash_bwd_input_impl(pts, n, nullptr, table_f16, n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound,
-                             d_feat, d_pts, stream);
+  return hash_bwd_input_impl(pts, n, nullptr, table_f16, LEVEL_ARGS, d_feat, d_pts, stream);
 }

@@ -292,24 +292,98 @@ def test_table_gradient_forms(ops, name, form):
                 ops.set_deterministic(False)
 
 
+def three_tables(c, which):
+    """(pts, d_feats fp32 [3, n, 2L], their largest magnitude, [(grad, count, abs_sum)] per table) of a named batch, built once:
+    one header, one scale for the whole launch"""
+    key = ("three_tables", which)
+    if key not in c:
+        pts_h, d_feat_h, ref = batch_of(c, which)
+        n = pts_h.shape[0]
+        rng = np.random.default_rng(21)
+        d_feats_h = np.stack([d_feat_h, -0.5 * d_feat_h[::-1], d_feat_h * rng.standard_normal((n, 1)).astype(np.float32)]).astype(np.float32)
+        c[key] = (pts_h, d_feats_h, float(np.abs(d_feats_h).max()), [ref.table_gradient(d_feats_h[k].astype(np.float64)) for k in range(3)])
+    return c[key]
+
+
+def tables_workspace(lib, n, L, k):
+    return torch.empty(max(lib.nerf_hash_encode_bwd_tables_workspace_bytes(n, L, k), 256), dtype=torch.uint8, device="cuda")
+
+
+def check_three_tables(tag, flat, refs, amax, n):
+    for k, (grad, count, abs_sum) in enumerate(refs):
+        check(f"{tag} table {k}", flat[k], grad, H.scatter_fixed_bound(count, abs_sum, amax, n))
+
+
 @pytest.mark.parametrize("name", TABLES)
 def test_table_gradient_of_three_tables_in_one_pass(ops, name):
     c = case_of(ops, name)
     lib = ops._lib.load()
     t, L, E, b = c["t"], c["L"], c["t"].entries, c["bound"]
     for which in BATCHES:
-        pts_h, d_feat_h, ref = batch_of(c, which)
+        pts_h, d_feats_h, amax, refs = three_tables(c, which)
         n = pts_h.shape[0]
-        rng = np.random.default_rng(21)
-        d_feats_h = np.stack([d_feat_h, -0.5 * d_feat_h[::-1], d_feat_h * rng.standard_normal((n, 1)).astype(np.float32)]).astype(np.float32)
-        amax = float(np.abs(d_feats_h).max())                                                  # one header, one scale for the whole launch
         flat = torch.full((3, E, 2), SENTINEL, device="cuda")
         d_feats = gpu(d_feats_h)
-        ws_of = lambda n_, L_, k_: torch.empty(max(lib.nerf_hash_encode_bwd_tables_workspace_bytes(n_, L_, k_), 256), dtype=torch.uint8, device="cuda")
+        ws_of = lambda n_, L_, k_: tables_workspace(lib, n_, L_, k_)
         assert ops.hash_encode_bwd_tables(gpu(pts_h), t, b, [d_feats[k] for k in range(3)], [flat[k] for k in range(3)], ws_of)
-        for k in range(3):
-            grad, count, abs_sum = ref.table_gradient(d_feats_h[k].astype(np.float64))
-            check(f"table gradient ws_store_tables {name} {which} table {k}", flat[k], grad, H.scatter_fixed_bound(count, abs_sum, amax, n))
+        check_three_tables(f"table gradient ws_store_tables {name} {which}", flat, refs, amax, n)
+
+
+@pytest.mark.parametrize("level_major", [False, True], ids=["row_major", "level_major"])
+@pytest.mark.parametrize("name", TABLES)
+def test_table_gradient_of_three_tables_speculative(ops, name, level_major):
+    """nerf_hash_encode_bwd_ws_store_tables_spec after a counted call on the same workspace, then after itself; the gradients
+    row-major, or (d_feat NULL) as the level-major copy a producer leaves in the workspace: float2 [table * L + level][n], the
+    row hash_bin_scatter_kernel reads as grad_lm[blockIdx.y * n + p] and nerf_p4_deform_bwd writes"""
+    c = case_of(ops, name)
+    lib = ops._lib.load()
+    t, L, E, b = c["t"], c["L"], c["t"].entries, c["bound"]
+    for which in BATCHES:
+        pts_h, d_feats_h, amax, refs = three_tables(c, which)
+        n = pts_h.shape[0]
+        pts, d_feats = gpu(pts_h), gpu(d_feats_h)
+        ws = tables_workspace(lib, n, L, 3)
+        ws_of = lambda n_, L_, k_: ws
+        tmp = torch.empty(3, E, 2, device="cuda")
+        assert ops.hash_encode_bwd_tables(pts, t, b, [d_feats[k] for k in range(3)], [tmp[k] for k in range(3)], ws_of)      # counted: leaves the true counts
+        off = lib.nerf_hash_encode_bwd_spec_status(ws.data_ptr()) - ws.data_ptr()
+        for round_, begin in (("after a counted call", True), ("after a speculative call", False)):
+            tag = f"table gradient ws_store_tables_spec {'level-major' if level_major else 'row-major'} {name} {which} {round_}"
+            if begin:
+                ops._lib.check(lib.nerf_hash_encode_bwd_spec_begin(ws.data_ptr(), torch.cuda.current_stream().cuda_stream), "spec_begin")
+            producer_slots(ops, lib, ws, n, 3 * L, torch.cat([d_feats[k] for k in range(3)], dim=1))
+            host = torch.full((8,), -1, dtype=torch.int32).pin_memory()
+            flat = torch.full((3, E, 2), SENTINEL, device="cuda")
+            assert ops.hash_encode_bwd_tables(pts, t, b, [d_feats[k] for k in range(3)], [flat[k] for k in range(3)], ws_of, spec_status=host,
+                                              spec_lm=level_major)
+            status = ws[off:off + 32].view(torch.int32).cpu().tolist()
+            assert host.tolist() == status
+            assert status[3] == 0, f"{tag}: {status[3]} records overflowed bins sized from the same batch"
+            assert status[4] == 0, f"{tag}: records lost ({status[4]})"
+            check_three_tables(tag, flat, refs, amax, n)
+
+
+@pytest.mark.parametrize("name", TABLES)
+def test_table_gradient_of_three_tables_deterministic(ops, name):
+    c = case_of(ops, name)
+    lib = ops._lib.load()
+    t, L, E, b = c["t"], c["L"], c["t"].entries, c["bound"]
+    ops.set_deterministic(True)
+    try:
+        for which in BATCHES:
+            pts_h, d_feats_h, amax, refs = three_tables(c, which)
+            n = pts_h.shape[0]
+            pts, d_feats = gpu(pts_h), gpu(d_feats_h)
+            ws = tables_workspace(lib, n, L, 3)
+            runs = []
+            for _ in range(2):
+                flat = torch.full((3, E, 2), SENTINEL, device="cuda")
+                assert ops.hash_encode_bwd_tables(pts, t, b, [d_feats[k] for k in range(3)], [flat[k] for k in range(3)], lambda n_, L_, k_: ws)
+                runs.append(flat)
+            assert torch.equal(runs[0].view(torch.int32), runs[1].view(torch.int32))
+            check_three_tables(f"table gradient ws_store_tables deterministic {name} {which}", runs[0], refs, amax, n)
+    finally:
+        ops.set_deterministic(False)
 
 
 # ------------------------------------------------------------------------------------------------ input gradient
