@@ -191,7 +191,7 @@ int nerf_sample_compact_ordered(const float* rays_o, const float* rays_d, const 
  * No reference counterpart (the reference has one stratified pass only); follows Mildenhall et al.
  * 2020 sec. 5.2 as restated in oracle/nerf_oracle.py::sample_pdf (parity unpinned).
  *   z_coarse [R,S] sorted depths, weights [R,S] compositing weights of the coarse pass,
- *   u [R,n_fine] uniform draws or NULL (deterministic linspace(0,1,n_fine));
+ *   u [R,n_fine] uniform draws or NULL (deterministic linspace(0,1,n_fine), which is [0] for n_fine == 1);
  *   z_out [R, S + n_fine]: coarse and fine depths merged and sorted. */
 int nerf_sample_pdf(const float* z_coarse, const float* weights, const float* u, int64_t n_rays,
                     int n_coarse, int n_fine, float* z_out, nerf_stream_t stream);
@@ -662,7 +662,9 @@ int nerf_p4_pack(const float* params_f32, void* packed, nerf_stream_t stream);
  * coord_noise_std / time_noise_std > 0 (training, use_coord_noise) Gaussian noise from the counter-based generator keyed by
  * (seed, counter) and the sample's index in the global batch (first_ray * n_samples + g), t' clamped to [0,1].
  * n_samples > 0: slot_of_sample [n_rays * n_samples] maps samples to compact rows (-1 = skipped), ray_times [n_rays];
- * n_samples == 0: point mode, n_rays points with ray_times per point.  x_deform may be NULL (no coordinate noise). */
+ * n_samples == 0: point mode, n_rays points with ray_times per point.  x_deform may be NULL (no coordinate noise).
+ * A sample owns four draws (indices 4 g .. 4 g + 3 of the counter's stream, g its global index) and a counter's stream holds
+ * 2^40: counter < 2^24 and (first_ray + n_rays) * max(n_samples, 1) < 2^38, anything beyond is refused (NERF_EINVAL). */
 int nerf_p4_sample_inputs(const int* slot_of_sample, const float* pts_compact, const float* ray_times, int64_t n_rays,
                           int n_samples, float coord_noise_std, float time_noise_std, uint64_t seed, uint64_t counter,
                           int64_t first_ray, float* x_deform, float* t_deform, nerf_stream_t stream);

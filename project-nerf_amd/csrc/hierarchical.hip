@@ -58,7 +58,7 @@ sample_pdf_kernel(const float* __restrict__ z, const float* __restrict__ weights
     for (int j = lane; j < NF; j += 64) {
       float uj;
       if (u != nullptr) uj = u[r * NF + j];
-      else uj = j < NF / 2 ? ustep * (float)j : __builtin_fmaf(-ustep, (float)(NF - 1 - j), 1.0f);   // torch.linspace(0,1,NF)
+      else uj = (j < NF / 2 || NF == 1) ? ustep * (float)j : __builtin_fmaf(-ustep, (float)(NF - 1 - j), 1.0f);   // torch.linspace(0,1,NF); [0] for NF = 1
       int lo = 0, hi = nb;                              // searchsorted(cdf, u, right=True)
       while (lo < hi) {
         const int mid = (lo + hi) >> 1;

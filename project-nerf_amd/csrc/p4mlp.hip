@@ -743,6 +743,11 @@ extern "C" int nerf_p4_sample_inputs(const int* slot_of_sample, const float* pts
                                      int n_samples, float coord_noise_std, float time_noise_std, uint64_t seed, uint64_t counter,
                                      int64_t first_ray, float* x_deform, float* t_deform, nerf_stream_t stream) {
   NERF_REQUIRE(n_rays >= 0 && n_samples >= 0 && first_ray >= 0 && counter < ((uint64_t)1 << 24), "nerf_p4_sample_inputs: bad sizes");
+  // four draws per sample (indices 4 g .. 4 g + 3 of the counter's stream), each below 2^40 where the next counter's stream begins
+  constexpr int64_t kSampleLimit = (int64_t)1 << 38;
+  NERF_REQUIRE(first_ray < kSampleLimit && n_rays < kSampleLimit &&
+                   first_ray + n_rays <= (kSampleLimit - 1) / (int64_t)(n_samples > 0 ? n_samples : 1),
+               "nerf_p4_sample_inputs: (first_ray + n_rays) * max(n_samples, 1) must stay below 2^38");
   const int64_t total = n_samples > 0 ? n_rays * n_samples : n_rays;
   if (total == 0) return NERF_OK;
   NERF_REQUIRE(pts_compact && ray_times && t_deform, "nerf_p4_sample_inputs: NULL pointer");
