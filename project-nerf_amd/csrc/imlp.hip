@@ -302,13 +302,6 @@ static IArgs iargs(const void* packed, void* ws, const float* dirs, int64_t n, f
   return a;
 }
 
-static int grid_for_tiles(int64_t tiles) {
-  int n_cu = 0;
-  if (device_cu_count(&n_cu) != NERF_OK) return -1;
-  const int64_t cap = (int64_t)n_cu * 4;
-  return (int)(tiles < cap ? tiles : cap);
-}
-
 }  // namespace nerf
 
 using namespace nerf;
@@ -329,7 +322,7 @@ extern "C" int nerf_imlp_fwd(const void* packed, void* workspace, const float* d
   if (n == 0) return NERF_OK;
   NERF_REQUIRE(packed && workspace && dirs && rgb && sigma && ((uintptr_t)workspace & 255) == 0, "nerf_imlp_fwd: bad pointer");
   const IArgs a = iargs(packed, workspace, dirs, n, rgb, sigma);
-  const int grid = grid_for_tiles(a.n_pad / kITile);
+  const int grid = grid_for(a.n_pad / kITile, 4);
   if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_imlp_fwd: cannot query device");
   if (train) hipLaunchKernelGGL(imlp_fwd_kernel<true>, dim3(grid), dim3(kIThreads), kIFwdFrags * 1024, as_stream(stream), a);
   else hipLaunchKernelGGL(imlp_fwd_kernel<false>, dim3(grid), dim3(kIThreads), kIFwdFrags * 1024, as_stream(stream), a);
@@ -344,7 +337,7 @@ extern "C" int nerf_imlp_fwd_encoded(const void* packed, void* workspace, const 
   IArgs a = iargs(packed, workspace, nullptr, n, rgb, sigma);
   a.x_enc = x_enc; a.d_enc = d_enc;
   a.hash_nat_out = const_cast<__bf16*>(a.hash_nat);
-  const int grid = grid_for_tiles(a.n_pad / kITile);
+  const int grid = grid_for(a.n_pad / kITile, 4);
   if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_imlp_fwd_encoded: cannot query device");
   if (train) hipLaunchKernelGGL(imlp_fwd_kernel<true>, dim3(grid), dim3(kIThreads), kIFwdFrags * 1024, as_stream(stream), a);
   else hipLaunchKernelGGL(imlp_fwd_kernel<false>, dim3(grid), dim3(kIThreads), kIFwdFrags * 1024, as_stream(stream), a);
@@ -392,7 +385,7 @@ static int imlp_bwd_impl(const void* packed, void* workspace, const float* rgb, 
   IArgs a = iargs(packed, workspace, nullptr, n, const_cast<float*>(rgb), const_cast<float*>(sigma));
   a.d_rgb = d_rgb; a.d_sigma = d_sigma; a.d_feat = d_feat; a.grad_lm = grad_lm; a.amax_bits = amax_bits;
   a.zero_grads = grads_f32;            // the dgrad kernel clears the vector the wgrad launch behind it adds to
-  const int grid = grid_for_tiles(a.n_pad / kITile);
+  const int grid = grid_for(a.n_pad / kITile, 4);
   if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_imlp_bwd: cannot query device");
   hipLaunchKernelGGL(imlp_bwd_kernel, dim3(grid), dim3(kIThreads), kIBwdFrags * 1024, as_stream(stream), a);
   int rc = check_launch("nerf_imlp_bwd (dgrad)");

@@ -7,7 +7,7 @@
 // as a blocked bf16 image: those are the A operands of the weight-gradient kernel
 // (mlp_wgrad.hip).  Input gradients of the Fourier codes are never formed (positions are
 // not trainable), so pts_layers.0^T and the code columns of layers 4 / view are skipped.
-#include "mlp_chain.h"
+#include "mlp_chain_body.h"
 #include "mlp_stash.h"
 
 namespace nerf {
@@ -29,15 +29,6 @@ struct BwdArgs {
   const float* amax_src;  // where the dgrad kernel reads it: == amax (bwd_amax_kernel ran) or the caller's value
 };
 
-// output-layer derivatives of one sample: sigmoid' and relu' applied to the upstream gradients
-__device__ __forceinline__ void out_derivs(const BwdArgs& a, int64_t n, float& g0, float& g1, float& g2, float& gs) {
-  const float r0 = a.rgb[n * 3 + 0], r1 = a.rgb[n * 3 + 1], r2 = a.rgb[n * 3 + 2];
-  g0 = a.d_rgb[n * 3 + 0] * r0 * (1.0f - r0);
-  g1 = a.d_rgb[n * 3 + 1] * r1 * (1.0f - r1);
-  g2 = a.d_rgb[n * 3 + 2] * r2 * (1.0f - r2);
-  gs = a.sigma[n] > 0.0f ? a.d_sigma[n] : 0.0f;
-}
-
 // amax of the dgrad chain's inputs: the e5m2 gradient images are divided by a power of two derived
 // from it (mlp_stash.h::grad_image_scale).  Non-negative floats order like their bit patterns.
 __global__ void __launch_bounds__(256) bwd_amax_kernel(const BwdArgs a) {
@@ -58,96 +49,13 @@ __global__ void __launch_bounds__(256) bwd_amax_kernel(const BwdArgs a) {
   }
 }
 
+// The compiler-scheduled dgrad: mlp_chain_body.h::chain_dgrad on the vanilla packed buffer.
 __global__ void __launch_bounds__(kChainThreads, 2) mlp_bwd_kernel(const BwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int col = lane & 31, half = lane >> 5;
-
-  WeightRing<true> ring;
-  ring.init(a.packed + kPackBwdOff, smem + kBiasLdsBytes, wave, lane);
-  ring.prologue();
-  const char* a_base = nullptr;
-
-  const int64_t n_tiles = a.n_pad / kTileSamples;
-  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const bool more = tile + gridDim.x < n_tiles;
-    const int64_t wave_tile = tile * 8 + wave;
-    const int64_t n = wave_tile * kWaveSamples + col;
-    const bool live = n < a.n;
-
-    // ---- output-layer derivatives: sigmoid' and relu' ----
-    float g0 = 0.f, g1 = 0.f, g2 = 0.f, gs = 0.f;
-    if (live) out_derivs(a, n, g0, g1, g2, gs);
-    bf16x8 small;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) small[j] = (__bf16)0.0f;
-    if (half == 0) {
-      small[0] = (__bf16)g0; small[1] = (__bf16)g1; small[2] = (__bf16)g2; small[3] = (__bf16)gs;
-    }
-    stash_nat(a.dsmall, wave_tile, 1, 0, col, half, small);
-
-    uint4 mask;
-    auto load_mask = [&](int layer) { mask = a.st_mask[(tile * 9 + layer) * kChainThreads + tid]; };
-    // epilogue: optional relu mask (bits of the layer whose output this gradient belongs to),
-    // bf16 operand for the next step, blocked stash for wgrad
-    auto grad_epi = [&](bf16x8* out, __bf16* stash, int width, bool masked) {
-      return [=, &mask](auto mc, f32x16 acc) {
-        constexpr int m = decltype(mc)::value;
-        if (masked) {
-          const uint32_t words[4] = {mask.x, mask.y, mask.z, mask.w};
-          const uint32_t bits = words[m >> 1] >> (16 * (m & 1));
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[r] = (bits >> r) & 1u ? acc[r] : 0.0f;
-        }
-        acc_to_operand(acc, out[2 * m], out[2 * m + 1]);
-        stash_block(stash, wave_tile, width / 32, m, col, half, out[2 * m], out[2 * m + 1]);
-      };
-    };
-
-    bf16x8 gA[16], gB[16];
-    // ---- rgb_layer^T: d(hv_pre) = relu'(hv) * W_rgb^T d(rgb_pre) ----
-    {
-      bf16x8 in[1];
-      in[0] = small;
-      if (half == 0) in[0][3] = (__bf16)0.0f;   // column 3 carries d(sigma_pre), not an rgb row
-      load_mask(8);
-      run_step<true, B_RGB, 1, true>(ring, a_base, more, in, nullptr, half, grad_epi(gA, a.dhv, 128, true));
-    }
-    // ---- view_layer^T (feature columns only): d(feat) ----
-    {
-      bf16x8 in[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) in[i] = gA[i];
-      run_step<true, B_VIEW, 8, true>(ring, a_base, more, in, nullptr, half, grad_epi(gB, a.dfeat, 256, false));
-    }
-    // ---- (feature_layer | sigma_layer)^T: d(h7_pre) ----
-    {
-      bf16x8 in[17];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) in[i] = gB[i];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) in[16][j] = (__bf16)0.0f;
-      if (half == 0) in[16][0] = (__bf16)gs;
-      load_mask(7);
-      run_step<true, B_HEAD, 17, true>(ring, a_base, more, in, nullptr, half, grad_epi(gA, a.dh + 7 * a.n_pad * 256, 256, true));
-    }
-    // ---- pts_layers.7 .. 1 transposed: d(h_{l-1}_pre) ----
-    load_mask(6);
-    run_step<true, B_PTS7, 16, true>(ring, a_base, more, gA, nullptr, half, grad_epi(gB, a.dh + 6 * a.n_pad * 256, 256, true));
-    load_mask(5);
-    run_step<true, B_PTS6, 16, true>(ring, a_base, more, gB, nullptr, half, grad_epi(gA, a.dh + 5 * a.n_pad * 256, 256, true));
-    load_mask(4);
-    run_step<true, B_PTS5, 16, true>(ring, a_base, more, gA, nullptr, half, grad_epi(gB, a.dh + 4 * a.n_pad * 256, 256, true));
-    load_mask(3);
-    run_step<true, B_PTS4, 16, true>(ring, a_base, more, gB, nullptr, half, grad_epi(gA, a.dh + 3 * a.n_pad * 256, 256, true));
-    load_mask(2);
-    run_step<true, B_PTS3, 16, true>(ring, a_base, more, gA, nullptr, half, grad_epi(gB, a.dh + 2 * a.n_pad * 256, 256, true));
-    load_mask(1);
-    run_step<true, B_PTS2, 16, true>(ring, a_base, more, gB, nullptr, half, grad_epi(gA, a.dh + 1 * a.n_pad * 256, 256, true));
-    load_mask(0);
-    run_step<true, B_PTS1, 16, true>(ring, a_base, more, gA, nullptr, half, grad_epi(gB, a.dh + 0 * a.n_pad * 256, 256, true));
-  }
+  chain_dgrad<kPackBwdOff>(a, smem, tid, lane, wave, col, half);
 }
 
 }  // namespace nerf
@@ -170,7 +78,7 @@ __global__ void __launch_bounds__(kChainThreads, 2) mlp_bwd_stream_kernel(const 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int col = lane & 31, half = lane >> 5;
 
-  WeightRing<true> ring;
+  BwdChain::Ring ring;
   ring.init(a.packed + kPackBwdOff, smem + kBiasLdsBytes, wave, lane);
   ring.template issue<0>(0);
   ring.template issue<1>(1);

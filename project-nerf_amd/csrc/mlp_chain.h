@@ -1,7 +1,11 @@
 // Building blocks of the decoder chain kernels (forward and dgrad): LDS weight ring fed by
 // global_load_lds_dwordx4, the per-m-tile MFMA loop, accumulator -> bf16 operand conversion,
-// and the in-register Fourier codes.  See mlp_plan.h for the data layout.
+// and the in-register Fourier codes.  See mlp_plan.h for the data layout.  The ring, the vmcnt
+// accounting and the step runner are generic over a `Chain` (chunk table, step table, m-tile
+// flavour): the vanilla forward and transposed chains and the Part 3 canonical forward chain
+// (p3canon_plan.h) are three instances; mlp_chain_body.h holds the kernel bodies built on them.
 #pragma once
+#include <limits.h>
 #include <type_traits>
 #include <utility>
 #include "common.h"
@@ -36,10 +40,12 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 //   barrier  -> every wave's DMA for chunk C has landed (hipcc drains vmcnt before
 //               __syncthreads) and every wave is done reading the other slot
 //   issue    -> DMA chunk C+1 (or chunk 0 of the next pass) into the other slot
+// One struct for every 8x256 stream: CH is the chunk table it walks (plan::kFwdChunks, plan::kBwdChunks, or the
+// Part 3 canonical decoder's cplan::kFwdChunks).
 // ---------------------------------------------------------------------------
-template <bool BWD>
+template <const plan::Chunks& CH>
 struct WeightRing {
-  static constexpr const plan::Chunks& chunks() { return BWD ? plan::kBwdChunks : plan::kFwdChunks; }
+  static constexpr const plan::Chunks& chunks() { return CH; }
   const char* stream;   // packed fragment stream in global memory
   char* lds;            // ring base
   int slot;             // slot holding the chunk being consumed
@@ -187,13 +193,25 @@ __device__ __forceinline__ void static_for(F&& f) {
   static_for_impl<N>(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
 }
 
+// A compiler-scheduled chain: the chunk table of its stream, the step table behind that table, forward (bias tiles, kinds
+// F_*) or transposed (zero tiles, kinds B_*), and the m-tile it runs: mtile_asm<KS> on an LDS address, or mtile<KS> on a
+// pointer for k-step counts the generated header does not have.
+template <const plan::Chunks& CH, plan::StepFn STEP, bool BWD, bool ASM_TILE>
+struct Chain {
+  using Ring = WeightRing<CH>;
+  static constexpr plan::StepFn kStep = STEP;
+  static constexpr bool kBwd = BWD, kAsmTile = ASM_TILE;
+};
+using FwdChain = Chain<plan::kFwdChunks, plan::step_of, false, true>;
+using BwdChain = Chain<plan::kBwdChunks, plan::step_of, true, true>;
+
 // stash stores (16-byte global stores) the epilogue of m-tile group g issues when training
-template <bool BWD>
+template <class C>
 constexpr int group_stores(int g) {
   int acc = 0;
-  for (int s = 0; s < plan::stream_steps(BWD); ++s) {
-    const int kind = plan::stream_first(BWD) + s;
-    const int mt = plan::step_of(kind).mt;
+  for (int s = 0; s < plan::stream_steps(C::kBwd); ++s) {
+    const int kind = plan::stream_first(C::kBwd) + s;
+    const int mt = C::kStep(kind).mt;
     if (g < acc + mt) {
       const int m = g - acc;
       if (kind == plan::F_RGB) return 0;
@@ -204,38 +222,38 @@ constexpr int group_stores(int g) {
   }
   return 0;
 }
-// stash stores issued while the chunk BEFORE the one opened by group g was consumed
-template <bool BWD>
-constexpr int prev_chunk_stores(int g) {
-  const plan::Chunks& ch = WeightRing<BWD>::chunks();
+// stash stores issued while the chunk BEFORE the one opened by group g was consumed, clamped to the largest vmcnt immediate
+// that is safe to name here (under-counting is safe: see WeightRing::advance; the vanilla tables never reach the clamp)
+constexpr int prev_chunk_stores(const plan::Chunks& ch, int (*stores)(int), int g) {
   const int c = ch.group_chunk[g];
   if (c == 0) return 0;            // wraps across tile passes: drain everything
   int n = 0;
-  for (int i = 0; i < ch.n_groups; ++i) n += ch.group_chunk[i] == c - 1 ? group_stores<BWD>(i) : 0;
-  return n;
+  for (int i = 0; i < ch.n_groups; ++i) n += ch.group_chunk[i] == c - 1 ? stores(i) : 0;
+  return n < 47 ? n : 47;
 }
 
-// Runs one GEMM step; epi(mc, acc) consumes each finished 32-row tile.
+// Runs one GEMM step of chain C; epi(mc, acc) consumes each finished 32-row tile.
 // STASH: the epilogues issue their stash stores (training); false for inference.
-template <bool BWD, int KIND, int KS, bool STASH, class Epi>
-__device__ __forceinline__ void run_step(WeightRing<BWD>& ring, const char*& a_base, bool more_passes,
+template <class C, int KIND, int KS, bool STASH, class Epi>
+__device__ __forceinline__ void run_step(typename C::Ring& ring, const char*& a_base, bool more_passes,
                                          const bf16x8 (&b)[KS], const float* bias_lds, int half, Epi&& epi) {
-  constexpr plan::Step st = plan::step_of(KIND);
+  constexpr plan::Step st = C::kStep(KIND);
   static_assert(KS == st.ks_acc + st.ks_nat, "operand k-steps");
   static_for<st.mt>([&](auto mc) {
     constexpr int m = decltype(mc)::value;
-    constexpr int g = plan::group_of(KIND, m);
-    constexpr const plan::Chunks& ch = WeightRing<BWD>::chunks();
+    constexpr int g = plan::group_of(KIND, m, C::kStep);
+    constexpr const plan::Chunks& ch = C::Ring::chunks();
     if constexpr (ch.group_first[g])
-      a_base = ring.template advance<ch.group_chunk[g], STASH ? prev_chunk_stores<BWD>(g) : 0>(more_passes);
+      a_base = ring.template advance<ch.group_chunk[g], STASH ? prev_chunk_stores(ch, group_stores<C>, g) : 0>(more_passes);
     f32x16 acc;
-    if constexpr (BWD) {
+    if constexpr (C::kBwd) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
     } else {
       acc = bias_tile(bias_lds, plan::bias_off(KIND) + 32 * m, half);
     }
-    acc = mtile_asm<KS>(lds_addr(a_base) + ch.group_off[g] * 1024, b, acc);
+    if constexpr (C::kAsmTile) acc = mtile_asm<KS>(lds_addr(a_base) + ch.group_off[g] * 1024, b, acc);
+    else acc = mtile<KS>(a_base, ch.group_off[g], b, acc);
     epi(mc, acc);
   });
 }
@@ -379,6 +397,16 @@ __device__ __forceinline__ void encoded_operand(const float* __restrict__ row, i
       out[ks][j] = (__bf16)(f < VALID ? row[f] : (f == VALID ? 1.0f : 0.0f));
     }
   }
+}
+
+// ---- host ----
+// workgroups of a chain launch: one per tile up to workgroups_per_cu per CU and `cap`; -1: the device cannot be queried
+static int grid_for(int64_t tiles, int workgroups_per_cu, int cap = INT_MAX) {
+  int n_cu = 0;
+  if (device_cu_count(&n_cu) != NERF_OK) return -1;
+  int64_t most = (int64_t)n_cu * workgroups_per_cu;
+  if (most > cap) most = cap;
+  return (int)(tiles < most ? tiles : most);
 }
 
 }  // namespace nerf

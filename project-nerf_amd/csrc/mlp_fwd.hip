@@ -10,7 +10,7 @@
 #include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include "mlp_chain.h"
+#include "mlp_chain_body.h"
 #include "mlp_stash.h"
 
 namespace nerf {
@@ -66,124 +66,31 @@ __device__ __forceinline__ void sample_operands(const FwdArgs& a, int64_t nc, in
   fourier_operand<2, kDirDim>(vx, vy, vz, half, denc);
 }
 
+// The compiler-scheduled forward: mlp_chain_body.h::chain_forward on the vanilla plan.  The code operand is the four
+// natural k-steps of sample_operands (ray, point or encoded mode); the skip layer reads the same registers again.
+struct VanillaCode {
+  static constexpr int kKs = 4;
+  __device__ __forceinline__ void form(const FwdArgs& a, int64_t nc, int half, bf16x8 (&xenc)[4], bf16x8 (&denc)[2]) {
+    sample_operands(a, nc, half, xenc, denc);
+  }
+  __device__ __forceinline__ void again(int, const bf16x8 (&xenc)[4], bf16x8 (&out)[4]) const {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) out[i] = xenc[i];
+  }
+};
+struct VanillaFwd {
+  using Chain = FwdChain;
+  using Code = VanillaCode;
+  static constexpr size_t kStreamOff = kPackFwdOff, kBiasOff = kPackBiasOff;
+};
+
 template <bool TRAIN>
 __global__ void __launch_bounds__(kChainThreads, 2) mlp_fwd_kernel(const FwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* bias_lds = reinterpret_cast<float*>(smem);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int col = lane & 31, half = lane >> 5;
-
-  const float* bias_g = reinterpret_cast<const float*>(a.packed + kPackBiasOff);
-  for (int i = tid; i < kBiasFloats; i += kChainThreads) bias_lds[i] = bias_g[i];
-
-  WeightRing<false> ring;
-  ring.init(a.packed + kPackFwdOff, smem + kBiasLdsBytes, wave, lane);
-  ring.prologue();
-  const char* a_base = nullptr;
-
-  const int64_t n_tiles = (a.n + kTileSamples - 1) / kTileSamples;
-  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const bool more = tile + gridDim.x < n_tiles;
-    const int64_t n = tile * kTileSamples + wave * kWaveSamples + col;
-    const bool live = n < a.n;
-    const int64_t nc = live ? n : a.n - 1;
-
-    // ---- a2 + a5: sample geometry and Fourier codes straight into MFMA B fragments ----
-    bf16x8 xenc[4], denc[2];
-    sample_operands(a, nc, half, xenc, denc);
-    const int64_t wave_tile = tile * 8 + wave;
-    if constexpr (TRAIN) {
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) stash_nat(a.st_xenc, wave_tile, 4, ks, col, half, xenc[ks]);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) stash_nat(a.st_denc, wave_tile, 2, ks, col, half, denc[ks]);
-    }
-
-    uint32_t mask_words[4];
-    // hidden-layer epilogue: relu, bf16 operand for the next step, optional stash + mask
-    auto hidden = [&](bf16x8* out, __bf16* stash, int width, bool relu) {
-      return [=, &mask_words](auto mc, f32x16 acc) {
-        constexpr int m = decltype(mc)::value;
-        if constexpr (TRAIN) {
-          if (relu) {
-            uint32_t bits = 0;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) bits |= (acc[r] > 0.0f ? 1u : 0u) << r;
-            if constexpr ((m & 1) == 0) mask_words[m >> 1] = bits;
-            else mask_words[m >> 1] |= bits << 16;
-          }
-        }
-        if (relu) acc_to_operand_relu<true>(acc, out[2 * m], out[2 * m + 1]);
-        else acc_to_operand_relu<false>(acc, out[2 * m], out[2 * m + 1]);
-        if constexpr (TRAIN) stash_block(stash, wave_tile, width / 32, m, col, half, out[2 * m], out[2 * m + 1]);
-      };
-    };
-    auto flush_mask = [&](int layer) {
-      if constexpr (TRAIN) {
-        a.st_mask[(tile * 9 + layer) * kChainThreads + tid] =
-            make_uint4(mask_words[0], mask_words[1], mask_words[2], mask_words[3]);
-      }
-    };
-
-    bf16x8 hA[16], hB[16];
-    // ---- a6: pts_layers.0 .. 7 (src/decoders.py:70-74) ----
-    run_step<false, F_PTS0, 4, TRAIN>(ring, a_base, more, xenc, bias_lds, half, hidden(hA, a.st_h + 0 * a.n_pad * 256, 256, true));
-    flush_mask(0);
-    run_step<false, F_PTS1, 16, TRAIN>(ring, a_base, more, hA, bias_lds, half, hidden(hB, a.st_h + 1 * a.n_pad * 256, 256, true));
-    flush_mask(1);
-    run_step<false, F_PTS2, 16, TRAIN>(ring, a_base, more, hB, bias_lds, half, hidden(hA, a.st_h + 2 * a.n_pad * 256, 256, true));
-    flush_mask(2);
-    run_step<false, F_PTS3, 16, TRAIN>(ring, a_base, more, hA, bias_lds, half, hidden(hB, a.st_h + 3 * a.n_pad * 256, 256, true));
-    flush_mask(3);
-    {
-      bf16x8 cat[20];   // skip connection: [h3 | xenc], hidden first (src/decoders.py:73)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) cat[i] = hB[i];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) cat[16 + i] = xenc[i];
-      run_step<false, F_PTS4, 20, TRAIN>(ring, a_base, more, cat, bias_lds, half, hidden(hA, a.st_h + 4 * a.n_pad * 256, 256, true));
-      flush_mask(4);
-    }
-    run_step<false, F_PTS5, 16, TRAIN>(ring, a_base, more, hA, bias_lds, half, hidden(hB, a.st_h + 5 * a.n_pad * 256, 256, true));
-    flush_mask(5);
-    run_step<false, F_PTS6, 16, TRAIN>(ring, a_base, more, hB, bias_lds, half, hidden(hA, a.st_h + 6 * a.n_pad * 256, 256, true));
-    flush_mask(6);
-    run_step<false, F_PTS7, 16, TRAIN>(ring, a_base, more, hA, bias_lds, half, hidden(hB, a.st_h + 7 * a.n_pad * 256, 256, true));
-    flush_mask(7);
-
-    // ---- feature_layer (linear) + sigma_layer (relu) (src/decoders.py:77-80) ----
-    {
-      auto feat_epi = hidden(hA, a.st_feat, 256, false);
-      run_step<false, F_HEAD, 16, TRAIN>(ring, a_base, more, hB, bias_lds, half, [&](auto mc, f32x16 acc) {
-        constexpr int m = decltype(mc)::value;
-        if constexpr (m < 8) feat_epi(mc, acc);
-        else if (live && half == 0) a.sigma[n] = fmaxf(acc[0], 0.0f);
-      });
-    }
-    // ---- view_layer on [feat | denc] (relu), rgb_layer (sigmoid) (src/decoders.py:83-85) ----
-    {
-      bf16x8 cat[18];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) cat[i] = hA[i];
-      cat[16] = denc[0];
-      cat[17] = denc[1];
-      mask_words[0] = mask_words[1] = mask_words[2] = mask_words[3] = 0;
-      run_step<false, F_VIEW, 18, TRAIN>(ring, a_base, more, cat, bias_lds, half, hidden(hB, a.st_hv, 128, true));
-      flush_mask(8);
-    }
-    {
-      bf16x8 hv[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) hv[i] = hB[i];
-      run_step<false, F_RGB, 8, TRAIN>(ring, a_base, more, hv, bias_lds, half, [&](auto, f32x16 acc) {
-        if (live && half == 0) {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) a.rgb[n * 3 + c] = 1.0f / (1.0f + __expf(-acc[c]));
-        }
-      });
-    }
-  }
+  chain_forward<VanillaFwd, TRAIN>(a, smem, tid, lane, wave, col, half);
 }
 
 }  // namespace nerf
@@ -213,7 +120,7 @@ __global__ void __launch_bounds__(kChainThreads, 2) mlp_fwd_stream_kernel(const 
   const float* bias_g = reinterpret_cast<const float*>(a.packed + kPackBiasOff);
   for (int i = tid; i < kBiasFloats; i += kChainThreads) bias_lds[i] = bias_g[i];
 
-  WeightRing<false> ring;
+  FwdChain::Ring ring;
   ring.init(a.packed + kPackFwdOff, smem + kBiasLdsBytes, wave, lane);
   ring.template issue<0>(0);
   ring.template issue<1>(1);
@@ -381,7 +288,7 @@ __global__ void __launch_bounds__(kChainThreads, 2) mlp_fwd_stream16_kernel(cons
   const float* bias_g = reinterpret_cast<const float*>(a.packed + kPackBiasOff);
   for (int i = tid; i < kBiasFloats; i += kChainThreads) bias_lds[i] = bias_g[i];
 
-  WeightRing<false> ring;
+  FwdChain::Ring ring;
   ring.init(a.packed + kPackFwd16Off, smem + kBiasLdsBytes, wave, lane);
   ring.template issue<0>(0);
   ring.template issue<1>(1);

@@ -73,15 +73,17 @@ constexpr Step step_of(int kind) {
     default: return {8, 16, 0};       // plain 256 -> 256 (forward or transposed)
   }
 }
-constexpr int step_ks(int kind) { return step_of(kind).ks_acc + step_of(kind).ks_nat; }
-constexpr int step_frags(int kind) { return step_of(kind).mt * step_ks(kind); }
+// The functions below take the step table they walk: step_of here, p3canon_plan.h's override with two wider steps there.
+using StepFn = Step (*)(int);
+constexpr int step_ks(int kind, StepFn step = step_of) { return step(kind).ks_acc + step(kind).ks_nat; }
+constexpr int step_frags(int kind, StepFn step = step_of) { return step(kind).mt * step_ks(kind, step); }
 
 constexpr int stream_first(bool bwd) { return bwd ? (int)B_RGB : (int)F_PTS0; }
 constexpr int stream_steps(bool bwd) { return bwd ? kBwdSteps : kFwdSteps; }
 
-constexpr int stream_frags(bool bwd) {
+constexpr int stream_frags(bool bwd, StepFn step = step_of) {
   int n = 0;
-  for (int s = 0; s < stream_steps(bwd); ++s) n += step_frags(stream_first(bwd) + s);
+  for (int s = 0; s < stream_steps(bwd); ++s) n += step_frags(stream_first(bwd) + s, step);
   return n;
 }
 constexpr int kFwdFrags = stream_frags(false);   // 1184
@@ -111,13 +113,13 @@ struct Chunks {
   int chunk_count[kMaxChunks];   // fragments in the chunk
 };
 
-constexpr Chunks make_chunks(bool bwd) {
+constexpr Chunks make_chunks(bool bwd, StepFn step = step_of) {
   Chunks c{};
   int g = 0, chunk = -1, fill = kChunkFrags + 1, frag = 0;
   for (int s = 0; s < stream_steps(bwd); ++s) {
     const int kind = stream_first(bwd) + s;
-    const int ks = step_ks(kind);
-    for (int m = 0; m < step_of(kind).mt; ++m, ++g) {
+    const int ks = step_ks(kind, step);
+    for (int m = 0; m < step(kind).mt; ++m, ++g) {
       const bool open = fill + ks > kChunkFrags;
       if (open) {
         ++chunk;
@@ -141,10 +143,10 @@ constexpr Chunks kFwdChunks = make_chunks(false);
 constexpr Chunks kBwdChunks = make_chunks(true);
 
 // global m-tile group index of (kind, m)
-constexpr int group_of(int kind, int m) {
+constexpr int group_of(int kind, int m, StepFn step = step_of) {
   const bool bwd = kind >= B_RGB;
   int g = 0;
-  for (int k = stream_first(bwd); k < kind; ++k) g += step_of(k).mt;
+  for (int k = stream_first(bwd); k < kind; ++k) g += step(k).mt;
   return g + m;
 }
 

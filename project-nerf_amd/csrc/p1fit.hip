@@ -344,7 +344,7 @@ static Layout layout(const Plan& p, int64_t n) {
   return s;
 }
 // H = 256: one layer fills the LDS of a CU
-static int grid_for(const Plan& p, int64_t tiles) { return sample_chain::grid_for(tiles, p.H == 256 ? 1 : 2, kLossParts); }
+static int grid_for(const Plan& p, int64_t tiles) { return nerf::grid_for(tiles, p.H == 256 ? 1 : 2, kLossParts); }
 static int lds_bytes(const Plan& p) { return p.mt * (p.ks > kCodeKs ? p.ks : kCodeKs) * 1024; }
 
 typedef void (*ChainKernel)(Args);

@@ -2,96 +2,26 @@
 // 233-281, src/decoders.py:29-87) for `canonical_type: nerf` (code(x_c) L 10, code(t') L 10: 84 columns) and for
 // `direct_time_conditioning` (code(x) L 10, code(t) L <= 10).  Plan: p3canon_plan.h.
 //
-//   fwd_kernel     the vanilla forward chain (mlp_fwd.hip, compiler-scheduled family) with six natural code k-steps at
-//                  pts_layers.0 and at the skip; the codes are formed in registers from x [n,3] and t [n] (and formed
-//                  again at the skip instead of being held live through layers 0..3).  TRAIN: blocked bf16 images of
-//                  every layer input and the ReLU masks, as the vanilla forward writes them.
-//   dgrad_kernel   the vanilla transposed chain (mlp_bwd.hip) on this layout's dgrad stream: pre-activation gradient images.
+//   fwd_kernel     mlp_chain_body.h::chain_forward, the body of the vanilla compiler-scheduled forward (mlp_fwd.hip), on this
+//                  plan: six natural code k-steps at pts_layers.0 and at the skip; the codes are formed in registers from
+//                  x [n,3] and t [n] (and formed again at the skip instead of being held live through layers 0..3).  TRAIN:
+//                  blocked bf16 images of every layer input and the ReLU masks, as the vanilla forward writes them.
+//   dgrad_kernel   mlp_chain_body.h::chain_dgrad, the body of mlp_bwd.hip::mlp_bwd_kernel, on this layout's dgrad stream:
+//                  pre-activation gradient images.
 //   dcode_kernel   d code(x) = W0[:, :63]^T dz0 + W4[:, 256:319]^T dz4 from the bf16 images of dz0 / dz4, then the Fourier
 //                  chain rule to d x [n,3], ADDED to the caller's vector (x_c = x + delta_x).
 //   weight grads   mlp_wgrad.hip's split-K kernel with this decoder's job table (partial tiles + ordered reduction into a
 //                  gradient image of fixed layout), then remap_kernel into the reference layout.
 #include <stddef.h>
 #include <stdint.h>
-#include "mlp_chain.h"
+#include "mlp_chain_body.h"
 #include "mlp_stash.h"
 #include "mlp_wgrad.h"
 #include "p3canon_plan.h"
 
 namespace nerf {
 namespace p3c {
-using plan::Chunks;
 using plan::Step;
-
-// ---------------------------------------------------------------------------------------------------- forward weight ring
-// mlp_chain.h::WeightRing<false> over this plan's chunk table
-struct CanonRing {
-  static constexpr const Chunks& chunks() { return cplan::kFwdChunks; }
-  const char* stream;
-  char* lds;
-  int slot;
-  int wave, lane;
-
-  __device__ __forceinline__ void init(const char* s, char* l, int w, int ln) {
-    stream = s; lds = l; slot = 1; wave = w; lane = ln;
-  }
-  template <int C>
-  __device__ __forceinline__ void issue(int dst_slot) const {
-    constexpr int frag0 = chunks().chunk_frag0[C];
-    constexpr int count = chunks().chunk_count[C];
-    const char* sbase = stream;
-    asm volatile("" : "+s"(sbase));
-    sbase += (size_t)(frag0 + wave) * 1024;
-    char* dst = lds + dst_slot * kRingSlotBytes + wave * 1024;
-    const uint32_t voff = (uint32_t)lane * 16u;
-#pragma unroll
-    for (int i = 0; i < (count + 7) / 8; ++i)
-      __builtin_amdgcn_global_load_lds((gptr_t)(sbase + i * 8192 + voff), (lptr_t)(dst + i * 8192), 16, 0, 0);
-  }
-  __device__ __forceinline__ void prologue() { issue<0>(0); }
-  template <int C, int STORES>
-  __device__ __forceinline__ const char* advance(bool more_passes) {
-    constexpr int n = chunks().n_chunks;
-    static_assert(STORES >= 0 && STORES < 48, "vmcnt immediate");
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(STORES) : "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    slot ^= 1;
-    if constexpr (C + 1 < n) issue<C + 1>(slot ^ 1);
-    else if (more_passes) issue<0>(slot ^ 1);
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return lds + slot * kRingSlotBytes + lane * 16;
-  }
-};
-
-// stash stores issued while the chunk before the one group g opens was consumed (under-counting is safe: see WeightRing)
-constexpr int prev_chunk_stores(int g) {
-  const Chunks& ch = cplan::kFwdChunks;
-  const int c = ch.group_chunk[g];
-  if (c == 0) return 0;
-  int n = 0;
-  for (int i = 0; i < ch.n_groups; ++i) n += ch.group_chunk[i] == c - 1 ? group_stores<false>(i) : 0;   // same m-tiles per step as vanilla
-  return n < 47 ? n : 47;
-}
-
-template <int KIND, int KS, bool STASH, class Epi>
-__device__ __forceinline__ void fwd_step(CanonRing& ring, const char*& a_base, bool more_passes, const bf16x8 (&b)[KS],
-                                         const float* bias_lds, int half, Epi&& epi) {
-  constexpr Step st = cplan::step_of(KIND);
-  static_assert(KS == st.ks_acc + st.ks_nat, "operand k-steps");
-  static_for<st.mt>([&](auto mc) {
-    constexpr int m = decltype(mc)::value;
-    constexpr int g = cplan::group_of(KIND, m);
-    constexpr const Chunks& ch = cplan::kFwdChunks;
-    if constexpr (ch.group_first[g])
-      a_base = ring.template advance<ch.group_chunk[g], STASH ? prev_chunk_stores(g) : 0>(more_passes);
-    f32x16 acc = bias_tile(bias_lds, plan::bias_off(KIND) + 32 * m, half);
-    acc = mtile<KS>(a_base, ch.group_off[g], b, acc);
-    epi(mc, acc);
-  });
-}
 
 // ---------------------------------------------------------------------------------------------------- codes
 // time code of one scalar, [t | sin(2^0 pi t) | cos(2^0 pi t) | sin(2^1 pi t) | ...] (src/embeddings.py:28-32, input_dim 1),
@@ -194,125 +124,35 @@ struct FwdArgs {
   uint4* st_mask;        // [tiles][9][512]: word (m>>1), bits 16*(m&1) + r (the compiler-scheduled family's masks)
 };
 
+// mlp_chain_body.h::chain_forward on this plan.  The forward chain walks cplan's chunk table and runs mtile<KS> on a pointer
+// (the generated asm m-tiles have no 6 or 22 k-step form).  The code operand keeps x and t, not the six operand registers:
+// the skip layer forms the code again from them: the same arithmetic on the same values (the same bits), 20 VGPRs fewer
+// live through layers 0..3.
+struct CanonCode {
+  static constexpr int kKs = cplan::kCodeKs;
+  float x0, x1, x2, t;
+  __device__ __forceinline__ void form(const FwdArgs& a, int64_t nc, int half, bf16x8 (&code)[kKs], bf16x8 (&denc)[2]) {
+    x0 = a.x[nc * 3 + 0]; x1 = a.x[nc * 3 + 1]; x2 = a.x[nc * 3 + 2]; t = a.t[nc];
+    code_operand(x0, x1, x2, t, half, code);
+    fourier_operand<2, plan::kDirDim>(a.dirs[nc * 3 + 0], a.dirs[nc * 3 + 1], a.dirs[nc * 3 + 2], half, denc);
+  }
+  __device__ __forceinline__ void again(int half, const bf16x8 (&)[kKs], bf16x8 (&out)[kKs]) const {
+    code_operand(x0, x1, x2, t, half, out);
+  }
+};
+struct CanonFwd {
+  using Chain = nerf::Chain<cplan::kFwdChunks, cplan::step_of, false, false>;
+  using Code = CanonCode;
+  static constexpr size_t kStreamOff = cplan::kPackFwdOff, kBiasOff = cplan::kPackBiasOff;
+};
+
 template <bool TRAIN>
 __global__ void __launch_bounds__(kChainThreads, 2) fwd_kernel(const FwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* bias_lds = reinterpret_cast<float*>(smem);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int col = lane & 31, half = lane >> 5;
-
-  const float* bias_g = reinterpret_cast<const float*>(a.packed + cplan::kPackBiasOff);
-  for (int i = tid; i < plan::kBiasFloats; i += kChainThreads) bias_lds[i] = bias_g[i];
-
-  CanonRing ring;
-  ring.init(a.packed + cplan::kPackFwdOff, smem + kBiasLdsBytes, wave, lane);
-  ring.prologue();
-  const char* a_base = nullptr;
-
-  const int64_t n_tiles = (a.n + kTileSamples - 1) / kTileSamples;
-  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const bool more = tile + gridDim.x < n_tiles;
-    const int64_t n = tile * kTileSamples + wave * kWaveSamples + col;
-    const bool live = n < a.n;
-    const int64_t nc = live ? n : a.n - 1;
-    const float px = a.x[nc * 3 + 0], py = a.x[nc * 3 + 1], pz = a.x[nc * 3 + 2], tt = a.t[nc];
-    const int64_t wave_tile = tile * 8 + wave;
-
-    bf16x8 code[cplan::kCodeKs];
-    code_operand(px, py, pz, tt, half, code);
-    bf16x8 denc[2];
-    fourier_operand<2, plan::kDirDim>(a.dirs[nc * 3 + 0], a.dirs[nc * 3 + 1], a.dirs[nc * 3 + 2], half, denc);
-    if constexpr (TRAIN) {
-#pragma unroll
-      for (int ks = 0; ks < cplan::kCodeKs; ++ks) stash_nat(a.st_xenc, wave_tile, cplan::kCodeKs, ks, col, half, code[ks]);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) stash_nat(a.st_denc, wave_tile, 2, ks, col, half, denc[ks]);
-    }
-
-    uint32_t mask_words[4];
-    auto hidden = [&](bf16x8* out, __bf16* stash, int width, bool relu) {
-      return [=, &mask_words](auto mc, f32x16 acc) {
-        constexpr int m = decltype(mc)::value;
-        if constexpr (TRAIN) {
-          if (relu) {
-            uint32_t bits = 0;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) bits |= (acc[r] > 0.0f ? 1u : 0u) << r;
-            if constexpr ((m & 1) == 0) mask_words[m >> 1] = bits;
-            else mask_words[m >> 1] |= bits << 16;
-          }
-        }
-        if (relu) acc_to_operand_relu<true>(acc, out[2 * m], out[2 * m + 1]);
-        else acc_to_operand_relu<false>(acc, out[2 * m], out[2 * m + 1]);
-        if constexpr (TRAIN) stash_block(stash, wave_tile, width / 32, m, col, half, out[2 * m], out[2 * m + 1]);
-      };
-    };
-    auto flush_mask = [&](int layer) {
-      if constexpr (TRAIN)
-        a.st_mask[(tile * 9 + layer) * kChainThreads + tid] = make_uint4(mask_words[0], mask_words[1], mask_words[2], mask_words[3]);
-    };
-
-    bf16x8 hA[16], hB[16];
-    // pts_layers.0 .. 3 on the code (src/decoders.py:70-74)
-    fwd_step<plan::F_PTS0, 6, TRAIN>(ring, a_base, more, code, bias_lds, half, hidden(hA, a.st_h + 0 * a.n_pad * 256, 256, true));
-    flush_mask(0);
-    fwd_step<plan::F_PTS1, 16, TRAIN>(ring, a_base, more, hA, bias_lds, half, hidden(hB, a.st_h + 1 * a.n_pad * 256, 256, true));
-    flush_mask(1);
-    fwd_step<plan::F_PTS2, 16, TRAIN>(ring, a_base, more, hB, bias_lds, half, hidden(hA, a.st_h + 2 * a.n_pad * 256, 256, true));
-    flush_mask(2);
-    fwd_step<plan::F_PTS3, 16, TRAIN>(ring, a_base, more, hA, bias_lds, half, hidden(hB, a.st_h + 3 * a.n_pad * 256, 256, true));
-    flush_mask(3);
-    {
-      // skip connection [h3 | code], hidden first (src/decoders.py:73); the code is formed again from x, t: the same
-      // arithmetic on the same values (the same bits), 20 VGPRs fewer live through layers 0..3
-      bf16x8 cat[22], again[cplan::kCodeKs];
-      code_operand(px, py, pz, tt, half, again);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) cat[i] = hB[i];
-#pragma unroll
-      for (int i = 0; i < cplan::kCodeKs; ++i) cat[16 + i] = again[i];
-      fwd_step<plan::F_PTS4, 22, TRAIN>(ring, a_base, more, cat, bias_lds, half, hidden(hA, a.st_h + 4 * a.n_pad * 256, 256, true));
-      flush_mask(4);
-    }
-    fwd_step<plan::F_PTS5, 16, TRAIN>(ring, a_base, more, hA, bias_lds, half, hidden(hB, a.st_h + 5 * a.n_pad * 256, 256, true));
-    flush_mask(5);
-    fwd_step<plan::F_PTS6, 16, TRAIN>(ring, a_base, more, hB, bias_lds, half, hidden(hA, a.st_h + 6 * a.n_pad * 256, 256, true));
-    flush_mask(6);
-    fwd_step<plan::F_PTS7, 16, TRAIN>(ring, a_base, more, hA, bias_lds, half, hidden(hB, a.st_h + 7 * a.n_pad * 256, 256, true));
-    flush_mask(7);
-    // feature_layer (linear) + sigma_layer (relu) (src/decoders.py:77-80)
-    {
-      auto feat_epi = hidden(hA, a.st_feat, 256, false);
-      fwd_step<plan::F_HEAD, 16, TRAIN>(ring, a_base, more, hB, bias_lds, half, [&](auto mc, f32x16 acc) {
-        constexpr int m = decltype(mc)::value;
-        if constexpr (m < 8) feat_epi(mc, acc);
-        else if (live && half == 0) a.sigma[n] = fmaxf(acc[0], 0.0f);
-      });
-    }
-    // view_layer on [feat | denc] (relu), rgb_layer (sigmoid) (src/decoders.py:83-85)
-    {
-      bf16x8 cat[18];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) cat[i] = hA[i];
-      cat[16] = denc[0];
-      cat[17] = denc[1];
-      mask_words[0] = mask_words[1] = mask_words[2] = mask_words[3] = 0;
-      fwd_step<plan::F_VIEW, 18, TRAIN>(ring, a_base, more, cat, bias_lds, half, hidden(hB, a.st_hv, 128, true));
-      flush_mask(8);
-    }
-    {
-      bf16x8 hv[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) hv[i] = hB[i];
-      fwd_step<plan::F_RGB, 8, TRAIN>(ring, a_base, more, hv, bias_lds, half, [&](auto, f32x16 acc) {
-        if (live && half == 0) {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) a.rgb[n * 3 + c] = 1.0f / (1.0f + __expf(-acc[c]));
-        }
-      });
-    }
-  }
+  chain_forward<CanonFwd, TRAIN>(a, smem, tid, lane, wave, col, half);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last pass's look-ahead DMA must not outlive the wave
 }
 
@@ -331,97 +171,14 @@ struct BwdArgs {
   __bf16* dh;            // 8 x blocked [n_pad,256]: dh[l] = d(pre-activation of pts_layers.l)
 };
 
-// mlp_bwd.hip::mlp_bwd_kernel on this layout's transposed stream (the same steps: the code columns are never contracted)
+// mlp_chain_body.h::chain_dgrad on this layout's transposed stream (the vanilla steps and chunks: the code columns are never
+// contracted)
 __global__ void __launch_bounds__(kChainThreads, 2) dgrad_kernel(const BwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int col = lane & 31, half = lane >> 5;
-
-  WeightRing<true> ring;
-  ring.init(a.packed + cplan::kPackBwdOff, smem + kBiasLdsBytes, wave, lane);
-  ring.prologue();
-  const char* a_base = nullptr;
-
-  const int64_t n_tiles = a.n_pad / kTileSamples;
-  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const bool more = tile + gridDim.x < n_tiles;
-    const int64_t wave_tile = tile * 8 + wave;
-    const int64_t n = wave_tile * kWaveSamples + col;
-    const bool live = n < a.n;
-
-    // output-layer derivatives: sigmoid' and relu'
-    float g0 = 0.f, g1 = 0.f, g2 = 0.f, gs = 0.f;
-    if (live) {
-      const float r0 = a.rgb[n * 3 + 0], r1 = a.rgb[n * 3 + 1], r2 = a.rgb[n * 3 + 2];
-      g0 = a.d_rgb[n * 3 + 0] * r0 * (1.0f - r0);
-      g1 = a.d_rgb[n * 3 + 1] * r1 * (1.0f - r1);
-      g2 = a.d_rgb[n * 3 + 2] * r2 * (1.0f - r2);
-      gs = a.sigma[n] > 0.0f ? a.d_sigma[n] : 0.0f;
-    }
-    bf16x8 small;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) small[j] = (__bf16)0.0f;
-    if (half == 0) {
-      small[0] = (__bf16)g0; small[1] = (__bf16)g1; small[2] = (__bf16)g2; small[3] = (__bf16)gs;
-    }
-    stash_nat(a.dsmall, wave_tile, 1, 0, col, half, small);
-
-    uint4 mask;
-    auto load_mask = [&](int layer) { mask = a.st_mask[(tile * 9 + layer) * kChainThreads + tid]; };
-    auto grad_epi = [&](bf16x8* out, __bf16* stash, int width, bool masked) {
-      return [=, &mask](auto mc, f32x16 acc) {
-        constexpr int m = decltype(mc)::value;
-        if (masked) {
-          const uint32_t words[4] = {mask.x, mask.y, mask.z, mask.w};
-          const uint32_t bits = words[m >> 1] >> (16 * (m & 1));
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[r] = (bits >> r) & 1u ? acc[r] : 0.0f;
-        }
-        acc_to_operand(acc, out[2 * m], out[2 * m + 1]);
-        stash_block(stash, wave_tile, width / 32, m, col, half, out[2 * m], out[2 * m + 1]);
-      };
-    };
-
-    bf16x8 gA[16], gB[16];
-    {
-      bf16x8 in[1];
-      in[0] = small;
-      if (half == 0) in[0][3] = (__bf16)0.0f;   // column 3 carries d(sigma_pre), not an rgb row
-      load_mask(8);
-      run_step<true, plan::B_RGB, 1, true>(ring, a_base, more, in, nullptr, half, grad_epi(gA, a.dhv, 128, true));
-    }
-    {
-      bf16x8 in[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) in[i] = gA[i];
-      run_step<true, plan::B_VIEW, 8, true>(ring, a_base, more, in, nullptr, half, grad_epi(gB, a.dfeat, 256, false));
-    }
-    {
-      bf16x8 in[17];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) in[i] = gB[i];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) in[16][j] = (__bf16)0.0f;
-      if (half == 0) in[16][0] = (__bf16)gs;
-      load_mask(7);
-      run_step<true, plan::B_HEAD, 17, true>(ring, a_base, more, in, nullptr, half, grad_epi(gA, a.dh + 7 * a.n_pad * 256, 256, true));
-    }
-    load_mask(6);
-    run_step<true, plan::B_PTS7, 16, true>(ring, a_base, more, gA, nullptr, half, grad_epi(gB, a.dh + 6 * a.n_pad * 256, 256, true));
-    load_mask(5);
-    run_step<true, plan::B_PTS6, 16, true>(ring, a_base, more, gB, nullptr, half, grad_epi(gA, a.dh + 5 * a.n_pad * 256, 256, true));
-    load_mask(4);
-    run_step<true, plan::B_PTS5, 16, true>(ring, a_base, more, gA, nullptr, half, grad_epi(gB, a.dh + 4 * a.n_pad * 256, 256, true));
-    load_mask(3);
-    run_step<true, plan::B_PTS4, 16, true>(ring, a_base, more, gB, nullptr, half, grad_epi(gA, a.dh + 3 * a.n_pad * 256, 256, true));
-    load_mask(2);
-    run_step<true, plan::B_PTS3, 16, true>(ring, a_base, more, gA, nullptr, half, grad_epi(gB, a.dh + 2 * a.n_pad * 256, 256, true));
-    load_mask(1);
-    run_step<true, plan::B_PTS2, 16, true>(ring, a_base, more, gB, nullptr, half, grad_epi(gA, a.dh + 1 * a.n_pad * 256, 256, true));
-    load_mask(0);
-    run_step<true, plan::B_PTS1, 16, true>(ring, a_base, more, gA, nullptr, half, grad_epi(gB, a.dh + 0 * a.n_pad * 256, 256, true));
-  }
+  chain_dgrad<cplan::kPackBwdOff>(a, smem, tid, lane, wave, col, half);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
@@ -513,7 +270,7 @@ constexpr FragTable make_frag_table() {
   int f = 0;
   for (int kind = plan::F_PTS0; kind <= plan::F_RGB; ++kind)
     for (int m = 0; m < cplan::step_of(kind).mt; ++m)
-      for (int k = 0; k < cplan::step_ks(kind); ++k) t.v[f++] = (kind << 16) | (m << 8) | k;
+      for (int k = 0; k < plan::step_ks(kind, cplan::step_of); ++k) t.v[f++] = (kind << 16) | (m << 8) | k;
   for (int kind = plan::B_RGB; kind <= plan::B_PTS1; ++kind)
     for (int m = 0; m < plan::step_of(kind).mt; ++m)
       for (int k = 0; k < plan::step_ks(kind); ++k) t.v[f++] = (kind << 16) | (m << 8) | k;
@@ -674,12 +431,6 @@ int launch_wgrad(const char* ws, const Layout& wl, int64_t n, hipStream_t stream
   return wgrad_launch(args, n, eg, stream, slab, wl.slab_bytes, 0, (size_t)cplan::eCount);
 }
 
-int grid_for(int64_t tiles) {
-  int n_cu = 0;
-  if (device_cu_count(&n_cu) != NERF_OK) return -1;
-  return (int)(tiles < n_cu ? tiles : n_cu);
-}
-
 }  // namespace p3c
 }  // namespace nerf
 
@@ -717,7 +468,7 @@ extern "C" int nerf_p3_canon_fwd(const void* packed, void* workspace, const floa
     a.st_denc = reinterpret_cast<__bf16*>(w + l.denc);
     a.st_mask = reinterpret_cast<uint4*>(w + l.mask);
   }
-  const int grid = p3c::grid_for(l.n_pad / kTileSamples);
+  const int grid = grid_for(l.n_pad / kTileSamples, 1);
   if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_p3_canon_fwd: cannot query device");
   const void* kernel = train ? (const void*)p3c::fwd_kernel<true> : (const void*)p3c::fwd_kernel<false>;
   if (int rc = ensure_dynamic_lds(kernel, kChainLds, "nerf_p3_canon_fwd"); rc != NERF_OK) return rc;
@@ -751,7 +502,7 @@ extern "C" int nerf_p3_canon_bwd(const void* packed, void* workspace, const floa
   a.dhv = reinterpret_cast<__bf16*>(w + l.dhv);
   a.dfeat = reinterpret_cast<__bf16*>(w + l.dfeat);
   a.dh = reinterpret_cast<__bf16*>(w + l.dh);
-  const int grid = p3c::grid_for(l.n_pad / kTileSamples);
+  const int grid = grid_for(l.n_pad / kTileSamples, 1);
   if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_p3_canon_bwd: cannot query device");
   if (int rc = ensure_dynamic_lds((const void*)p3c::dgrad_kernel, kChainLds, "nerf_p3_canon_bwd"); rc != NERF_OK) return rc;
   hipLaunchKernelGGL(p3c::dgrad_kernel, dim3(grid), dim3(kChainThreads), kChainLds, as_stream(stream), a);

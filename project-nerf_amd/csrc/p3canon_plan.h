@@ -7,6 +7,9 @@
 // constant 1 of the vanilla Fourier operand (bias column of the weight gradient), k >= 64 + time_dim is zero.
 // The dgrad chain never forms the code's gradient inside the chain, so its stream is the vanilla one
 // (plan::kBwdChunks), packed from this layout's offsets.
+// This file holds what the layout changes: the parameter Layout, the e* gradient image, code_k / code_col, the two-entry
+// step_of override and the pack offsets.  Fragment counts, the chunk table and the m-tile group index come from
+// mlp_plan.h's functions, called with this step_of.
 #pragma once
 #include "mlp_plan.h"
 
@@ -72,52 +75,15 @@ constexpr Step step_of(int kind) {
   if (kind == plan::F_PTS4) return {8, 16, kCodeKs};
   return plan::step_of(kind);
 }
-constexpr int step_ks(int kind) { return step_of(kind).ks_acc + step_of(kind).ks_nat; }
-constexpr int step_frags(int kind) { return step_of(kind).mt * step_ks(kind); }
-constexpr int fwd_frags() {
-  int n = 0;
-  for (int k = plan::F_PTS0; k <= plan::F_RGB; ++k) n += step_frags(k);
-  return n;
-}
-constexpr int kFwdFrags = fwd_frags();
+constexpr int kFwdFrags = plan::stream_frags(false, step_of);
 static_assert(kFwdFrags == plan::kFwdFrags + 32, "two code steps, two k-steps wider, eight m-tiles each");
 constexpr int kBwdFrags = plan::kBwdFrags;
 // d code(x) stream of the input gradient: A[j][k] = W0[k][j] (part 0) and W4[k][256 + j] (part 1), code rows j < 64
 // (two m-tiles) x 16 accumulator-order k-steps over the 256 hidden units
 constexpr int kGradFrags = 2 * 2 * 16;
 
-constexpr int group_of(int kind, int m) {
-  int g = 0;
-  for (int k = plan::F_PTS0; k < kind; ++k) g += step_of(k).mt;
-  return g + m;
-}
-
-constexpr Chunks make_fwd_chunks() {
-  Chunks c{};
-  int g = 0, chunk = -1, fill = plan::kChunkFrags + 1, frag = 0;
-  for (int kind = plan::F_PTS0; kind <= plan::F_RGB; ++kind) {
-    const int ks = step_ks(kind);
-    for (int m = 0; m < step_of(kind).mt; ++m, ++g) {
-      const bool open = fill + ks > plan::kChunkFrags;
-      if (open) {
-        ++chunk;
-        fill = 0;
-        c.chunk_frag0[chunk] = frag;
-        c.chunk_count[chunk] = 0;
-      }
-      c.group_chunk[g] = chunk;
-      c.group_off[g] = fill;
-      c.group_first[g] = open;
-      fill += ks;
-      frag += ks;
-      c.chunk_count[chunk] += ks;
-    }
-  }
-  c.n_groups = g;
-  c.n_chunks = chunk + 1;
-  return c;
-}
-constexpr Chunks kFwdChunks = make_fwd_chunks();
+// the vanilla chunk builder (greedy, m-tile granular, <= 64 fragments) over this step table
+constexpr Chunks kFwdChunks = plan::make_chunks(false, step_of);
 static_assert(kFwdChunks.n_chunks <= plan::kMaxChunks && kFwdChunks.n_groups <= plan::kMaxGroups, "chunk table size");
 
 // ---- packed buffer (bytes): forward stream | dgrad stream | fp32 bias table (vanilla layout) | d-code stream ----

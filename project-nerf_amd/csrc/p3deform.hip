@@ -361,11 +361,6 @@ static Args args_of(const void* packed, void* ws, int64_t n) {
   for (int k = 0; k < 3; ++k) { a.h[k] = reinterpret_cast<__bf16*>(w + l.h[k]); a.dz[k] = reinterpret_cast<__bf16*>(w + l.dz[k]); }
   return a;
 }
-static int grid_for(int64_t tiles) {
-  int n_cu = 0;
-  if (device_cu_count(&n_cu) != NERF_OK) return -1;
-  return (int)(tiles < n_cu ? tiles : n_cu);       // one workgroup per CU (LDS)
-}
 
 }  // namespace p3
 }  // namespace nerf
@@ -393,7 +388,7 @@ extern "C" int nerf_p3_deform_fwd(const void* packed, void* workspace, const flo
   a.packed = static_cast<const char*>(packed);
   a.n = n; a.n_pad = (n + p3::kTile - 1) / p3::kTile * p3::kTile;
   a.x_code = x_code ? x_code : pts; a.x = pts; a.t = t_deform; a.dx = delta_x; a.xc = x_canonical;
-  const int grid = p3::grid_for(a.n_pad / p3::kTile);
+  const int grid = grid_for(a.n_pad / p3::kTile, 1);   // one workgroup per CU (LDS)
   if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_p3_deform_fwd: cannot query device");
   const void* kernel = train ? (const void*)p3::fwd_kernel<true> : (const void*)p3::fwd_kernel<false>;
   if (int rc = ensure_dynamic_lds(kernel, p3::kFwdLds, "nerf_p3_deform_fwd"); rc != NERF_OK) return rc;
@@ -409,7 +404,7 @@ extern "C" int nerf_p3_deform_bwd(const void* packed, void* workspace, const flo
   NERF_REQUIRE(packed && workspace && d_delta_x && ((uintptr_t)workspace & 255) == 0, "nerf_p3_deform_bwd: bad pointer");
   p3::Args a = p3::args_of(packed, workspace, n);
   a.d_dx = d_delta_x;
-  const int grid = p3::grid_for(a.n_pad / p3::kTile);
+  const int grid = grid_for(a.n_pad / p3::kTile, 1);   // one workgroup per CU (LDS)
   if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_p3_deform_bwd: cannot query device");
   if (int rc = ensure_dynamic_lds((const void*)p3::dgrad_kernel, p3::kBwdLds, "nerf_p3_deform_bwd"); rc != NERF_OK) return rc;
   hipLaunchKernelGGL(p3::dgrad_kernel, dim3(grid), dim3(p3::kThreads), p3::kBwdLds, as_stream(stream), a);

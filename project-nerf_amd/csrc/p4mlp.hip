@@ -705,13 +705,6 @@ static CanonArgs canon_args(const void* packed, void* ws, int64_t n) {
   return a;
 }
 
-static int grid_for(int64_t tiles) {
-  int n_cu = 0;
-  if (device_cu_count(&n_cu) != NERF_OK) return -1;
-  const int64_t cap = (int64_t)n_cu * 4;
-  return (int)(tiles < cap ? tiles : cap);
-}
-
 }  // namespace p4
 }  // namespace nerf
 
@@ -769,7 +762,7 @@ extern "C" int nerf_p4_deform_fwd(const void* packed, const float* params_f32, v
                "nerf_p4_deform_fwd: bad pointer");
   DeformArgs a = deform_args(packed, params_f32, workspace, n);
   a.t = t_deform; a.blend = blend; a.x = pts; a.dx = delta_x; a.xc = x_canonical;
-  const int grid = grid_for(a.n_pad / kTile);
+  const int grid = grid_for(a.n_pad / kTile, 4);
   if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_p4_deform_fwd: cannot query device");
   const int lds = kDeformFwdN * 1024 + 256;
   if (train) hipLaunchKernelGGL(p4::deform_fwd_kernel<true>, dim3(grid), dim3(kThreads), lds, as_stream(stream), a);
@@ -784,7 +777,7 @@ extern "C" int nerf_p4_canon_fwd(const void* packed, void* workspace, const floa
   NERF_REQUIRE(packed && workspace && t_deform && dirs && rgb && sigma && ((uintptr_t)workspace & 255) == 0, "nerf_p4_canon_fwd: bad pointer");
   CanonArgs a = canon_args(packed, workspace, n);
   a.t = t_deform; a.dirs = dirs; a.rgb = rgb; a.sigma = sigma;
-  const int grid = grid_for(a.n_pad / kTile);
+  const int grid = grid_for(a.n_pad / kTile, 4);
   if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_p4_canon_fwd: cannot query device");
   if (train) hipLaunchKernelGGL(p4::canon_fwd_kernel<true>, dim3(grid), dim3(kThreads), kCanonFwdN * 1024, as_stream(stream), a);
   else hipLaunchKernelGGL(p4::canon_fwd_kernel<false>, dim3(grid), dim3(kThreads), kCanonFwdN * 1024, as_stream(stream), a);
@@ -811,7 +804,7 @@ extern "C" int nerf_p4_canon_bwd(const void* packed, void* workspace, const floa
   CanonArgs a = canon_args(packed, workspace, n);
   a.rgb = const_cast<float*>(rgb); a.sigma = const_cast<float*>(sigma); a.d_rgb = d_rgb; a.d_sigma = d_sigma;
   a.amax_bits = static_cast<unsigned*>(amax_bits); a.grad_lm = static_cast<float2*>(grad_lm);
-  const int grid = grid_for(a.n_pad / kTile);
+  const int grid = grid_for(a.n_pad / kTile, 4);
   if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_p4_canon_bwd: cannot query device");
   hipLaunchKernelGGL(p4::canon_bwd_kernel, dim3(grid), dim3(kThreads), kCanonBwdN * 1024, as_stream(stream), a);
   if (int rc = check_launch("nerf_p4_canon_bwd (dgrad)"); rc != NERF_OK) return rc;
@@ -840,7 +833,7 @@ extern "C" int nerf_p4_deform_bwd(const void* packed, const float* params_f32, v
   DeformArgs a = deform_args(packed, params_f32, workspace, n);
   a.d_dx = d_delta_x; a.g_scale = grads_f32 + kScale; a.amax_bits = static_cast<unsigned*>(amax_bits);
   a.grad_lm = static_cast<float2*>(grad_lm);
-  const int grid = grid_for(a.n_pad / kTile);
+  const int grid = grid_for(a.n_pad / kTile, 4);
   if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_p4_deform_bwd: cannot query device");
   const bool det = options().deterministic != 0;
   const Layout l = layout(n);

@@ -6,7 +6,6 @@
 // pack source map, its code operand, its chain kernels, its job table and its C entries; every __global__ entry point stays in its
 // own file and namespace.
 #pragma once
-#include <limits.h>
 #include "mlp_chain.h"
 
 namespace nerf {
@@ -185,14 +184,6 @@ static size_t take(size_t* o, size_t bytes) {
   const size_t at = *o;
   *o += (bytes + 255) / 256 * 256;
   return at;
-}
-// workgroups of a chain launch: one per tile up to workgroups_per_cu per CU and `cap`; -1: the device cannot be queried
-static int grid_for(int64_t tiles, int workgroups_per_cu, int cap = INT_MAX) {
-  int n_cu = 0;
-  if (device_cu_count(&n_cu) != NERF_OK) return -1;
-  int64_t most = (int64_t)n_cu * workgroups_per_cu;
-  if (most > cap) most = cap;
-  return (int)(tiles < most ? tiles : most);
 }
 template <class A>
 static int launch_chain(void (*kernel)(A), int grid, int threads, int lds, nerf_stream_t stream, const char* what, const A& args) {

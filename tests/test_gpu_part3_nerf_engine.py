@@ -365,3 +365,56 @@ def test_run_py_with_the_engine_trains_and_evaluates(tmp_path, mode):
     assert np.isfinite(float(line.split("Test PSNR:")[1].split("dB")[0])), line
     ckpt = torch.load(tmp_path / "out" / "dyn" / "best_model.pth", map_location="cpu")
     assert ("decoder_direct.pts_layers.0.weight" if mode == "dtc" else "deform_net.net.0.weight") in ckpt["model_state_dict"]
+
+
+# ------------------------------------------------------------------ one chain body, two decoders
+@pytest.fixture
+def compiler_scheduled_family():
+    """the vanilla decoder on its compiler-scheduled kernels (library option chain_legacy), restored afterwards"""
+    from project_nerf_amd import _lib
+    _lib.set_option("chain_legacy", 1)
+    yield
+    _lib.set_option("chain_legacy", 0)
+
+
+def embed_vanilla_in_canonical(flat, tdim):
+    """the vanilla decoder's parameter vector in the canonical layout for 63 + tdim code columns (p3canon_plan.h::layout): the time
+    columns of pts_layers.0 and pts_layers.4 are zero, everything else is copied"""
+    C, plain = 63 + tdim, 256 * 256 + 256
+    w0 = torch.zeros(256, C)
+    w0[:, :63] = flat[:256 * 63].view(256, 63)
+    v4 = 256 * 63 + 256 + 3 * plain                        # pts_layers.4.weight [256, 319] in the vanilla vector
+    w4 = torch.zeros(256, 256 + C)
+    w4[:, :319] = flat[v4:v4 + 256 * 319].view(256, 319)
+    return torch.cat([w0.reshape(-1), flat[256 * 63:v4], w4.reshape(-1), flat[v4 + 256 * 319:]])
+
+
+@pytest.mark.parametrize("n", [1, 300, 70464])
+def test_canonical_forward_equals_the_vanilla_forward_bit_for_bit(n, compiler_scheduled_family):
+    """mlp_fwd_kernel (vanilla, compiler-scheduled) and p3c::fwd_kernel are two instances of one body (mlp_chain_body.h).  On a
+    vanilla parameter vector embedded in the canonical layout they run the same MFMA sequence per m-tile from the same bias, k-step
+    0 upward; the canonical chain's two extra k-steps multiply finite time codes by exact zeros, and column 63 has a zero weight
+    in both packers: rgb and sigma are equal bit for bit, for any finite t, with and without the training images.
+    n = 300: one full tile and a ragged one whose upper waves have no live sample; n = 70464: 276 tiles, more than the CU count,
+    so some workgroups take a second pass across the ring's wrap-around."""
+    from oracle import nerf_oracle as O
+    from project_nerf_amd import ops
+    from project_nerf_amd import part3_nerf as p3n
+    params = O.nerf_init_params(seed=5)                                   # weights x 2.5: outputs that vary
+    flat = torch.cat([(params[k] * 2.5 if k.endswith("weight") else params[k]).reshape(-1) for k, _ in O.nerf_param_shapes()])
+    x, d, _ = points(n, 11)
+    packed_v = ops.mlp_pack(flat.cuda())
+    rgb_v, sigma_v = ops.mlp_fwd(packed_v, x, d, None)
+    stash = torch.empty(max(ops.mlp_stash_bytes(n), 256), dtype=torch.uint8, device="cuda")
+    rgb_vt, sigma_vt = ops.mlp_fwd(packed_v, x, d, None, stash=stash)
+    assert torch.equal(rgb_v, rgb_vt) and torch.equal(sigma_v, sigma_vt)
+    assert n == 1 or float(rgb_v.std()) > 0.0                             # not a comparison of constants
+    g = torch.Generator().manual_seed(12)
+    t = ((torch.rand(n, generator=g) - 0.5) * 40.0).cuda()                # arbitrary finite times
+    ws = torch.empty(p3n.canon_workspace_bytes(n), dtype=torch.uint8, device="cuda")
+    for tdim in (21, 13):
+        canon = embed_vanilla_in_canonical(flat, tdim).cuda()
+        packed = p3n.canon_pack(canon, tdim)
+        for workspace in (None, ws):
+            rgb_c, sigma_c = p3n.canon_fwd(packed, x, t, d, workspace=workspace)
+            assert torch.equal(rgb_c, rgb_v) and torch.equal(sigma_c, sigma_v), (tdim, workspace is not None)
