@@ -7,11 +7,12 @@
 // and the direction code always take two natural-order k-steps, whose columns past 2L (past D) are structural zeros of the
 // weight fragments.
 //
-// The register chain is imlp.hip's, step for step and k-step for k-step (32 samples per wave on the MFMA column, accumulator
-// tiles -> bf16 B fragments, every weight fragment resident in LDS for the whole launch: 68 KiB forward at H = 128), with the
-// same rounding points -- bf16 hash features, direction code, post-ReLU activations, h16 and gradient images, fp32 accumulation,
-// sigma and rgb -- and the same softplus, softplus' (-expm1f(-sigma)) and sigmoid formulas: at (16, 64, 4) the forward and the
-// feature gradients carry imlp.hip's bits.
+// The register chain is imlp.hip's, step for step and k-step for k-step, on the shared pieces of resident_chain.h (32 samples per
+// wave on the MFMA column, accumulator tiles -> bf16 B fragments, every weight fragment resident in LDS for the whole launch:
+// 68 KiB forward at H = 128; pack loop, LDS prologue, fenced step runner, the Instant head), with the same rounding points --
+// bf16 hash features, direction code, post-ReLU activations, h16 and gradient images, fp32 accumulation, sigma and rgb -- and the
+// same softplus, softplus' (-expm1f(-sigma)) and sigmoid formulas: at (16, 64, 4) the forward and the feature gradients carry
+// imlp.hip's bits.
 //
 // The hash forward writes columns 0..2L-1 of its operand image only (hashgrid.hip: n_ks = ceil(2L / 16) k-steps per wave tile):
 // columns 2L..16 n_ks - 1 may hold anything, NaN included, and a zero weight does not remove a NaN.  They are cleared by a select
@@ -29,11 +30,13 @@
 //   sigma_net : W1 [H, pad16(2L)] | W2 [16, H]
 //   color_net : W1 [H, pad16(16 + D)] | W2 [H, H] | W3 [16, H] (rows 3..15 unused)
 #include <math.h>
+#include "resident_chain.h"
 #include "sample_chain.h"
 
 namespace nerf {
 namespace ishape {
 using namespace sample_chain;
+using namespace resident;
 
 constexpr int kThreads = 256, kTile = 128;
 constexpr int kHashLd = 32, kCatLd = 48, kH16Ld = 16, kSmallLd = 8;
@@ -57,7 +60,6 @@ static const char* make_plan(int L, int H, int Ld, Plan* p) {
 }
 
 // fragment plan of one H; forward steps 0..4 = S1 S2 C1 C2 C3, backward 5..9 = C3t C2t C1t S2t S1t (imlp.hip::istep at H = 64)
-struct Step { int mt, ks_acc, ks_nat, frag0; };
 __host__ __device__ constexpr Step step_of(int H, int s) {
   const int MT = H / 32, KS = H / 16;
   const int mt[10] = {MT, 1, MT, MT, 1, MT, MT, 1, MT, 1};
@@ -67,6 +69,8 @@ __host__ __device__ constexpr Step step_of(int H, int s) {
   for (int i = 0; i < s; ++i) f += mt[i] * (ka[i] + kn[i]);
   return {mt[s], ka[s], kn[s], f};
 }
+template <int H>
+constexpr Step step_h(int s) { return step_of(H, s); }
 __host__ __device__ constexpr int fwd_frags(int H) { return step_of(H, 5).frag0; }
 __host__ __device__ constexpr int all_frags(int H) { return step_of(H, 9).frag0 + H / 16; }
 static size_t packed_bytes(const Plan& p) { return (size_t)all_frags(p.H) * 1024; }
@@ -89,24 +93,9 @@ __device__ __forceinline__ int src_index(const Plan& p, int step, int row, int k
 }
 
 __global__ void __launch_bounds__(256) pack_kernel(const float* __restrict__ params, char* __restrict__ packed, const Plan p) {
-  const int total = all_frags(p.H);
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total * 64; t += gridDim.x * blockDim.x) {
-    const int frag = t >> 6, lane = t & 63, h = lane >> 5;
-    int step = 0;
-    for (int s = 0; s < 10; ++s) if (frag >= step_of(p.H, s).frag0) step = s;
-    const Step st = step_of(p.H, step);
-    const int kpt = st.ks_acc + st.ks_nat, rel = frag - st.frag0, mt = rel / kpt, ks = rel % kpt;
-    const bool nat = ks >= st.ks_acc;
-    const int row = mt * 32 + (lane & 31);
-    unsigned short out[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int k = frag_column(nat ? ks - st.ks_acc : ks, h, j, nat);
-      const int src = src_index(p, step, row, k, nat);
-      out[j] = __builtin_bit_cast(unsigned short, (__bf16)(src >= 0 ? params[src] : 0.0f));
-    }
-    store_fragment(packed, frag, lane, out);
-  }
+  pack_fragments(params, packed, all_frags(p.H), 10, [&](int s) { return step_of(p.H, s); },
+                 [&](int step, int row, int k, bool nat) { return src_index(p, step, row, k, nat); }, [](int) { return false; },
+                 blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
 struct Args {
@@ -138,21 +127,6 @@ __device__ __forceinline__ uint32_t relu_bits16(const bf16x8& lo, const bf16x8& 
     bits |= (((th >> 15) & 1u) | ((th >> 30) & 2u)) << (8 + 2 * q);
   }
   return bits;
-}
-
-template <int H, int STEP, int KS, class Epi>
-__device__ __forceinline__ void step_run(const char* wbase, const bf16x8 (&b)[KS], Epi&& epi) {
-  constexpr Step st = step_of(H, STEP);
-  static_assert(KS == st.ks_acc + st.ks_nat, "k-steps");
-  static_for<st.mt>([&](auto mc) {
-    constexpr int m = decltype(mc)::value;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    acc = mtile<KS>(wbase, st.frag0 + m * KS, b, acc);
-    epi(mc, acc);
-    __builtin_amdgcn_sched_barrier(0);       // one tile at a time: interleaved tiles cost registers at H = 128
-  });
 }
 
 // the two natural-order k-steps of the hash features of wave tile wt: feature f = 16 ks + 8 half + j, CLEARED from 2L on (the
@@ -193,10 +167,8 @@ __global__ void __launch_bounds__(kThreads, 2) fwd_kernel(const Args a) {
   constexpr int KS = H / 16, MW = mask_words(H), FR = fwd_frags(H);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
-  for (int i = tid; i < FR * 64; i += kThreads)
-    reinterpret_cast<uint4*>(smem)[i] = reinterpret_cast<const uint4*>(a.packed)[i];
+  const char* wbase = resident_weights<kThreads>(smem, a.packed, 0, FR, tid, lane);
   __syncthreads();
-  const char* wbase = smem + lane * 16;
   const int64_t n_tiles = a.n_pad / kTile;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const int64_t wt = tile * 4 + wave, n = wt * 32 + col;
@@ -226,27 +198,21 @@ __global__ void __launch_bounds__(kThreads, 2) fwd_kernel(const Args a) {
       };
     };
     bf16x8 hs1[KS], h16[2], hc1[KS], hc2[KS];
-    step_run<H, 0, 2>(wbase, hin, relu_epi(hs1, a.hs1, 0));
+    run_step<step_h<H>, 0, 2, true>(wbase, hin, nullptr, MfmaBf{}, relu_epi(hs1, a.hs1, 0));
     float h0 = 0.0f;
-    step_run<H, 1, KS>(wbase, hs1, [&](auto, f32x16 acc) {
+    run_step<step_h<H>, 1, KS, true>(wbase, hs1, nullptr, MfmaBf{}, [&](auto, f32x16 acc) {
       h0 = acc[0];
       acc_to_operand(acc, h16[0], h16[1]);            // rows 16..31 of this tile are structural zeros: h16[1] is not used
       if constexpr (TRAIN) store_rows16(a.cat, kCatLd, n, half, h16[0]);
     });
-    if (live && half == 0) {
-      const float x = h0 - 5.0f;                               // decoders.py:153
-      a.sigma[n] = x > 20.0f ? x : log1pf(expf(x));            // F.softplus (threshold 20)
-    }
+    if (live && half == 0) a.sigma[n] = head_sigma(h0);
     {
       bf16x8 cat[3] = {h16[0], denc[0], denc[1]};
-      step_run<H, 2, 3>(wbase, cat, relu_epi(hc1, a.hc1, 1));
+      run_step<step_h<H>, 2, 3, true>(wbase, cat, nullptr, MfmaBf{}, relu_epi(hc1, a.hc1, 1));
     }
-    step_run<H, 3, KS>(wbase, hc1, relu_epi(hc2, a.hc2, 2));
-    step_run<H, 4, KS>(wbase, hc2, [&](auto, f32x16 acc) {
-      if (live && half == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) a.rgb[n * 3 + c] = 1.0f / (1.0f + __expf(-acc[c]));
-      }
+    run_step<step_h<H>, 3, KS, true>(wbase, hc1, nullptr, MfmaBf{}, relu_epi(hc2, a.hc2, 2));
+    run_step<step_h<H>, 4, KS, true>(wbase, hc2, nullptr, MfmaBf{}, [&](auto, f32x16 acc) {
+      if (live && half == 0) head_rgb_store(a.rgb, n, acc);
     });
     if constexpr (TRAIN) {
       unsigned* mp = a.mask + (tile * kThreads + tid) * (3 * MW);
@@ -261,28 +227,20 @@ __global__ void __launch_bounds__(kThreads, 2) dgrad_kernel(const Args a) {
   constexpr int KS = H / 16, MW = mask_words(H), FR = fwd_frags(H), BR = all_frags(H) - FR;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
-  for (int i = tid; i < BR * 64; i += kThreads)
-    reinterpret_cast<uint4*>(smem)[i] = reinterpret_cast<const uint4*>(a.packed + FR * 1024)[i];
+  const char* wbase = resident_weights<kThreads>(smem, a.packed, FR, BR, tid, lane);     // step_of().frag0 counts from the forward stream
   __syncthreads();
-  const char* wbase = smem + lane * 16 - FR * 1024;            // step_of().frag0 counts from the forward stream
   const int64_t n_tiles = a.n_pad / kTile;
   const int F = a.p.F;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const int64_t wt = tile * 4 + wave, n = wt * 32 + col;
     const bool live = n < a.n;
-    float g0 = 0.f, g1 = 0.f, g2 = 0.f, gs = 0.f;
-    if (live) {
-      const float r0 = a.rgb[n * 3 + 0], r1 = a.rgb[n * 3 + 1], r2 = a.rgb[n * 3 + 2];
-      g0 = a.d_rgb[n * 3 + 0] * r0 * (1.0f - r0);
-      g1 = a.d_rgb[n * 3 + 1] * r1 * (1.0f - r1);
-      g2 = a.d_rgb[n * 3 + 2] * r2 * (1.0f - r2);
-      gs = a.d_sigma[n] * -expm1f(-a.sigma[n]);                // softplus'(x) = sigmoid(x) = 1 - exp(-softplus(x)), no cancellation
-    }
+    float g[4];
+    head_derivs(a, n, live, g);
     bf16x8 small;
 #pragma unroll
     for (int j = 0; j < 8; ++j) small[j] = (__bf16)0.0f;
-    if (half == 0) {
-      small[0] = (__bf16)g0; small[1] = (__bf16)g1; small[2] = (__bf16)g2;
+    if (half == 0) {                                           // small_operand, and its row-major image from the same lanes
+      small[0] = (__bf16)g[0]; small[1] = (__bf16)g[1]; small[2] = (__bf16)g[2];
       *reinterpret_cast<bf16x8*>(a.dsmall + n * kSmallLd) = small;
     }
     uint32_t mw[3 * MW];
@@ -294,23 +252,21 @@ __global__ void __launch_bounds__(kThreads, 2) dgrad_kernel(const Args a) {
     auto grad_epi = [&](bf16x8* out, __bf16* img, int layer) {
       return [=, &mw](auto mc, f32x16 acc) {
         constexpr int m = decltype(mc)::value;
-        const uint32_t bits = mw[layer * MW + (m >> 1)] >> (16 * (m & 1));
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = (bits >> r) & 1u ? acc[r] : 0.0f;
+        mask_grad(acc, mw[layer * MW + (m >> 1)] >> (16 * (m & 1)));
         acc_to_operand(acc, out[2 * m], out[2 * m + 1]);
         store_rows(img, H, n, m, half, out[2 * m], out[2 * m + 1]);
       };
     };
     bf16x8 gc2[KS], gc1[KS], g16[2], gs1[KS];
-    { bf16x8 in[1] = {small}; step_run<H, 5, 1>(wbase, in, grad_epi(gc2, a.dzc2, 2)); }
-    step_run<H, 6, KS>(wbase, gc2, grad_epi(gc1, a.dzc1, 1));
-    step_run<H, 7, KS>(wbase, gc1, [&](auto, f32x16 acc) {
-      if (half == 0) acc[0] += gs;                              // row 0 of h also feeds sigma
+    { bf16x8 in[1] = {small}; run_step<step_h<H>, 5, 1, true>(wbase, in, nullptr, MfmaBf{}, grad_epi(gc2, a.dzc2, 2)); }
+    run_step<step_h<H>, 6, KS, true>(wbase, gc2, nullptr, MfmaBf{}, grad_epi(gc1, a.dzc1, 1));
+    run_step<step_h<H>, 7, KS, true>(wbase, gc1, nullptr, MfmaBf{}, [&](auto, f32x16 acc) {
+      if (half == 0) acc[0] += g[3];                             // row 0 of h also feeds sigma
       acc_to_operand(acc, g16[0], g16[1]);
       store_rows16(a.dzs2, kH16Ld, n, half, g16[0]);
     });
-    { bf16x8 in[1] = {g16[0]}; step_run<H, 8, 1>(wbase, in, grad_epi(gs1, a.dzs1, 0)); }
-    step_run<H, 9, KS>(wbase, gs1, [&](auto, f32x16 acc) {
+    { bf16x8 in[1] = {g16[0]}; run_step<step_h<H>, 8, 1, true>(wbase, in, nullptr, MfmaBf{}, grad_epi(gs1, a.dzs1, 0)); }
+    run_step<step_h<H>, 9, KS, true>(wbase, gs1, nullptr, MfmaBf{}, [&](auto, f32x16 acc) {
       if (!live) return;
       // registers 4g..4g+3 = features 8g + 4 half + (0..3); a row of d_feat is 8L bytes: 8-byte stores, columns below 2L only
       float* row = a.d_feat + n * F;

@@ -126,12 +126,6 @@ __device__ __forceinline__ f32x16 mtile(const char* a_base, int frag_off, const 
   return acc;
 }
 
-// Packing a 1-KiB A fragment (32 rows x 16 k): lane (row & 31, h) holds 8 elements.  Column of element j of k-step ks_rel:
-// natural order (the operand is a code or a gradient read as stored) 16 ks + 8 h + j; accumulator order (the operand is the
-// previous step's accumulator tiles: register r of lane-half h is row 8 (r >> 2) + 4 h + (r & 3) of its 32)
-__host__ __device__ __forceinline__ int frag_column(int ks_rel, int h, int j, bool nat) {
-  return nat ? 16 * ks_rel + 8 * h + j : 32 * (ks_rel >> 1) + 16 * (ks_rel & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
-}
 // the lane's eight 16-bit elements (bf16 or fp16 bit patterns) -> bytes [16 lane, 16 lane + 16) of fragment `frag`
 __device__ __forceinline__ void store_fragment(char* packed, size_t frag, int lane, const unsigned short (&out)[8]) {
   uint4 bits;
@@ -182,6 +176,11 @@ __device__ __forceinline__ void acc_to_operand(const f32x16& acc, bf16x8& lo, bf
     lo[j] = (__bf16)acc[j];
     hi[j] = (__bf16)acc[8 + j];
   }
+}
+// the same as fp16 fragments (the forward chains of p4mlp.hip / p3deform.hip contract v_mfma_f32_32x32x16_f16)
+__device__ __forceinline__ void acc_to_operand16(const f32x16& acc, f16x8& lo, f16x8& hi) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { lo[j] = (_Float16)acc[j]; hi[j] = (_Float16)acc[8 + j]; }
 }
 
 template <int N, class F, int... I>
@@ -407,6 +406,12 @@ static int grid_for(int64_t tiles, int workgroups_per_cu, int cap = INT_MAX) {
   int64_t most = (int64_t)n_cu * workgroups_per_cu;
   if (most > cap) most = cap;
   return (int)(tiles < most ? tiles : most);
+}
+// the next `bytes` of a workspace laid out from *o, every piece 256-byte aligned
+static size_t take(size_t* o, size_t bytes) {
+  const size_t at = *o;
+  *o += (bytes + 255) / 256 * 256;
+  return at;
 }
 
 }  // namespace nerf

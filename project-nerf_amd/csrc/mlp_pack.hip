@@ -89,9 +89,7 @@ pack_kernel(const float* __restrict__ params, __bf16* __restrict__ packed_fwd,
     bf16x8 out;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      int k;
-      if (nat) k = 16 * (ks - st.ks_acc) + 8 * h + j;
-      else k = 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
+      const int k = frag_column(nat ? ks - st.ks_acc : ks, h, j, nat);
       const int src = src_index(kind, row, k, nat);
       out[j] = (__bf16)(src >= 0 ? params[src] : 0.0f);
     }

@@ -172,4 +172,11 @@ constexpr size_t kPackBytes = kPackFwd16Off + (size_t)kFwdFrags * kFragBytes + k
 constexpr int kStashXenc = 64, kStashDenc = 32;
 
 }  // namespace plan
+
+// Packing a 1-KiB A fragment (32 rows x 16 k): lane (row & 31, h) holds 8 elements.  Column of element j of k-step ks_rel:
+// natural order (the operand is a code or a gradient read as stored) 16 ks + 8 h + j; accumulator order (the operand is the
+// previous step's accumulator tiles: register r of lane-half h is row 8 (r >> 2) + 4 h + (r & 3) of its 32)
+constexpr int frag_column(int ks_rel, int h, int j, bool nat) {
+  return nat ? 16 * ks_rel + 8 * h + j : 32 * (ks_rel >> 1) + 16 * (ks_rel & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
+}
 }  // namespace nerf

@@ -59,6 +59,28 @@ struct WgradArgs {
   int debug;            // development aid (NERF_WGRAD_DEBUG): bit0 skip MFMA/LDS reads, bit1 skip DMA, bit2 skip flush
 };
 
+// a job on images of one workspace `w`: A at a_off (a_bytes per wave tile, mt_a 32-row tiles), nt_acc blocked column tiles at
+// b_off, nt_nat natural ones at bn_off; the caller sets the parameter block (w_off ...) and whatever else its kind needs
+static inline WgradJob make_job(const char* w, size_t a_off, int a_bytes, int mt_a, size_t b_off, int nt_acc, size_t bn_off, int nt_nat,
+                                int kind) {
+  WgradJob j{};
+  j.a = w + a_off; j.a_bytes = a_bytes; j.mt_a = mt_a;
+  if (nt_acc) { j.b_acc = w + b_off; j.b_acc_bytes = nt_acc * 2048; j.nt_acc = nt_acc; }
+  if (nt_nat) { j.b_nat = w + bn_off; j.b_nat_bytes = nt_nat * 2048; j.nt_nat = nt_nat; }
+  j.bias_nat_col = -1; j.kind = kind;
+  return j;
+}
+
+// Jobs 1..4 of an Instant-NGP decoder backward (imlp.hip, p4mlp.hip's canonical chain): sigma-net layer 2 and the three
+// colour-net layers, whose images and shapes both decoders share.  Job 0, the sigma-net's first layer, differs in its input
+// image and stays with each caller.
+struct InstantImages { size_t hs1, h16, denc, hc1, hc2, dzs2, dzc1, dzc2, dsmall; };   // workspace offsets
+static inline void instant_common_jobs(WgradArgs& wa, const char* w, const InstantImages& o, int s2, int c1, int c2, int c3) {
+  { WgradJob j = make_job(w, o.dzs2, 2048, 1, o.hs1, 2, 0, 0, 7); j.w_off = s2; j.w_ld = 64; j.o_valid = 16; j.acc_valid = 64; wa.jobs[1] = j; }
+  { WgradJob j = make_job(w, o.dzc1, 4096, 2, o.h16, 1, o.denc, 1, 8); j.w_off = c1; j.w_ld = 48; j.o_valid = 64; j.acc_valid = 16; j.nat_valid = 27; j.nat_col0 = 16; wa.jobs[2] = j; }
+  { WgradJob j = make_job(w, o.dzc2, 4096, 2, o.hc1, 2, 0, 0, 7); j.w_off = c2; j.w_ld = 64; j.o_valid = 64; j.acc_valid = 64; wa.jobs[3] = j; }
+  { WgradJob j = make_job(w, o.dsmall, 1024, 1, o.hc2, 2, 0, 0, 9); j.a_nat = 1; j.split_n = 1; j.w_off = c3; j.w_ld = 64; j.o_valid = 3; j.acc_valid = 64; wa.jobs[4] = j; }
+}
 
 // fills cost0 / total_cost / wave_tiles / grads and launches; jobs[0..n_jobs) must be set
 // slab: partial-tile memory of slab_bytes (mlp_stash.h::kSlabBytes) or null for the atomic flush; in slab mode

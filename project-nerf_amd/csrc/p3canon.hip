@@ -89,20 +89,19 @@ inline Layout layout(int64_t n) {
   s.n_pad = (n + 255) / 256 * 256;
   const size_t np = (size_t)s.n_pad;
   size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
-  s.xenc = take(np * cplan::kCodeK * 2);
-  s.h = take(np * 256 * 2 * 8);
-  s.feat = take(np * 256 * 2);
-  s.hv = take(np * 128 * 2);
-  s.denc = take(np * 32 * 2);
-  s.mask = take((np / 256) * 9 * 512 * 16);
-  s.dsmall = take(np * 16 * 2);
-  s.dhv = take(np * 128 * 2);
-  s.dfeat = take(np * 256 * 2);
-  s.dh = take(np * 256 * 2 * 8);
-  s.egrad = take((size_t)cplan::eCount * 4);
+  s.xenc = take(&o, np * cplan::kCodeK * 2);
+  s.h = take(&o, np * 256 * 2 * 8);
+  s.feat = take(&o, np * 256 * 2);
+  s.hv = take(&o, np * 128 * 2);
+  s.denc = take(&o, np * 32 * 2);
+  s.mask = take(&o, (np / 256) * 9 * 512 * 16);
+  s.dsmall = take(&o, np * 16 * 2);
+  s.dhv = take(&o, np * 128 * 2);
+  s.dfeat = take(&o, np * 256 * 2);
+  s.dh = take(&o, np * 256 * 2 * 8);
+  s.egrad = take(&o, (size_t)cplan::eCount * 4);
   s.slab_bytes = slab_bytes(n);
-  s.slab = take(s.slab_bytes);
+  s.slab = take(&o, s.slab_bytes);
   s.total = o;
   return s;
 }
@@ -324,7 +323,7 @@ __global__ void __launch_bounds__(256) pack_kernel(const float* __restrict__ par
     bf16x8 out;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const int k = nat ? 16 * (ks - st.ks_acc) + 8 * h + j : 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
+      const int k = frag_column(nat ? ks - st.ks_acc : ks, h, j, nat);
       const int src = src_index(L, td, kind, row, k, nat);
       out[j] = (__bf16)(src >= 0 ? params[src] : 0.0f);
     }

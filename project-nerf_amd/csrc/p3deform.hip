@@ -8,12 +8,12 @@
 //   dx = W4 h3 + b4                       128 -> 3
 //   x_c = x + dx                          x, NOT the noised x' (core.py:268-270)
 //
-// Same register chain as p4mlp.hip: 32 samples per wave on the MFMA column, accumulator tiles -> 16-bit B fragments of the
-// next layer, every weight fragment of one direction resident in LDS (forward 96 KiB fp16 + 1 KiB of biases, backward 68 KiB
-// bf16: one workgroup of 8 waves per CU).  The forward contracts fp16 operands (v_mfma_f32_32x32x16_f16) for the reason
-// p4mlp.hip gives: dx moves x_c inside a canonical hash grid whose finest cells are ~4.3e-4 wide.  The backward and the
-// training images are bf16.  b1 rides on a constant-1 column (84) of the layer-1 operand, b2 / b3 initialise the accumulators,
-// b4 is added to the output.
+// The resident-weight register chain of resident_chain.h (pack loop, LDS prologue, step runner): 32 samples per wave on the MFMA
+// column, accumulator tiles -> 16-bit B fragments of the next layer, every weight fragment of one direction resident in LDS
+// (forward 96 KiB fp16 + 1 KiB of biases, backward 68 KiB bf16: one workgroup of 8 waves per CU).  The forward contracts fp16
+// operands (v_mfma_f32_32x32x16_f16) for the reason p4mlp.hip gives: dx moves x_c inside a canonical hash grid whose finest cells
+// are ~4.3e-4 wide.  The backward and the training images are bf16.  b1 rides on a constant-1 column (84) of the layer-1 operand,
+// b2 / b3 initialise the accumulators, b4 is added to the output.
 //
 // Training images are row-major [n_pad][width] bf16 (code 96, h1..h3 128; the relu masks are h > 0 of the stored values,
 // which bf16 rounding cannot flip).  The backward runs the transposed chain on the stored masks (no input gradient: x', t'
@@ -22,17 +22,17 @@
 //
 // Parameter vector (fp32, the module's state dict concatenated, [out, in] row-major):
 //   W1 [128,84] b1 [128] W2 [128,128] b2 [128] W3 [128,128] b3 [128] W4 [3,128] b4 [3]   deform_net.net.{0,2,4,6}
-#include "mlp_chain.h"
+#include "resident_chain.h"
+#include "sample_chain.h"
 
 namespace nerf {
 namespace p3 {
+using namespace resident;
 
 constexpr int kIn = 84, kHid = 128, kCodeLd = 96, kTimeDim = 21, kPosDim = 63;
 constexpr int kW1 = 0, kB1 = 10752, kW2 = 10880, kB2 = 27264, kW3 = 27392, kB3 = 43776, kW4 = 43904, kB4 = 44288, kParams = 44291;
 constexpr int kThreads = 512, kWaves = kThreads / 64, kTile = kWaves * 32;
 
-// (m-tiles, k-steps fed by accumulators, natural-order k-steps, first fragment)
-struct Step { int mt, ks_acc, ks_nat, frag0; };
 enum { F1, F2, F3, F4, B4t, B3t, B2t, kSteps };
 constexpr Step step_of(int s) {
   switch (s) {
@@ -53,7 +53,7 @@ constexpr int kFwdLds = kFwdN * 1024 + 2048, kBwdLds = kBwdN * 1024;
 // weight gradients: chunk-partial tiles of every parameter, then one ordered sum
 constexpr int kMaxChunks = 256, kMinChunk = 1024, kSub = 32;
 
-__device__ __forceinline__ int src_of(int step, int row, int k) {
+__device__ __forceinline__ int src_of(int step, int row, int k, bool) {
   switch (step) {
     case F1: return k < kIn ? kW1 + row * kIn + k : (k == kIn ? kB1 + row : -1);
     case F2: return kW2 + row * kHid + k;
@@ -66,70 +66,12 @@ __device__ __forceinline__ int src_of(int step, int row, int k) {
 }
 
 __global__ void __launch_bounds__(256) pack_kernel(const float* __restrict__ params, char* __restrict__ packed) {
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < kFrags * 64; t += gridDim.x * blockDim.x) {
-    const int frag = t >> 6, lane = t & 63;
-    int step = 0;
-    for (int s = 0; s < kSteps; ++s) if (frag >= step_of(s).frag0) step = s;
-    const Step st = step_of(step);
-    const int ksn = st.ks_acc + st.ks_nat, rel = frag - st.frag0, mt = rel / ksn, ks = rel % ksn;
-    const int row = mt * 32 + (lane & 31), h = lane >> 5;
-    const bool nat = ks >= st.ks_acc;
-    const bool fwd = step <= F4;
-    unsigned short out[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int k = nat ? 16 * (ks - st.ks_acc) + 8 * h + j : 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
-      const int src = src_of(step, row, k);
-      const float v = src >= 0 ? params[src] : 0.0f;
-      out[j] = fwd ? __builtin_bit_cast(unsigned short, (_Float16)v) : __builtin_bit_cast(unsigned short, (__bf16)v);
-    }
-    uint4 bits;
-    bits.x = out[0] | ((unsigned)out[1] << 16); bits.y = out[2] | ((unsigned)out[3] << 16);
-    bits.z = out[4] | ((unsigned)out[5] << 16); bits.w = out[6] | ((unsigned)out[7] << 16);
-    *reinterpret_cast<uint4*>(packed + (size_t)frag * 1024 + lane * 16) = bits;
-  }
+  pack_fragments(params, packed, kFrags, kSteps, step_of, src_of, [](int step) { return step <= F4; },   // forward: fp16, backward: bf16
+                 blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
   if (blockIdx.x == 0) {
     float* bias = reinterpret_cast<float*>(packed + kBiasOff);
     for (int i = threadIdx.x; i < 512; i += blockDim.x)
       bias[i] = i < 128 ? params[kB2 + i] : (i < 256 ? params[kB3 + i - 128] : (i < 259 ? params[kB4 + i - 256] : 0.0f));
-  }
-}
-
-// every m-tile of STEP: acc = bias (or 0) + A B, then epi(m, acc)
-template <int STEP, int KS, class V, class F, class Epi>
-__device__ __forceinline__ void run(const char* wbase, const V (&b)[KS], const float* bias_lds, F mfma, Epi&& epi) {
-  constexpr Step st = step_of(STEP);
-  static_assert(KS == st.ks_acc + st.ks_nat, "k-steps");
-  const int half = (threadIdx.x & 63) >> 5;
-  static_for<st.mt>([&](auto mc) {
-    constexpr int m = decltype(mc)::value;
-    f32x16 acc;
-    if (bias_lds != nullptr) acc = bias_tile(bias_lds, 32 * m, half);
-    else {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    }
-    acc = mtile<KS>(wbase, st.frag0 + m * KS, b, acc, mfma);
-    epi(m, acc);
-  });
-}
-
-// accumulator rows of register r in lane-half h: 8 (r >> 2) + 4 h + (r & 3): four runs of 4 consecutive features
-__device__ __forceinline__ void store_rows(__bf16* img, int64_t n, int m, int half, const f32x16& acc) {
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    bf16x4 v;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = (__bf16)acc[4 * g + r];
-    *reinterpret_cast<bf16x4*>(img + n * kHid + 32 * m + 8 * g + 4 * half) = v;
-  }
-}
-__device__ __forceinline__ void load_rows(const __bf16* img, int64_t n, int m, int half, float (&out)[16]) {
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const bf16x4 v = *reinterpret_cast<const bf16x4*>(img + n * kHid + 32 * m + 8 * g + 4 * half);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) out[4 * g + r] = (float)v[r];
   }
 }
 
@@ -148,10 +90,9 @@ template <bool TRAIN>
 __global__ void __launch_bounds__(kThreads) fwd_kernel(const Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
-  for (int i = tid; i < kFwdN * 64; i += kThreads) reinterpret_cast<uint4*>(smem)[i] = reinterpret_cast<const uint4*>(a.packed)[i];
+  const char* wbase = resident_weights<kThreads>(smem, a.packed, kFwd0, kFwdN, tid, lane);
   if (tid < 128) reinterpret_cast<uint4*>(smem + kFwdN * 1024)[tid] = reinterpret_cast<const uint4*>(a.packed + kBiasOff)[tid];
   __syncthreads();
-  const char* wbase = smem + lane * 16;
   const float* bias = reinterpret_cast<const float*>(smem + kFwdN * 1024);
   const int64_t n_tiles = a.n_pad / kTile;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -183,19 +124,23 @@ __global__ void __launch_bounds__(kThreads) fwd_kernel(const Args a) {
       if constexpr (TRAIN) *reinterpret_cast<bf16x8*>(a.code + n * kCodeLd + 16 * ks + 8 * half) = cb;
     }
     auto relu_epi = [&](f16x8* out, __bf16* img) {
-      return [=](int m, f32x16 acc) {
+      return [=](auto mc, f32x16 acc) {
+        constexpr int m = decltype(mc)::value;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.0f);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { out[2 * m][j] = (_Float16)acc[j]; out[2 * m + 1][j] = (_Float16)acc[8 + j]; }
-        if constexpr (TRAIN) store_rows(img, n, m, half, acc);
+        acc_to_operand16(acc, out[2 * m], out[2 * m + 1]);
+        if constexpr (TRAIN) {
+          bf16x8 lo, hi;
+          acc_to_operand(acc, lo, hi);
+          sample_chain::store_rows(img, kHid, n, m, half, lo, hi);
+        }
       };
     };
     f16x8 h1[8], h2[8];
-    run<F1, 6>(wbase, code, nullptr, Mfma16{}, relu_epi(h1, a.h[0]));
-    run<F2, 8>(wbase, h1, bias, Mfma16{}, relu_epi(h2, a.h[1]));
-    run<F3, 8>(wbase, h2, bias + 128, Mfma16{}, relu_epi(h1, a.h[2]));
-    run<F4, 8>(wbase, h1, nullptr, Mfma16{}, [&](int, f32x16 acc) {
+    run_step<step_of, F1, 6>(wbase, code, nullptr, Mfma16{}, relu_epi(h1, a.h[0]));
+    run_step<step_of, F2, 8>(wbase, h1, bias, Mfma16{}, relu_epi(h2, a.h[1]));
+    run_step<step_of, F3, 8>(wbase, h2, bias + 128, Mfma16{}, relu_epi(h1, a.h[2]));
+    run_step<step_of, F4, 8>(wbase, h1, nullptr, Mfma16{}, [&](auto, f32x16 acc) {
       if (live && half == 0) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -211,10 +156,8 @@ __global__ void __launch_bounds__(kThreads) fwd_kernel(const Args a) {
 __global__ void __launch_bounds__(kThreads) dgrad_kernel(const Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
-  for (int i = tid; i < kBwdLds / 16; i += kThreads)
-    reinterpret_cast<uint4*>(smem)[i] = reinterpret_cast<const uint4*>(a.packed + kBwd0 * 1024)[i];
+  const char* wbase = resident_weights<kThreads>(smem, a.packed, kBwd0, kBwdN, tid, lane);
   __syncthreads();
-  const char* wbase = smem + lane * 16 - kBwd0 * 1024;
   const int64_t n_tiles = a.n_pad / kTile;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const int64_t n = (tile * kWaves + wave) * 32 + col;
@@ -228,19 +171,20 @@ __global__ void __launch_bounds__(kThreads) dgrad_kernel(const Args a) {
     }
     // d h_k -> dz_k = d h_k [h_k > 0] (stored activations), bf16 operand of the next transposed layer + image for the wgrad
     auto mask_epi = [&](bf16x8* out, const __bf16* h, __bf16* dz) {
-      return [=](int m, f32x16 acc) {
+      return [=](auto mc, f32x16 acc) {
+        constexpr int m = decltype(mc)::value;
         float hv[16];
-        load_rows(h, n, m, half, hv);
+        sample_chain::load_rows(h, kHid, n, m, half, hv);
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = hv[r] > 0.0f ? acc[r] : 0.0f;
         acc_to_operand(acc, out[2 * m], out[2 * m + 1]);
-        store_rows(dz, n, m, half, acc);
+        sample_chain::store_rows(dz, kHid, n, m, half, out[2 * m], out[2 * m + 1]);
       };
     };
     bf16x8 g3[8], g2[8], g1[8];
-    run<B4t, 1>(wbase, small, nullptr, MfmaBf{}, mask_epi(g3, a.h[2], a.dz[2]));
-    run<B3t, 8>(wbase, g3, nullptr, MfmaBf{}, mask_epi(g2, a.h[1], a.dz[1]));
-    run<B2t, 8>(wbase, g2, nullptr, MfmaBf{}, mask_epi(g1, a.h[0], a.dz[0]));
+    run_step<step_of, B4t, 1>(wbase, small, nullptr, MfmaBf{}, mask_epi(g3, a.h[2], a.dz[2]));
+    run_step<step_of, B3t, 8>(wbase, g3, nullptr, MfmaBf{}, mask_epi(g2, a.h[1], a.dz[1]));
+    run_step<step_of, B2t, 8>(wbase, g2, nullptr, MfmaBf{}, mask_epi(g1, a.h[0], a.dz[0]));
     (void)g1;
   }
 }
@@ -343,11 +287,10 @@ static Layout layout(int64_t n) {
   s.n_pad = (n + kTile - 1) / kTile * kTile;
   const size_t np = (size_t)s.n_pad;
   size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
-  s.code = take(np * kCodeLd * 2);
-  for (int k = 0; k < 3; ++k) s.h[k] = take(np * kHid * 2);
-  for (int k = 0; k < 3; ++k) s.dz[k] = take(np * kHid * 2);
-  s.slab = take((size_t)kMaxChunks * kParams * 4);
+  s.code = take(&o, np * kCodeLd * 2);
+  for (int k = 0; k < 3; ++k) s.h[k] = take(&o, np * kHid * 2);
+  for (int k = 0; k < 3; ++k) s.dz[k] = take(&o, np * kHid * 2);
+  s.slab = take(&o, (size_t)kMaxChunks * kParams * 4);
   s.total = o;
   return s;
 }

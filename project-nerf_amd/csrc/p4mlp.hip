@@ -12,8 +12,8 @@
 //     x_c   = x + dx                                                                             (core.py:341)
 //   canonical chain: InstantNeRFDecoder on [hash(x_c) (32) | tcode (21)] and the direction code  (core.py:344-349)
 //
-// Same register chain as imlp.hip / the 8x256 decoder (mlp_chain.h): 32 samples per wave on the MFMA column,
-// accumulator tiles -> 16-bit B fragments, all weight fragments resident in LDS.  The FORWARD chains contract fp16
+// The resident-weight register chain of resident_chain.h (step runner, LDS prologue, epilogues, pack loop); the canonical
+// chain's two kernel bodies are imlp.hip's (instant_chain_body.h) under this file's policy.  The FORWARD chains contract fp16
 // operands (v_mfma_f32_32x32x16_f16, what tinycudann's FullyFusedMLP computes in): delta_x moves x_canonical inside a
 // hash grid whose finest cells are 4e-4 wide, and bf16's 8 mantissa bits put ~1e-3 of rounding on a displacement of
 // 0.2 -- several cells; fp16 keeps it below one.  The backward chains and the training images stay bf16 (gradients span
@@ -26,19 +26,19 @@
 //   S1 [64,64] S2 [16,64]                                   decoder.sigma_net.params       (cols: 32 hash | 21 tcode | pad)
 //   C1 [64,48] C2 [64,64] C3 [16,64]                        decoder.color_net.params
 //   scale [1]                                               deform_decoder.displacement_scale
-#include "mlp_chain.h"
+#include "instant_chain_body.h"
 #include "mlp_wgrad.h"
 
 namespace nerf {
 namespace p4 {
+using namespace resident;
 
 constexpr int kT1W = 0, kT1b = 1344, kT2W = 1408, kT2b = 5504, kD1 = 5568, kD2 = 11712, kD3 = 15808;
 constexpr int kS1 = 16832, kS2 = 20928, kC1 = 21952, kC2 = 25024, kC3 = 29120, kScale = 30144, kParams = 30145;
 constexpr int kTimeDim = 21, kHashDeform = 24, kDirDim = 27;
 constexpr int kThreads = 256, kTile = 128;
+static_assert(kThreads == kInstantThreads && kTile == kInstantTile, "the canonical chain runs instant_chain_body.h's geometry");
 
-// (m-tiles, k-steps fed by the previous step's accumulators, natural-order k-steps, first fragment)
-struct Step { int mt, ks_acc, ks_nat, frag0; };
 enum { T1, T2, D1, D2, D3, D3t, D2t, D1tT, D1tH, T2t, S1, S2, C1, C2, C3, C3t, C2t, C1t, S2t, S1t, kSteps };
 constexpr Step step_of(int s) {
   switch (s) {
@@ -97,28 +97,9 @@ __device__ __forceinline__ int src_of(int step, int row, int k, bool nat) {
 }
 
 __global__ void __launch_bounds__(256) pack_kernel(const float* __restrict__ params, char* __restrict__ packed) {
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < kFrags * 64; t += gridDim.x * blockDim.x) {
-    const int frag = t >> 6, lane = t & 63;
-    int step = 0;
-    for (int s = 0; s < kSteps; ++s) if (frag >= step_of(s).frag0) step = s;
-    const Step st = step_of(step);
-    const int ksn = st.ks_acc + st.ks_nat, rel = frag - st.frag0, mt = rel / ksn, ks = rel % ksn;
-    const int row = mt * 32 + (lane & 31), h = lane >> 5;
-    const bool nat = ks >= st.ks_acc;
-    const bool fwd = step <= D3 || (step >= S1 && step <= C3);       // forward chains: fp16 fragments; backward: bf16
-    unsigned short out[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int k = nat ? 16 * (ks - st.ks_acc) + 8 * h + j : 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
-      const int src = src_of(step, row, k, nat);
-      const float v = src >= 0 ? params[src] : 0.0f;
-      out[j] = fwd ? __builtin_bit_cast(unsigned short, (_Float16)v) : __builtin_bit_cast(unsigned short, (__bf16)v);
-    }
-    uint4 bits;
-    bits.x = out[0] | ((unsigned)out[1] << 16); bits.y = out[2] | ((unsigned)out[3] << 16);
-    bits.z = out[4] | ((unsigned)out[5] << 16); bits.w = out[6] | ((unsigned)out[7] << 16);
-    *reinterpret_cast<uint4*>(packed + (size_t)frag * 1024 + lane * 16) = bits;
-  }
+  // forward chains: fp16 fragments; backward: bf16
+  pack_fragments(params, packed, kFrags, kSteps, step_of, src_of, [](int step) { return step <= D3 || (step >= S1 && step <= C3); },
+                 blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
   if (blockIdx.x == 0 && threadIdx.x < 64) reinterpret_cast<float*>(packed + kPackBiasOff)[threadIdx.x] = params[kT2b + threadIdx.x];
 }
 
@@ -157,51 +138,6 @@ __device__ __forceinline__ void cast_values(const float (&v)[KS][8], f16x8 (&h)[
   for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
     for (int j = 0; j < 8; ++j) { h[ks][j] = (_Float16)v[ks][j]; b[ks][j] = (__bf16)v[ks][j]; }
-}
-
-template <int STEP, int KS, class Epi>
-__device__ __forceinline__ void run16(const char* wbase, const f16x8 (&b)[KS], Epi&& epi) {
-  constexpr Step st = step_of(STEP);
-  static_assert(KS == st.ks_acc + st.ks_nat, "k-steps");
-  static_for<st.mt>([&](auto mc) {
-    constexpr int m = decltype(mc)::value;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    acc = mtile<KS>(wbase, st.frag0 + m * KS, b, acc, Mfma16{});
-    epi(mc, acc);
-  });
-}
-__device__ __forceinline__ void acc_to_operand16(const f32x16& acc, f16x8& lo, f16x8& hi) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { lo[j] = (_Float16)acc[j]; hi[j] = (_Float16)acc[8 + j]; }
-}
-__device__ __forceinline__ f16x8 load_nat16(const __bf16* img, int64_t wt, int n_ks, int ks, int col, int half) {
-  return *reinterpret_cast<const f16x8*>(reinterpret_cast<const char*>(img) + ((wt * n_ks + ks) * 64 + 2 * col + half) * 16);
-}
-
-template <int STEP, int KS, class Epi>
-__device__ __forceinline__ void run(const char* wbase, const bf16x8 (&b)[KS], Epi&& epi) {
-  constexpr Step st = step_of(STEP);
-  static_assert(KS == st.ks_acc + st.ks_nat, "k-steps");
-  static_for<st.mt>([&](auto mc) {
-    constexpr int m = decltype(mc)::value;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    acc = mtile<KS>(wbase, st.frag0 + m * KS, b, acc);
-    epi(mc, acc);
-  });
-}
-
-__device__ __forceinline__ bf16x8 load_nat(const __bf16* img, int64_t wt, int n_ks, int ks, int col, int half) {
-  return *reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(img) + ((wt * n_ks + ks) * 64 + 2 * col + half) * 16);
-}
-// the two B fragments of m-tile m of a blocked image (what stash_block wrote)
-__device__ __forceinline__ void load_block(const __bf16* img, int64_t wt, int n_mtiles, int m, int col, int half, bf16x8& lo, bf16x8& hi) {
-  const char* p = reinterpret_cast<const char*>(img) + (wt * n_mtiles + m) * 2048 + block_lane_offset(col, half);
-  lo = *reinterpret_cast<const bf16x8*>(p);
-  hi = *reinterpret_cast<const bf16x8*>(p + 128);
 }
 
 struct DeformArgs {
@@ -247,12 +183,10 @@ template <bool TRAIN>
 __global__ void __launch_bounds__(kThreads) deform_fwd_kernel(const DeformArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
-  for (int i = tid; i < kDeformFwdN * 64; i += kThreads)
-    reinterpret_cast<uint4*>(smem)[i] = reinterpret_cast<const uint4*>(a.packed + kDeformFwd0 * 1024)[i];
+  const char* wbase = resident_weights<kThreads>(smem, a.packed, kDeformFwd0, kDeformFwdN, tid, lane);
   float* bias_lds = reinterpret_cast<float*>(smem + kDeformFwdN * 1024);
   if (tid < 64) bias_lds[tid] = reinterpret_cast<const float*>(a.packed + kPackBiasOff)[tid];
   __syncthreads();
-  const char* wbase = smem + lane * 16 - kDeformFwd0 * 1024;
   const float scale = a.params[kScale];
   const int64_t n_tiles = a.n_pad / kTile;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -268,36 +202,16 @@ __global__ void __launch_bounds__(kThreads) deform_fwd_kernel(const DeformArgs a
       cast_values<2>(v, tc, tc_b);
     }
     uint32_t mw[3] = {0, 0, 0};
-    // relu epilogue: fp16 operand of the next step; training: bf16 image of the same values for the weight-gradient pass
-    auto relu_epi = [&](f16x8* out, __bf16* stash, int layer) {
-      return [=, &mw](auto mc, f32x16 acc) {
-        constexpr int m = decltype(mc)::value;
-        uint32_t bits = 0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { bits |= (acc[r] > 0.0f ? 1u : 0u) << r; acc[r] = fmaxf(acc[r], 0.0f); }
-        mw[layer] |= bits << (16 * m);
-        acc_to_operand16(acc, out[2 * m], out[2 * m + 1]);
-        if constexpr (TRAIN) {
-          bf16x8 lo, hi;
-          acc_to_operand(acc, lo, hi);
-          stash_block(stash, wt, 2, m, col, half, lo, hi);
-        }
-      };
-    };
     // ---- time modulation (decoders.py:368-371) ----
     f16x8 ht1[4], tm[4];
-    run16<T1, 2>(wbase, tc, relu_epi(ht1, a.ht1, 0));
-    run16<T2, 4>(wbase, ht1, [&](auto mc, f32x16 acc) {
+    run_step<step_of, T1, 2>(wbase, tc, nullptr, Mfma16{}, relu_epilogue<TRAIN>(ht1, a.ht1, mw[0], wt, col, half));
+    run_step<step_of, T2, 4>(wbase, ht1, nullptr, Mfma16{}, [&](auto mc, f32x16 acc) {
       constexpr int m = decltype(mc)::value;
       const f32x16 b = bias_tile(bias_lds, 32 * m, half);
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 1.0f / (1.0f + __expf(-(acc[r] + b[r])));
       acc_to_operand16(acc, tm[2 * m], tm[2 * m + 1]);
-      if constexpr (TRAIN) {
-        bf16x8 lo, hi;
-        acc_to_operand(acc, lo, hi);
-        stash_block(a.tm, wt, 2, m, col, half, lo, hi);
-      }
+      if constexpr (TRAIN) stash_tile(a.tm, wt, 2, m, col, half, acc, tm[2 * m], tm[2 * m + 1]);
     });
     // ---- tri-grid blend (core.py:313-336) ----
     float w[3];
@@ -307,8 +221,8 @@ __global__ void __launch_bounds__(kThreads) deform_fwd_kernel(const DeformArgs a
     bf16x8 df_b[2];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      const f16x8 f0 = load_nat16(a.feat[0], wt, 2, ks, col, half), f1 = load_nat16(a.feat[1], wt, 2, ks, col, half),
-                  f2 = load_nat16(a.feat[2], wt, 2, ks, col, half);
+      const f16x8 f0 = load_nat<f16x8>(a.feat[0], wt, 2, ks, col, half), f1 = load_nat<f16x8>(a.feat[1], wt, 2, ks, col, half),
+                  f2 = load_nat<f16x8>(a.feat[2], wt, 2, ks, col, half);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const bool valid = 16 * ks + 8 * half + j < kHashDeform;      // the hash forward leaves features 24..31 unwritten
@@ -328,10 +242,10 @@ __global__ void __launch_bounds__(kThreads) deform_fwd_kernel(const DeformArgs a
     f16x8 hd1[4], hd2[4];
     {
       f16x8 cat[6] = {tm[0], tm[1], tm[2], tm[3], df[0], df[1]};
-      run16<D1, 6>(wbase, cat, relu_epi(hd1, a.hd1, 1));
+      run_step<step_of, D1, 6>(wbase, cat, nullptr, Mfma16{}, relu_epilogue<TRAIN>(hd1, a.hd1, mw[1], wt, col, half));
     }
-    run16<D2, 4>(wbase, hd1, relu_epi(hd2, a.hd2, 2));
-    run16<D3, 4>(wbase, hd2, [&](auto, f32x16 acc) {
+    run_step<step_of, D2, 4>(wbase, hd1, nullptr, Mfma16{}, relu_epilogue<TRAIN>(hd2, a.hd2, mw[2], wt, col, half));
+    run_step<step_of, D3, 4>(wbase, hd2, nullptr, Mfma16{}, [&](auto, f32x16 acc) {
       if (live && half == 0) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -349,10 +263,8 @@ __global__ void __launch_bounds__(kThreads) deform_fwd_kernel(const DeformArgs a
 __global__ void __launch_bounds__(kThreads) deform_bwd_kernel(const DeformArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
-  for (int i = tid; i < kDeformBwdN * 64; i += kThreads)
-    reinterpret_cast<uint4*>(smem)[i] = reinterpret_cast<const uint4*>(a.packed + kDeformBwd0 * 1024)[i];
+  const char* wbase = resident_weights<kThreads>(smem, a.packed, kDeformBwd0, kDeformBwdN, tid, lane);
   __syncthreads();
-  const char* wbase = smem + lane * 16 - kDeformBwd0 * 1024;
   const float scale = a.params[kScale];
   float gscale_local = 0.0f, amax = 0.0f;
   const int64_t n_tiles = a.n_pad / kTile;
@@ -368,27 +280,14 @@ __global__ void __launch_bounds__(kThreads) deform_bwd_kernel(const DeformArgs a
         if (half == 0) gscale_local += d * a.raw[n * 3 + c];
       }
     }
-    bf16x8 small;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) small[j] = (__bf16)0.0f;
-    if (half == 0) { small[0] = (__bf16)g[0]; small[1] = (__bf16)g[1]; small[2] = (__bf16)g[2]; }
+    const bf16x8 small = small_operand(g[0], g[1], g[2], half);
     stash_nat(a.dsmall, wt, 1, 0, col, half, small);
     const uint4 mask = a.mask[tile * kThreads + tid];
-    auto grad_epi = [&](bf16x8* out, __bf16* stash, uint32_t bits32) {
-      return [=](auto mc, f32x16 acc) {
-        constexpr int m = decltype(mc)::value;
-        const uint32_t bits = bits32 >> (16 * m);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = (bits >> r) & 1u ? acc[r] : 0.0f;
-        acc_to_operand(acc, out[2 * m], out[2 * m + 1]);
-        stash_block(stash, wt, 2, m, col, half, out[2 * m], out[2 * m + 1]);
-      };
-    };
     bf16x8 gd2[4], gd1[4], gt2[4], gt1[4];
-    { bf16x8 in[1] = {small}; run<D3t, 1>(wbase, in, grad_epi(gd2, a.dzd2, mask.z)); }
-    run<D2t, 4>(wbase, gd2, grad_epi(gd1, a.dzd1, mask.y));
+    { bf16x8 in[1] = {small}; run_step<step_of, D3t, 1>(wbase, in, nullptr, MfmaBf{}, grad_epilogue(gd2, a.dzd2, mask.z, wt, col, half)); }
+    run_step<step_of, D2t, 4>(wbase, gd2, nullptr, MfmaBf{}, grad_epilogue(gd1, a.dzd1, mask.y, wt, col, half));
     // d(tm) -> through the sigmoid: d(tm_pre) = d(tm) tm (1 - tm), with the stashed (bf16) gate values
-    run<D1tT, 4>(wbase, gd1, [&](auto mc, f32x16 acc) {
+    run_step<step_of, D1tT, 4>(wbase, gd1, nullptr, MfmaBf{}, [&](auto mc, f32x16 acc) {
       constexpr int m = decltype(mc)::value;
       bf16x8 lo, hi;
       load_block(a.tm, wt, 2, m, col, half, lo, hi);
@@ -401,7 +300,7 @@ __global__ void __launch_bounds__(kThreads) deform_bwd_kernel(const DeformArgs a
       stash_block(a.dzt2, wt, 2, m, col, half, gt2[2 * m], gt2[2 * m + 1]);
     });
     // d(df) -> the three grids, each weighted by its blend weight
-    run<D1tH, 4>(wbase, gd1, [&](auto, f32x16 acc) {
+    run_step<step_of, D1tH, 4>(wbase, gd1, nullptr, MfmaBf{}, [&](auto, f32x16 acc) {
       if (live) {
         const f32x4 w = *reinterpret_cast<const f32x4*>(a.wts + n * 4);
 #pragma unroll
@@ -424,7 +323,7 @@ __global__ void __launch_bounds__(kThreads) deform_bwd_kernel(const DeformArgs a
         }
       }
     });
-    run<T2t, 4>(wbase, gt2, grad_epi(gt1, a.dzt1, mask.x));
+    run_step<step_of, T2t, 4>(wbase, gt2, nullptr, MfmaBf{}, grad_epilogue(gt1, a.dzt1, mask.x, wt, col, half));
     (void)gt1;
   }
   // one atomic per workgroup (same-address float atomics retire one after the other in L2)
@@ -463,23 +362,22 @@ struct CanonArgs {
   float2* grad_lm;         // non-null: INSTEAD of d_feat, level-major gradients [16][n]
 };
 
-template <bool TRAIN>
-__global__ void __launch_bounds__(kThreads) canon_fwd_kernel(const CanonArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
-  for (int i = tid; i < kCanonFwdN * 64; i += kThreads)
-    reinterpret_cast<uint4*>(smem)[i] = reinterpret_cast<const uint4*>(a.packed + kCanonFwd0 * 1024)[i];
-  __syncthreads();
-  const char* wbase = smem + lane * 16 - kCanonFwd0 * 1024;
-  const int64_t n_tiles = a.n_pad / kTile;
-  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const int64_t wt = tile * 4 + wave, n = wt * 32 + col;
-    const bool live = n < a.n;
-    const int64_t nc = live ? n : a.n - 1;
-    f16x8 sin[4], denc[2];
+// what instant_chain_body.h needs to know of this decoder: fp16 forward operands with bf16 images of the same values, four natural
+// k-steps [hash (32) | tcode (21, zero pad)] into the sigma-net, gradients accumulated by the caller (nothing cleared here)
+struct CanonPolicy {
+  static constexpr StepFn step_of = p4::step_of;
+  static constexpr int S1 = p4::S1, S2 = p4::S2, C1 = p4::C1, C2 = p4::C2, C3 = p4::C3;
+  static constexpr int C3t = p4::C3t, C2t = p4::C2t, C1t = p4::C1t, S2t = p4::S2t, S1t = p4::S1t;
+  static constexpr int kFwd0 = kCanonFwd0, kFwdN = kCanonFwdN, kBwd0 = kCanonBwd0, kBwdN = kCanonBwdN;
+  static constexpr int kSigmaKs = 4;
+  static constexpr bool kZeroGrads = false, kFence = false;
+  using V = f16x8;
+  using Mfma = Mfma16;
+  template <bool TRAIN>
+  static __device__ __forceinline__ void operands(const CanonArgs& a, int64_t wt, int64_t nc, int col, int half, f16x8 (&sin)[4], f16x8 (&denc)[2]) {
     bf16x8 sin_b[4], denc_b[2];
-    sin[0] = load_nat16(a.hash_nat, wt, 2, 0, col, half);
-    sin[1] = load_nat16(a.hash_nat, wt, 2, 1, col, half);
+    sin[0] = load_nat<f16x8>(a.hash_nat, wt, 2, 0, col, half);
+    sin[1] = load_nat<f16x8>(a.hash_nat, wt, 2, 1, col, half);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -501,117 +399,20 @@ __global__ void __launch_bounds__(kThreads) canon_fwd_kernel(const CanonArgs a) 
       stash_nat(a.denc, wt, 2, 0, col, half, denc_b[0]);
       stash_nat(a.denc, wt, 2, 1, col, half, denc_b[1]);
     }
-    uint32_t mw[3] = {0, 0, 0};
-    auto relu_epi = [&](f16x8* out, __bf16* stash, int layer) {
-      return [=, &mw](auto mc, f32x16 acc) {
-        constexpr int m = decltype(mc)::value;
-        uint32_t bits = 0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { bits |= (acc[r] > 0.0f ? 1u : 0u) << r; acc[r] = fmaxf(acc[r], 0.0f); }
-        mw[layer] |= bits << (16 * m);
-        acc_to_operand16(acc, out[2 * m], out[2 * m + 1]);
-        if constexpr (TRAIN) {
-          bf16x8 lo, hi;
-          acc_to_operand(acc, lo, hi);
-          stash_block(stash, wt, 2, m, col, half, lo, hi);
-        }
-      };
-    };
-    f16x8 hs1[4], h16[2], hc1[4], hc2[4];
-    run16<S1, 4>(wbase, sin, relu_epi(hs1, a.hs1, 0));
-    float h0 = 0.0f;
-    run16<S2, 4>(wbase, hs1, [&](auto, f32x16 acc) {
-      h0 = acc[0];
-      acc_to_operand16(acc, h16[0], h16[1]);
-      if constexpr (TRAIN) {
-        bf16x8 lo, hi;
-        acc_to_operand(acc, lo, hi);
-        stash_block(a.h16, wt, 1, 0, col, half, lo, hi);
-      }
-    });
-    if (live && half == 0) {
-      const float x = h0 - 5.0f;                                     // decoders.py:153
-      a.sigma[n] = x > 20.0f ? x : log1pf(expf(x));
-    }
-    {
-      f16x8 cat[3] = {h16[0], denc[0], denc[1]};
-      run16<C1, 3>(wbase, cat, relu_epi(hc1, a.hc1, 1));
-    }
-    run16<C2, 4>(wbase, hc1, relu_epi(hc2, a.hc2, 2));
-    run16<C3, 4>(wbase, hc2, [&](auto, f32x16 acc) {
-      if (live && half == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) a.rgb[n * 3 + c] = 1.0f / (1.0f + __expf(-acc[c]));
-      }
-    });
-    if constexpr (TRAIN) a.mask[tile * kThreads + tid] = make_uint4(mw[0], mw[1], mw[2], 0);
   }
+};
+
+template <bool TRAIN>
+__global__ void __launch_bounds__(kThreads) canon_fwd_kernel(const CanonArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
+  instant_forward<CanonPolicy, TRAIN>(a, smem, tid, lane, wave, col, half);
 }
 
 __global__ void __launch_bounds__(kThreads) canon_bwd_kernel(const CanonArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
-  for (int i = tid; i < kCanonBwdN * 64; i += kThreads)
-    reinterpret_cast<uint4*>(smem)[i] = reinterpret_cast<const uint4*>(a.packed + kCanonBwd0 * 1024)[i];
-  __syncthreads();
-  const char* wbase = smem + lane * 16 - kCanonBwd0 * 1024;
-  const int64_t n_tiles = a.n_pad / kTile;
-  float amax = 0.0f;
-  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const int64_t wt = tile * 4 + wave, n = wt * 32 + col;
-    const bool live = n < a.n;
-    float g0 = 0.f, g1 = 0.f, g2 = 0.f, gs = 0.f;
-    if (live) {
-      const float r0 = a.rgb[n * 3 + 0], r1 = a.rgb[n * 3 + 1], r2 = a.rgb[n * 3 + 2];
-      g0 = a.d_rgb[n * 3 + 0] * r0 * (1.0f - r0);
-      g1 = a.d_rgb[n * 3 + 1] * r1 * (1.0f - r1);
-      g2 = a.d_rgb[n * 3 + 2] * r2 * (1.0f - r2);
-      gs = a.d_sigma[n] * -expm1f(-a.sigma[n]);                      // softplus' = 1 - exp(-softplus)
-    }
-    bf16x8 small;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) small[j] = (__bf16)0.0f;
-    if (half == 0) { small[0] = (__bf16)g0; small[1] = (__bf16)g1; small[2] = (__bf16)g2; }
-    stash_nat(a.dsmall, wt, 1, 0, col, half, small);
-    const uint4 mask = a.mask[tile * kThreads + tid];
-    auto grad_epi = [&](bf16x8* out, __bf16* stash, uint32_t bits32) {
-      return [=](auto mc, f32x16 acc) {
-        constexpr int m = decltype(mc)::value;
-        const uint32_t bits = bits32 >> (16 * m);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = (bits >> r) & 1u ? acc[r] : 0.0f;
-        acc_to_operand(acc, out[2 * m], out[2 * m + 1]);
-        stash_block(stash, wt, 2, m, col, half, out[2 * m], out[2 * m + 1]);
-      };
-    };
-    bf16x8 gc2[4], gc1[4], g16[2], gs1[4];
-    { bf16x8 in[1] = {small}; run<C3t, 1>(wbase, in, grad_epi(gc2, a.dzc2, mask.z)); }
-    run<C2t, 4>(wbase, gc2, grad_epi(gc1, a.dzc1, mask.y));
-    run<C1t, 4>(wbase, gc1, [&](auto, f32x16 acc) {
-      if (half == 0) acc[0] += gs;                                   // row 0 of h also feeds sigma
-      acc_to_operand(acc, g16[0], g16[1]);
-      stash_block(a.dzs2, wt, 1, 0, col, half, g16[0], g16[1]);
-    });
-    { bf16x8 in[1] = {g16[0]}; run<S2t, 1>(wbase, in, grad_epi(gs1, a.dzs1, mask.x)); }
-    run<S1t, 4>(wbase, gs1, [&](auto, f32x16 acc) {
-      if (live) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          f32x4 v = {acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
-          if (a.grad_lm != nullptr) {                                // levels 4q + 2 half, + 1
-            float2* lm = a.grad_lm + (int64_t)(4 * q + 2 * half) * a.n + n;
-            lm[0] = make_float2(v[0], v[1]);
-            lm[a.n] = make_float2(v[2], v[3]);
-          } else *reinterpret_cast<f32x4*>(a.d_feat + n * 32 + 8 * q + 4 * half) = v;
-        }
-        if (a.amax_bits != nullptr) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) amax = fmaxf(amax, fabsf(acc[r]));
-        }
-      }
-    });
-  }
-  if (a.amax_bits != nullptr) publish_amax_slots(amax, a.amax_bits);
+  instant_dgrad<CanonPolicy>(a, smem, tid, lane, wave, col, half);
 }
 
 // ------------------------------------------------------------------------------------------------ per-sample inputs
@@ -657,21 +458,20 @@ static Layout layout(int64_t n) {
   s.n_pad = (n + kTile - 1) / kTile * kTile;
   const size_t np = (size_t)s.n_pad;
   size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
-  for (int k = 0; k < 3; ++k) s.feat[k] = take(np * 32 * 2);
-  s.canon_nat = take(np * 32 * 2);
-  s.tc = take(np * 32 * 2); s.ht1 = take(np * 64 * 2); s.tm = take(np * 64 * 2); s.df = take(np * 32 * 2);
-  s.hd1 = take(np * 64 * 2); s.hd2 = take(np * 64 * 2); s.dmask = take((np / kTile) * kThreads * 16);
-  s.wts = take(np * 16); s.raw = take(np * 12);
-  s.dzt1 = take(np * 64 * 2); s.dzt2 = take(np * 64 * 2); s.dzd1 = take(np * 64 * 2); s.dzd2 = take(np * 64 * 2);
-  s.dsmall_d = take(np * 16 * 2);
-  for (int k = 0; k < 3; ++k) s.dfeat[k] = take(np * kHashDeform * 4);
-  s.sin_nat = take(np * 64 * 2); s.hs1 = take(np * 64 * 2); s.h16 = take(np * 32 * 2); s.denc = take(np * 32 * 2);
-  s.hc1 = take(np * 64 * 2); s.hc2 = take(np * 64 * 2); s.cmask = take((np / kTile) * kThreads * 16);
-  s.dzs1 = take(np * 64 * 2); s.dzs2 = take(np * 32 * 2); s.dzc1 = take(np * 64 * 2); s.dzc2 = take(np * 64 * 2);
-  s.dsmall_c = take(np * 16 * 2); s.dfeat_c = take(np * 32 * 4);
+  for (int k = 0; k < 3; ++k) s.feat[k] = take(&o, np * 32 * 2);
+  s.canon_nat = take(&o, np * 32 * 2);
+  s.tc = take(&o, np * 32 * 2); s.ht1 = take(&o, np * 64 * 2); s.tm = take(&o, np * 64 * 2); s.df = take(&o, np * 32 * 2);
+  s.hd1 = take(&o, np * 64 * 2); s.hd2 = take(&o, np * 64 * 2); s.dmask = take(&o, (np / kTile) * kThreads * 16);
+  s.wts = take(&o, np * 16); s.raw = take(&o, np * 12);
+  s.dzt1 = take(&o, np * 64 * 2); s.dzt2 = take(&o, np * 64 * 2); s.dzd1 = take(&o, np * 64 * 2); s.dzd2 = take(&o, np * 64 * 2);
+  s.dsmall_d = take(&o, np * 16 * 2);
+  for (int k = 0; k < 3; ++k) s.dfeat[k] = take(&o, np * kHashDeform * 4);
+  s.sin_nat = take(&o, np * 64 * 2); s.hs1 = take(&o, np * 64 * 2); s.h16 = take(&o, np * 32 * 2); s.denc = take(&o, np * 32 * 2);
+  s.hc1 = take(&o, np * 64 * 2); s.hc2 = take(&o, np * 64 * 2); s.cmask = take(&o, (np / kTile) * kThreads * 16);
+  s.dzs1 = take(&o, np * 64 * 2); s.dzs2 = take(&o, np * 32 * 2); s.dzc1 = take(&o, np * 64 * 2); s.dzc2 = take(&o, np * 64 * 2);
+  s.dsmall_c = take(&o, np * 16 * 2); s.dfeat_c = take(&o, np * 32 * 4);
   // option "deterministic": ordered sum of the displacement-scale gradient, partial tiles of the weight-gradient launches
-  s.sum_ws = take(ordered_sum_ws_words(1) * sizeof(unsigned)); s.slab = take(kSmallSlabBytes);
+  s.sum_ws = take(&o, ordered_sum_ws_words(1) * sizeof(unsigned)); s.slab = take(&o, kSmallSlabBytes);
   s.total = o;
   return s;
 }
@@ -784,15 +584,6 @@ extern "C" int nerf_p4_canon_fwd(const void* packed, void* workspace, const floa
   return check_launch("nerf_p4_canon_fwd");
 }
 
-static WgradJob make_job(const char* w, size_t a_off, int a_bytes, int mt_a, size_t b_off, int nt_acc, size_t bn_off, int nt_nat, int kind) {
-  WgradJob j{};
-  j.a = w + a_off; j.a_bytes = a_bytes; j.mt_a = mt_a;
-  if (nt_acc) { j.b_acc = w + b_off; j.b_acc_bytes = nt_acc * 2048; j.nt_acc = nt_acc; }
-  if (nt_nat) { j.b_nat = w + bn_off; j.b_nat_bytes = nt_nat * 2048; j.nt_nat = nt_nat; }
-  j.bias_nat_col = -1; j.kind = kind;
-  return j;
-}
-
 // Backward of the canonical chain: d_feat (workspace slot 7) = d loss / d hash features; the five weight gradients are
 // ACCUMULATED into grads_f32 (the caller zeroes the vector once per step: several passes -- data batch, regulariser
 // probes -- add into it)
@@ -812,10 +603,7 @@ extern "C" int nerf_p4_canon_bwd(const void* packed, void* workspace, const floa
   const char* w = static_cast<const char*>(workspace);
   WgradArgs wa{};
   { WgradJob j = make_job(w, l.dzs1, 4096, 2, 0, 0, l.sin_nat, 2, 12); j.w_off = kS1; j.w_ld = 64; j.o_valid = 64; j.nat_valid = 32 + kTimeDim; wa.jobs[0] = j; }
-  { WgradJob j = make_job(w, l.dzs2, 2048, 1, l.hs1, 2, 0, 0, 7); j.w_off = kS2; j.w_ld = 64; j.o_valid = 16; j.acc_valid = 64; wa.jobs[1] = j; }
-  { WgradJob j = make_job(w, l.dzc1, 4096, 2, l.h16, 1, l.denc, 1, 8); j.w_off = kC1; j.w_ld = 48; j.o_valid = 64; j.acc_valid = 16; j.nat_valid = kDirDim; j.nat_col0 = 16; wa.jobs[2] = j; }
-  { WgradJob j = make_job(w, l.dzc2, 4096, 2, l.hc1, 2, 0, 0, 7); j.w_off = kC2; j.w_ld = 64; j.o_valid = 64; j.acc_valid = 64; wa.jobs[3] = j; }
-  { WgradJob j = make_job(w, l.dsmall_c, 1024, 1, l.hc2, 2, 0, 0, 9); j.a_nat = 1; j.split_n = 1; j.w_off = kC3; j.w_ld = 64; j.o_valid = 3; j.acc_valid = 64; wa.jobs[4] = j; }
+  instant_common_jobs(wa, w, InstantImages{l.hs1, l.h16, l.denc, l.hc1, l.hc2, l.dzs2, l.dzc1, l.dzc2, l.dsmall_c}, kS2, kC1, kC2, kC3);
   wa.n_jobs = 5;
   if (options().deterministic)
     return wgrad_launch(wa, n, grads_f32, as_stream(stream), reinterpret_cast<float*>(const_cast<char*>(w) + l.slab), kSmallSlabBytes);

@@ -1,5 +1,5 @@
 // What the sample-major fused chains (p1fit.hip, p2chain.hip) share: the register chain's staging and tile loop, the
-// sample-axis weight-gradient job, the ordered chunk sum and the host-side chunking / workspace / launch helpers.
+// sample-axis weight-gradient job, the ordered chunk sum and the host-side chunking / launch helpers.
 //
 // The chain: 32 samples per wave on the MFMA column (v_mfma_f32_32x32x16_bf16), accumulator tiles -> bf16 B fragments of the next
 // step, ONE step's weight fragments at a time staged from the packed fragment image (L2) into LDS.  Each engine keeps its plan, its
@@ -178,12 +178,6 @@ static void chunking(int64_t n, int64_t* chunk, int64_t* chunks) {
   len = (len + kSub - 1) / kSub * kSub;
   *chunk = len;
   *chunks = (n + len - 1) / len;
-}
-// the next `bytes` of a workspace laid out from *o, every piece 256-byte aligned
-static size_t take(size_t* o, size_t bytes) {
-  const size_t at = *o;
-  *o += (bytes + 255) / 256 * 256;
-  return at;
 }
 template <class A>
 static int launch_chain(void (*kernel)(A), int grid, int threads, int lds, nerf_stream_t stream, const char* what, const A& args) {
