@@ -12,6 +12,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib, ops
+from .flat_engine import cosine_lr, render_chunks
 
 Tensor = torch.Tensor
 P = lambda t: None if t is None else t.data_ptr()
@@ -99,8 +100,7 @@ class DynamicEngine:
 
     def lr(self, mult: float = 1.0) -> float:
         """CosineAnnealingLR of a group whose initial rate is mult * learning_rate (run.py:1016-1021, 1684-1743)"""
-        base = self.lr0 * mult
-        return self.eta_min + (base - self.eta_min) * (1 + math.cos(math.pi * self.step_count / self.t_max)) / 2
+        return cosine_lr(self.lr0 * mult, self.eta_min, self.step_count, self.t_max)
 
     def _buf(self, name: str, nbytes: int) -> Tensor:
         """ONE grow-only byte buffer per use: the active-point count changes almost every step, a buffer per count would churn
@@ -150,12 +150,8 @@ class DynamicEngine:
                      bg: Optional[Tensor] = None) -> Tensor:
         """one view at one time, ``chunk`` (default RENDER_CHUNK) rays per render_rays call"""
         chunk = chunk or self.RENDER_CHUNK
-        shape = rays_o.shape[:-1]
-        o, d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
-        out = torch.empty(o.shape[0], 3, device=self.device)
-        for i in range(0, o.shape[0], chunk):
-            out[i:i + chunk] = self.render_rays(o[i:i + chunk], d[i:i + chunk], time.reshape(1, 1).to(self.device), n_samples, bg=bg)[0]
-        return out.view(*shape, 3)
+        return render_chunks(lambda o, d: self.render_rays(o, d, time.reshape(1, 1).to(self.device), n_samples, bg=bg), rays_o, rays_d, chunk,
+                             self.device)
 
 
 class GridEngine(DynamicEngine):

@@ -18,7 +18,8 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from . import ops
+from . import flat_params, ops
+from .flat_engine import LapSlots, ViewSlots, cosine_lr, render_chunks
 
 Tensor = torch.Tensor
 
@@ -26,15 +27,7 @@ Tensor = torch.Tensor
 def param_shapes():
     """(name, shape) of NeRFDecoder parameters in reference registration order
     (src/decoders.py:49-66; keys as in state_dict under the ``decoder.`` prefix)."""
-    out = []
-    for i in range(8):
-        k = 63 if i == 0 else (319 if i == 4 else 256)
-        out += [(f"pts_layers.{i}.weight", (256, k)), (f"pts_layers.{i}.bias", (256,))]
-    out += [("sigma_layer.weight", (1, 256)), ("sigma_layer.bias", (1,)),
-            ("feature_layer.weight", (256, 256)), ("feature_layer.bias", (256,)),
-            ("view_layer.weight", (128, 283)), ("view_layer.bias", (128,)),
-            ("rgb_layer.weight", (3, 128)), ("rgb_layer.bias", (3,))]
-    return out
+    return [(k, shape) for k, _, shape in flat_params.nerf_decoder_table("", 63, 27)]
 
 
 def default_init(seed: int = 0) -> Tensor:
@@ -50,18 +43,11 @@ def default_init(seed: int = 0) -> Tensor:
 
 
 def flatten_state_dict(sd: Dict[str, Tensor], prefix: str = "decoder.") -> Tensor:
-    return torch.cat([sd[prefix + k].reshape(-1).float() for k, _ in param_shapes()])
+    return flat_params.flatten(flat_params.nerf_decoder_table(prefix, 63, 27), sd)
 
 
 def unflatten(flat: Tensor, prefix: str = "decoder.") -> Dict[str, Tensor]:
-    out, off = {}, 0
-    for k, shape in param_shapes():
-        n = 1
-        for s in shape:
-            n *= s
-        out[prefix + k] = flat[off:off + n].view(shape)
-        off += n
-    return out
+    return flat_params.unflatten(flat_params.nerf_decoder_table(prefix, 63, 27), flat)
 
 
 class VanillaNerfEngine:
@@ -85,6 +71,8 @@ class VanillaNerfEngine:
         # per-step device scalars (loss, largest output-layer derivative): one fresh zeroed slot per step
         # out of a ring that is cleared once per lap, instead of a memset launch per step
         self._scalars = torch.zeros(2, 1024, device=self.device)
+        self._slots = LapSlots(self._scalars)
+        self._infer_stale = False
         self.repack()
 
     # -- weights ---------------------------------------------------------------
@@ -95,7 +83,7 @@ class VanillaNerfEngine:
         self._infer_stale = training_only
 
     def _inference_weights(self) -> Tensor:
-        if getattr(self, "_infer_stale", False):
+        if self._infer_stale:
             ops.mlp_pack(self.params, self.packed, which=2)
             self._infer_stale = False
         return self.packed
@@ -132,11 +120,7 @@ class VanillaNerfEngine:
         stash = self._buf("stash", ops.mlp_stash_bytes(n))
         rgb, sigma = ops.mlp_fwd(self.packed, rays_o, rays_d, z, stash)
         mark("fwd")
-        self._grad_calls = getattr(self, "_grad_calls", -1) + 1
-        slot = self._grad_calls % self._scalars.shape[1]
-        if slot == 0:
-            self._scalars.zero_()
-        loss, amax = self._scalars[0, slot:slot + 1], self._scalars[1, slot:slot + 1]
+        loss, amax = self._slots.take()
         # compositing + MSE + their backward in one kernel (run.py:324-337); it also hands the dgrad chain the
         # largest output-layer derivative, from which the e5m2 gradient images take their scale
         d_rgb, d_sigma, _ = ops.composite_mse_bwd(rgb.view(R, n_samples, 3), sigma.view(R, n_samples), z, rays_d, self.bg,
@@ -155,7 +139,7 @@ class VanillaNerfEngine:
             sync_grads(self.grads)            # RCCL all-reduce (sum); averaged by grad_scale in apply_gradients
         # a copy, not a view of the scalar ring: the ring is cleared every 1024 steps, a caller that keeps loss
         # tensors (to average them later) must not see them zeroed or overwritten
-        return loss[0].clone()
+        return LapSlots.keep(loss)
 
     def apply_gradients(self) -> None:
         self.step_count += 1
@@ -200,18 +184,15 @@ class VanillaNerfEngine:
 
     @torch.no_grad()
     def render_image(self, rays_o: Tensor, rays_d: Tensor, n_samples: int, chunk: int = 65536, n_fine: int = 0) -> Tensor:
-        shape = rays_o.shape[:-1]
-        o, d = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3)
         if n_fine == 0:
+            shape = rays_o.shape[:-1]
+            o, d = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3)
             # one launch chain over all chunks in one reused workspace (nerf_render_rays_fwd): chunking is a
             # property of the launch chain, not a Python loop with per-chunk allocations
             chunk = max(1, min(chunk, o.shape[0]))
             ws = self._buf("render", ops._lib.load().nerf_render_rays_workspace_bytes(chunk, n_samples))
             return ops.render_rays_fwd(self._inference_weights(), o, d, n_samples, self.near, self.far, self.bg, chunk, ws)[0].view(*shape, 3)
-        out = torch.empty(o.shape[0], 3, device=self.device)
-        for i in range(0, o.shape[0], chunk):
-            out[i:i + chunk] = self.render_rays_hierarchical(o[i:i + chunk], d[i:i + chunk], n_samples, n_fine)[0]
-        return out.view(*shape, 3)
+        return render_chunks(lambda o, d: self.render_rays_hierarchical(o, d, n_samples, n_fine), rays_o, rays_d, chunk, self.device)
 
 
 class InstantNgpEngine:
@@ -282,7 +263,8 @@ class InstantNgpEngine:
         self.step_count, self.world_size = 0, world_size
         self._scratch = ops.normsq_ws(self.device)
         self._net_scratch = ops.normsq_ws(self.device)
-        self._loss_ring = torch.zeros(65536, device=self.device)      # a step's loss is a VIEW of its slot: valid for the next 32768 steps
+        self._loss_ring = ViewSlots(torch.zeros(65536, 1, device=self.device))   # a step's loss is a VIEW of its slot: valid for the next 32768 steps
+        self._jitter_counter = -1
 
     # the decoder's shape-specific pieces (instant_shapes.InstantShapeEngine overrides them and _field)
     def _check_shape(self, cfg: dict) -> None:
@@ -304,13 +286,12 @@ class InstantNgpEngine:
         self.packed = ops.imlp_pack(self.net, self.packed)
 
     def _decoder_bwd(self, ws: Tensor, rgb: Tensor, sigma: Tensor, d_rgb: Tensor, d_sigma: Tensor, n: int, d_feat: Tensor) -> None:
-        P = lambda t: t.data_ptr()
+        P = ops._p
         ops._lib.check(ops._lib.load().nerf_imlp_bwd(P(self.packed), P(ws), P(rgb), P(sigma), P(d_rgb), P(d_sigma), n,
                                                      P(self.g_net), P(d_feat), ops._stream()), "nerf_imlp_bwd")
 
     def lr(self) -> float:
-        import math
-        return self.eta_min + (self.lr0 - self.eta_min) * (1 + math.cos(math.pi * self.step_count / self.t_max)) / 2
+        return cosine_lr(self.lr0, self.eta_min, self.step_count, self.t_max)
 
     def _gather_table(self) -> Tensor:
         """the table the forward gathers from: the fp16 copy, brought up to date if torch code wrote the fp32 one"""
@@ -357,7 +338,7 @@ class InstantNgpEngine:
         against the occupancy grid as it is now; prepare again after ``update_grid`` to use the new one."""
         jitter = None
         if u is None:                 # the jitter is drawn in the compaction kernel: no [R, S] tensor of uniforms
-            self._jitter_counter = getattr(self, "_jitter_counter", -1) + 1
+            self._jitter_counter += 1
             jitter = (self.seed, self._jitter_counter)
         return ops.sample_compact_async(rays_o, rays_d, self.near, self.far, n_samples, self.binary_grid, self.bound, u=u,
                                         jitter=jitter, first_ray=first_ray)
@@ -434,15 +415,10 @@ class InstantNgpEngine:
             if spec:
                 self.spec.begin(hws)               # (a launch only after a counted call: a speculative call leaves the header clean)
             rgb, sigma, ws = self._field(pts, dirs, True, hist_ws=hws if precount else None)
-            P = lambda t: t.data_ptr()
+            P = ops._p
             # a fresh zeroed loss slot per step out of a ring cleared half a lap ahead (no fill launch, no copy launch per step: the
             # returned loss is a view of the slot)
-            self._grad_calls = getattr(self, "_grad_calls", -1) + 1
-            ring = self._loss_ring.numel()
-            slot = self._grad_calls % ring
-            if slot % (ring // 2) == 0 and self._grad_calls > 0:
-                self._loss_ring[slot:slot + ring // 2].zero_()
-            loss = self._loss_ring[slot:slot + 1]
+            loss = self._loss_ring.take()
             d_rgb, d_sigma, _ = ops.composite_mse_bwd(rgb, sigma, z, rays_d, self.bg, target, loss, slots=slots)
             if precount or spec:
                 import ctypes
@@ -577,9 +553,4 @@ class InstantNgpEngine:
 
     @torch.no_grad()
     def render_image(self, rays_o: Tensor, rays_d: Tensor, n_samples: int, chunk: int = 200000) -> Tensor:
-        shape = rays_o.shape[:-1]
-        o, d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
-        out = torch.empty(o.shape[0], 3, device=self.device)
-        for i in range(0, o.shape[0], chunk):
-            out[i:i + chunk] = self.render_rays(o[i:i + chunk], d[i:i + chunk], n_samples)[0]
-        return out.view(*shape, 3)
+        return render_chunks(lambda o, d: self.render_rays(o, d, n_samples), rays_o, rays_d, chunk, self.device)

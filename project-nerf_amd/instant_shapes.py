@@ -16,16 +16,16 @@ keeps it on InstantNgpEngine.
 """
 from __future__ import annotations
 
-import math
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
+from . import ops
 from .decoders import tiny_mlp_init, tiny_mlp_shapes
 from .engine import InstantNgpEngine
 
 Tensor = torch.Tensor
-P = lambda t: None if t is None else t.data_ptr()
+P = ops._p
 
 HIDDEN = (32, 64, 128)
 MAX_LEVELS, MAX_L_DIR = 16, 4
@@ -124,7 +124,6 @@ class InstantShapeEngine(InstantNgpEngine):
         why = supported(cfg)
         if why is not None:
             raise NotImplementedError(f"the fused Instant shape chain is not compiled for {why}")
-        from . import ops
         self.shape = _shape(cfg)
         n = ops._lib.load().nerf_imlp_shape_param_count(*self.shape)
         if n != param_count(cfg):
@@ -141,7 +140,6 @@ class InstantShapeEngine(InstantNgpEngine):
             torch.random.set_rng_state(state)
 
     def _pack(self) -> None:
-        from . import ops
         lib = ops._lib.load()
         if self.packed is None:
             self.packed = torch.empty(lib.nerf_imlp_shape_packed_bytes(*self.shape), device=self.device, dtype=torch.uint8)
@@ -154,7 +152,6 @@ class InstantShapeEngine(InstantNgpEngine):
         self._pack()
 
     def _field(self, pts: Tensor, dirs: Tensor, train: bool, hist_ws: Optional[Tensor] = None):
-        from . import ops
         if hist_ws is not None:
             raise NotImplementedError("the precounted hash backward stays with the default shape")
         lib = ops._lib.load()
@@ -169,7 +166,6 @@ class InstantShapeEngine(InstantNgpEngine):
         return rgb, sigma, ws
 
     def _decoder_bwd(self, ws: Tensor, rgb: Tensor, sigma: Tensor, d_rgb: Tensor, d_sigma: Tensor, n: int, d_feat: Tensor) -> None:
-        from . import ops
         ops._lib.check(ops._lib.load().nerf_imlp_shape_bwd(P(self.packed), P(ws), P(rgb), P(sigma), P(d_rgb), P(d_sigma), n, *self.shape,
                                                            P(self.g_net), P(d_feat), ops._stream()), "nerf_imlp_shape_bwd")
 

@@ -36,6 +36,11 @@ def _p(t: Optional[Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _bg_rows(bg: Optional[Tensor]) -> int:
+    """rows of a background as the compositing kernels take it: 0 none, 1 one colour for every ray, else one per ray"""
+    return 0 if bg is None else (1 if bg.dim() == 1 else bg.shape[0])
+
+
 # --------------------------------------------------------------------------- a1-a3
 def sample_rays(rays_o: Tensor, rays_d: Tensor, near: float, far: float, n_samples: int,
                 u: Optional[Tensor] = None, want_points: bool = False):
@@ -225,22 +230,29 @@ def _compact_launch(lib, rays_o, rays_d, u, jitter, first_ray, R, n_samples, nea
 
 
 # --------------------------------------------------------------------------- a1-a4 fused
-def sample_compact(rays_o: Tensor, rays_d: Tensor, near: float, far: float, n_samples: int,
-                   binary_grid: Tensor, bound: float, u: Optional[Tensor] = None):
-    """z [R,S], slot_of_sample [R*S] (int32, -1 = skipped), pts [n_act,3], dirs [n_act,3].
-    One host read of the active count (the reference syncs at the same place: ``.any()`` and the
-    boolean-index gathers, renderer.py:309-323)."""
-    lib = _lib.load()
+def _compact_outputs(rays_o: Tensor, rays_d: Tensor, n_samples: int, binary_grid: Tensor, u: Optional[Tensor]):
+    """the checked inputs and the allocated outputs of sample_compact / sample_compact_async:
+    (rays_o, rays_d, grid, u, R, z [R,S], slots [R*S], pts [R*S,3], dirs [R*S,3]); pts and dirs are cut to the active count later"""
     rays_o, rays_d = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d")
     grid = _dev(binary_grid, "binary_grid", torch.bool)
     R = rays_o.shape[0]
     n = R * n_samples
     if u is not None:
         u = _dev(u, "u")
-    z = torch.empty(R, n_samples, device=rays_o.device)
-    slots = torch.empty(n, device=rays_o.device, dtype=torch.int32)
-    pts = torch.empty(max(n, 1), 3, device=rays_o.device)
-    dirs = torch.empty(max(n, 1), 3, device=rays_o.device)
+    dev = rays_o.device
+    z = torch.empty(R, n_samples, device=dev)
+    slots = torch.empty(n, device=dev, dtype=torch.int32)
+    pts, dirs = torch.empty(max(n, 1), 3, device=dev), torch.empty(max(n, 1), 3, device=dev)
+    return rays_o, rays_d, grid, u, R, z, slots, pts, dirs
+
+
+def sample_compact(rays_o: Tensor, rays_d: Tensor, near: float, far: float, n_samples: int,
+                   binary_grid: Tensor, bound: float, u: Optional[Tensor] = None):
+    """z [R,S], slot_of_sample [R*S] (int32, -1 = skipped), pts [n_act,3], dirs [n_act,3].
+    One host read of the active count (the reference syncs at the same place: ``.any()`` and the
+    boolean-index gathers, renderer.py:309-323)."""
+    lib = _lib.load()
+    rays_o, rays_d, grid, u, R, z, slots, pts, dirs = _compact_outputs(rays_o, rays_d, n_samples, binary_grid, u)
     count = torch.empty(1, device=rays_o.device, dtype=torch.int32)          # the call clears it
     _compact_launch(lib, rays_o, rays_d, u, None, 0, R, n_samples, near, far, grid, bound, z, slots, pts, dirs, count)
     n_act = int(count.item())
@@ -282,16 +294,7 @@ def sample_compact_async(rays_o: Tensor, rays_d: Tensor, near: float, far: float
     instead of being read from a [R, S] tensor of uniforms; ``first_ray``: these rays are rays [first_ray, first_ray + R)
     of a larger batch (data-parallel shards of one global batch draw the jitter one GPU would draw)."""
     lib = _lib.load()
-    rays_o, rays_d = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d")
-    grid = _dev(binary_grid, "binary_grid", torch.bool)
-    R = rays_o.shape[0]
-    n = R * n_samples
-    if u is not None:
-        u = _dev(u, "u")
-    dev = rays_o.device
-    z = torch.empty(R, n_samples, device=dev)
-    slots = torch.empty(n, device=dev, dtype=torch.int32)
-    pts, dirs = torch.empty(max(n, 1), 3, device=dev), torch.empty(max(n, 1), 3, device=dev)
+    rays_o, rays_d, grid, u, R, z, slots, pts, dirs = _compact_outputs(rays_o, rays_d, n_samples, binary_grid, u)
     count = _compact_launch(lib, rays_o, rays_d, u, jitter, first_ray, R, n_samples, near, far, grid, bound, z, slots, pts, dirs, None)
     if isinstance(count, tuple):                                       # chained form: (host block, seq) to poll
         import weakref
@@ -314,7 +317,7 @@ class _CompositeIndexed(torch.autograd.Function):
         out_rgb = torch.empty(R, 3, device=z.device)
         depth = torch.empty(R, device=z.device)
         acc = torch.empty(R, device=z.device)
-        bg_rows = 0 if bg is None else (1 if bg.dim() == 1 else bg.shape[0])
+        bg_rows = _bg_rows(bg)
         _lib.check(lib.nerf_composite_fwd_indexed(_p(rgb_c), _p(sigma_c), _p(slots), _p(z), _p(rays_d), _p(bg), bg_rows,
                                                   R, S, _p(out_rgb), _p(depth), _p(acc), _stream()),
                    "nerf_composite_fwd_indexed")
@@ -327,7 +330,7 @@ class _CompositeIndexed(torch.autograd.Function):
         rgb_c, sigma_c, slots, z, rays_d, bg = ctx.saved_tensors
         R, S = z.shape
         d_rgb, d_sigma = torch.empty_like(rgb_c), torch.empty_like(sigma_c)
-        bg_rows = 0 if bg is None else (1 if bg.dim() == 1 else bg.shape[0])
+        bg_rows = _bg_rows(bg)
         _lib.check(lib.nerf_composite_bwd_indexed(_p(rgb_c), _p(sigma_c), _p(slots), _p(z), _p(rays_d), _p(bg), bg_rows,
                                                   _p(g_rgb.contiguous()), _p(g_depth.contiguous()), _p(g_acc.contiguous()),
                                                   R, S, _p(d_rgb), _p(d_sigma), _stream()), "nerf_composite_bwd_indexed")
@@ -392,10 +395,8 @@ def composite_fwd(rgb: Tensor, sigma: Tensor, z: Tensor, rays_d: Tensor, bg: Opt
     lib = _lib.load()
     rgb, sigma, z, rays_d = _dev(rgb, "rgb"), _dev(sigma, "sigma"), _dev(z, "z"), _dev(rays_d, "rays_d")
     R, S = z.shape
-    bg_rows = 0
-    if bg is not None:
-        bg = _dev(bg, "bg")
-        bg_rows = 1 if bg.dim() == 1 else bg.shape[0]
+    bg = None if bg is None else _dev(bg, "bg")
+    bg_rows = _bg_rows(bg)
     out_rgb = torch.empty(R, 3, device=z.device, dtype=torch.float32)
     depth = torch.empty(R, device=z.device, dtype=torch.float32)
     acc = torch.empty(R, device=z.device, dtype=torch.float32)
@@ -414,10 +415,8 @@ def composite_bwd(rgb, sigma, z, rays_d, bg, extra, g_rgb, g_depth, g_acc, g_ext
     lib = _lib.load()
     rgb, sigma, z, rays_d = _dev(rgb, "rgb"), _dev(sigma, "sigma"), _dev(z, "z"), _dev(rays_d, "rays_d")
     R, S = z.shape
-    bg_rows = 0
-    if bg is not None:
-        bg = _dev(bg, "bg")
-        bg_rows = 1 if bg.dim() == 1 else bg.shape[0]
+    bg = None if bg is None else _dev(bg, "bg")
+    bg_rows = _bg_rows(bg)
     g_rgb = _dev(g_rgb, "g_rgb")
     g_depth = None if g_depth is None else _dev(g_depth, "g_depth")
     g_acc = None if g_acc is None else _dev(g_acc, "g_acc")
@@ -443,10 +442,8 @@ def composite_mse_bwd(rgb: Tensor, sigma: Tensor, z: Tensor, rays_d: Tensor, bg:
     lib = _lib.load()
     rgb, sigma, z, rays_d, target = _dev(rgb, "rgb"), _dev(sigma, "sigma"), _dev(z, "z"), _dev(rays_d, "rays_d"), _dev(target, "target")
     R, S = z.shape
-    bg_rows = 0
-    if bg is not None:
-        bg = _dev(bg, "bg")
-        bg_rows = 1 if bg.dim() == 1 else bg.shape[0]
+    bg = None if bg is None else _dev(bg, "bg")
+    bg_rows = _bg_rows(bg)
     d_rgb, d_sigma = torch.empty_like(rgb), torch.empty_like(sigma)
     pred = torch.empty(R, 3, device=z.device) if want_pred else None
     w = 1.0 / (3 * R) if loss_weight is None else loss_weight
@@ -536,10 +533,8 @@ def render_rays_fwd(packed: Tensor, rays_o: Tensor, rays_d: Tensor, n_samples: i
     need = lib.nerf_render_rays_workspace_bytes(chunk, n_samples)
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(need, device=rays_o.device, dtype=torch.uint8)
-    bg_rows = 0
-    if bg is not None:
-        bg = _dev(bg, "bg")
-        bg_rows = 1 if bg.dim() == 1 else bg.shape[0]
+    bg = None if bg is None else _dev(bg, "bg")
+    bg_rows = _bg_rows(bg)
     out = torch.empty(R, 3, device=rays_o.device)
     depth, acc = torch.empty(R, device=rays_o.device), torch.empty(R, device=rays_o.device)
     _lib.check(lib.nerf_render_rays_fwd(_p(packed), _p(rays_o), _p(rays_d), R, n_samples, float(near), float(far), _p(bg), bg_rows,

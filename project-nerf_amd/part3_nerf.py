@@ -20,7 +20,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import _lib, ops
+from . import _lib, flat_params, ops
 from . import part3 as p3
 from .dynamic_engine import DynamicEngine, clip_adamw_flat, composite_mse_reg_bwd, normsq_flat, sample_inputs
 
@@ -63,15 +63,7 @@ def supported_nerf(cfg: dict) -> Optional[str]:
 
 def decoder_shapes(prefix: str, code_dim: int):
     """(state-dict key, shape) of NeRFDecoder(pos_dim=code_dim, dir_dim=27) in registration order (src/decoders.py:37-66)"""
-    out = []
-    for layer in range(8):
-        k = code_dim if layer == 0 else (256 + code_dim if layer == 4 else 256)
-        out += [(f"{prefix}.pts_layers.{layer}.weight", (256, k)), (f"{prefix}.pts_layers.{layer}.bias", (256,))]
-    out += [(f"{prefix}.sigma_layer.weight", (1, 256)), (f"{prefix}.sigma_layer.bias", (1,)),
-            (f"{prefix}.feature_layer.weight", (256, 256)), (f"{prefix}.feature_layer.bias", (256,)),
-            (f"{prefix}.view_layer.weight", (128, 256 + DIR_DIM)), (f"{prefix}.view_layer.bias", (128,)),
-            (f"{prefix}.rgb_layer.weight", (3, 128)), (f"{prefix}.rgb_layer.bias", (3,))]
-    return out
+    return [(key, shape) for key, _, shape in flat_params.nerf_decoder_table(prefix + ".", code_dim, DIR_DIM)]
 
 
 def slice_table(cfg: dict):

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib, ops
 from .dynamic_engine import GridEngine, clip_adamw_flat, composite_mse_reg_bwd, normsq_flat, sample_inputs, wait_all
+from .flat_engine import ViewSlots
 
 Tensor = torch.Tensor
 P = lambda t: None if t is None else t.data_ptr()
@@ -293,7 +294,7 @@ class DualHashEngine(GridEngine):
         self.tv_disp = float(cfg.get("tv_displacement_weight", 0.001)) / 3.0 if cfg.get("use_tv_displacement", True) else 0.0
         self.tv_canon = float(cfg.get("tv_loss_weight", 1e-5))
         self._scalars = self._g_net_scalars[N_PARAMS:]
-        self._loss_ring, self._grad_calls = torch.zeros(32768, 2, device=self.device), -1
+        self._loss_ring = ViewSlots(torch.zeros(32768, 2, device=self.device))
         assert (3 * nd) % 4 == 0
         self._tv_codes = torch.empty((total + 3) // 4, dtype=torch.uint8, device=self.device)   # two-bit signs of the TV terms
         from .specbwd import SpeculativeScatter
@@ -362,12 +363,8 @@ class DualHashEngine(GridEngine):
         self._g_net_scalars.zero_()
         # a fresh zeroed (loss, regulariser) slot per step out of a ring cleared half a lap ahead: the returned loss is a VIEW of its
         # slot (valid for the next 16384 steps) -- no copy launch per step
-        self._grad_calls += 1
-        ring = self._loss_ring.shape[0]
-        slot = self._grad_calls % ring
-        if slot % (ring // 2) == 0 and self._grad_calls > 0:
-            self._loss_ring[slot:slot + ring // 2].zero_()
-        loss, reg = self._loss_ring[slot, 0:1], self._loss_ring[slot, 1:2]
+        row = self._loss_ring.take()
+        loss, reg = row[0:1], row[1:2]
         self.last_reg = reg[0]                 # displacement regulariser of this batch (times its weight), a view like the loss
         handles = []
         reduce = (lambda view: handles.append(sync_grads_async(view))) if sync_grads_async is not None else (lambda view: None)

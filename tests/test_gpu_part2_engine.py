@@ -332,6 +332,19 @@ def test_two_runs_give_the_same_bits():
     assert runs[0][1].abs().sum() > 0
 
 
+def test_loss_slot_across_a_lap_of_the_ring():
+    """RING + 1 gradient calls on the same inputs at the smallest compiled shape, 8 rays x 4 samples (one 32-sample wave tile):
+    the loss is an ordered sum into a slot that is zero when handed out, so call RING (slot 0 again, after the lap's clear)
+    gives the bits of call 0; and what was returned is a copy, so the tensors kept from calls 0 and 1 outlive that clear."""
+    R, S = 8, 4
+    o, d, target = rays(R, seed=4)
+    u = torch.rand(R, S, device="cuda")
+    eng = part2.Part2Engine(make_cfg(64, 2, 1, 64, 1, 0), device="cuda", seed=5)
+    kept = [eng.compute_gradients(o, d, target, S, u=u) for _ in range(eng.RING + 1)]
+    assert float(kept[0]) > 0.0 and torch.equal(kept[0], kept[eng.RING])
+    assert torch.equal(kept[1], kept[0])          # slot 1 was cleared by the lap and not yet written again
+
+
 def test_dead_density_gives_exactly_zero_gradients():
     R, S = 40, 32
     o, d, target = rays(R, seed=3)

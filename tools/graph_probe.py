@@ -20,7 +20,7 @@ t0 = time.perf_counter()
 for c in range(200): step(c)
 torch.cuda.synchronize()
 print(f"stream launches: {(time.perf_counter() - t0) / 200 * 1e3:.4f} ms/step")
-eng._grad_calls = 0            # slot 1 at capture: no conditional zero_ inside the graph
+eng._slots.calls = 1           # slot 1 at capture: no conditional zero_ inside the graph
 side = torch.cuda.Stream()
 side.wait_stream(torch.cuda.current_stream())
 with torch.cuda.stream(side):
