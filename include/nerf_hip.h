@@ -44,7 +44,8 @@ extern "C" {
 /* 5: the Part 1 image-fit chain entries nerf_p1_* are new. */
 /* 6: the vanilla NeRF decoder chain for non-default shapes, nerf_p2_*, is new. */
 /* 7: the Instant-NGP tiny-MLP chain for non-default shapes, nerf_imlp_shape_*, is new. */
-#define NERF_ABI_VERSION 7
+/* 8: the Instant-NGP evaluation launch chain, nerf_instant_render_*, is new. */
+#define NERF_ABI_VERSION 8
 
 typedef void* nerf_stream_t;
 
@@ -527,6 +528,41 @@ int nerf_render_rays_fwd(const void* packed, const float* rays_o, const float* r
                          int n_samples, float near_plane, float far_plane, const float* bg, int64_t bg_rows,
                          int64_t chunk_rays, void* workspace, float* out_rgb, float* out_depth, float* out_acc,
                          nerf_stream_t stream);
+
+/* ---- a1-a4 + a7 + a8 + a10 + a11: evaluation of the Instant-NGP field as one launch chain ------
+ * replaces render_rays(perturb=False) with a density_grid and render_image's chunk loop
+ * (src/renderer.py:240-384, 387-418) for mode part2_instant, the field query being src/core.py:354-359
+ * (hash encoding -> InstantNeRFDecoder).  Per chunk of `chunk_rays` rays, on the caller's stream:
+ * clear the count word -> nerf_sample_compact (plain depths) -> hash gather -> tiny-MLP chain ->
+ * nerf_composite_fwd_indexed.  The gather and the chain read the compaction's active count from DEVICE
+ * memory, so the host never does: no allocation, no host read, no event, no synchronisation; the whole
+ * frame can be captured in a hipGraph.  Results are bit-identical to the same five steps called one by
+ * one with the count read back (nerf_sample_compact, nerf_hash_encode_fwd_nat, nerf_imlp_fwd,
+ * nerf_composite_fwd_indexed): a sample's value does not depend on its compact slot.
+ *   imlp_packed: nerf_imlp_pack's image.  table_f32 / table_f16 (exactly one), n_levels (16: the
+ *   default-shape chain of nerf_imlp_fwd is the one wired) ... dense_host, hash_bound: as
+ *   nerf_hash_encode_fwd_nat.  binary_grid [res,res,res] bytes, grid_resolution <= 32768, grid_bound: as
+ *   nerf_sample_compact.  rays_o / rays_d [n_rays,3]; 2 <= n_samples <= 1024; bg / bg_rows as
+ *   nerf_composite_fwd (bg_rows in {1, n_rays}); chunk_rays * n_samples < 2^31.
+ *   workspace: nerf_instant_render_workspace_bytes(chunk_rays, n_samples) bytes, 256-byte aligned, contents
+ *   irrelevant.  With n = chunk_rays * n_samples, every piece rounded up to 256 bytes: 256 (the count word),
+ *   z n*4, slots n*4, pts n*12, dirs n*12, bf16 hash operand image roundup(n,128)*64, rgb n*12, sigma n*4
+ *   -- 112 bytes per sample (nerf_imlp_workspace_bytes' training layout, ~1 KB per sample, is not used).
+ *   The query returns 0 for non-positive arguments.  After the call the count word holds the LAST chunk's
+ *   active count.
+ * Semantics: a skipped sample contributes sigma = 0 and rgb = 0; a chunk without an active sample
+ * renders the background, depth 0 and acc 0.  One difference from the reference: its forced query of
+ * sample 0 of the first ray when nothing is active (src/renderer.py:309-311) keeps an autograd graph
+ * connected; there is no graph here and the step is not reproduced.  n_rays == 0 is a successful no-op. */
+size_t nerf_instant_render_workspace_bytes(int64_t chunk_rays, int n_samples);
+int nerf_instant_render_rays_fwd(const void* imlp_packed, const float* table_f32, const void* table_f16, int n_levels,
+                                 const float* scale_host, const unsigned* res_host, const unsigned* size_host,
+                                 const unsigned* offset_host, const unsigned* dense_host, float hash_bound,
+                                 const uint8_t* binary_grid, int grid_resolution, float grid_bound,
+                                 const float* rays_o, const float* rays_d, int64_t n_rays, int n_samples,
+                                 float near_plane, float far_plane, const float* bg, int64_t bg_rows,
+                                 int64_t chunk_rays, void* workspace, float* out_rgb, float* out_depth, float* out_acc,
+                                 nerf_stream_t stream);
 
 /* ---- a9 + a14: compositing fused with the MSE loss and its backward --------------------------
  * replaces, for one training step, volume_render (src/renderer.py:204-237), nn.MSELoss

@@ -58,6 +58,15 @@ Options& options();
 int device_cu_count(int* n_cu);
 int ensure_dynamic_lds(const void* kernel, int bytes, const char* what);
 
+// Launches whose sample count is a DEVICE word (the compaction's active count; at most `capacity`, which sizes the grids), for
+// render_instant.hip's launch chain: no host ever reads the count.  hashgrid.hip: bf16 operand image [roundup(capacity, 128), 32] of
+// the first *count points; imlp.hip: the inference decoder chain on that image.  Nothing is touched when *count is 0.
+int hash_fwd_counted(const float* pts, const unsigned* count, int64_t capacity, const float* table_f32, const void* table_f16,
+                     int n_levels, const float* scale_host, const unsigned* res_host, const unsigned* size_host,
+                     const unsigned* offset_host, const unsigned* dense_host, float bound, void* out_nat, nerf_stream_t stream);
+int imlp_fwd_counted(const void* packed, const void* hash_nat, const float* dirs, const unsigned* count, int64_t capacity, float* rgb,
+                     float* sigma, nerf_stream_t stream);
+
 #define NERF_REQUIRE(cond, ...) \
   do {                          \
     if (!(cond)) return ::nerf::fail(NERF_EINVAL, __VA_ARGS__); \

@@ -210,6 +210,43 @@ hash_fwd_kernel(const float* __restrict__ pts, int64_t n, int64_t n_pad, const T
   }
 }
 
+// hash_fwd_kernel's bf16 operand image with the point count read from DEVICE memory (nerf_instant_render_rays_fwd: the count is the
+// compaction's, which no host ever sees).  The launch is sized for `capacity` points; the loop bounds come from *count (clamped to the
+// capacity: a count the compaction cannot produce must not turn into a store outside the image).  Same corners, same gathers, same
+// eight-term sums in the same order, same rounding and operand address as hash_fwd_kernel; pad rows repeat point n - 1; no fp32
+// rows, corner indices, histogram or table set.  n == 0 leaves before n - 1 exists.
+template <class TableT>
+__global__ void __launch_bounds__(256)
+hash_fwd_counted_kernel(const float* __restrict__ pts, const unsigned* __restrict__ count, int64_t capacity,
+                        const TableT* __restrict__ table, HashLevels L, __bf16* __restrict__ out_nat, int n_chunks) {
+  int64_t n = (int64_t)*count;
+  if (n == 0) return;
+  n = n < capacity ? n : capacity;
+  const int64_t n_pad = (n + 127) / 128 * 128;
+  const LevelChunk lc = level_chunk(L.n_levels, n_chunks);
+  if (lc.lvl >= L.n_levels) return;
+  const int lvl = lc.lvl;
+  for (int64_t p = lc.chunk * (int64_t)blockDim.x + threadIdx.x; p < n_pad; p += (int64_t)lc.chunks * blockDim.x) {
+    const int64_t ps = p < n ? p : n - 1;
+    const Corner c = corners_of(L, lvl, pts[ps * 3 + 0], pts[ps * 3 + 1], pts[ps * 3 + 2]);
+    float f0 = 0.0f, f1 = 0.0f;
+    float2 v[8];
+    gather_cell(table, c, v);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {                           // the sums run over the corners in the reference's order
+      f0 += c.w[k] * v[k].x;
+      f1 += c.w[k] * v[k].y;
+    }
+    const int f = 2 * lvl, ks = f >> 4, h = (f >> 3) & 1, j = f & 7;
+    const int64_t wt = p >> 5;
+    const int col = (int)(p & 31);
+    const int n_ks = (2 * L.n_levels + 15) / 16;
+    __bf16* dst = out_nat + ((wt * n_ks + ks) * 64 + 2 * col + h) * 8 + j;
+    dst[0] = (__bf16)f0;
+    dst[1] = (__bf16)f1;
+  }
+}
+
 // d_feat [n, 2L] fp32 -> scatter into d_table [E, 2].  Level-major work split (blockIdx.y = level,
 // consecutive lanes = consecutive points, i.e. neighbouring samples of a ray): a wave's 64 x 16
 // float atomics then fall into ONE level's table, mostly into neighbouring cells, instead of 16
@@ -1237,6 +1274,32 @@ static int hash_fwd_impl(const float* pts, int64_t n, const float* table, const 
                        reinterpret_cast<const float2*>(table), L, out_f32, static_cast<__bf16*>(out_nat_bf16), idx_out, x.nat_f16,
                        hist_count, lb, n_chunks, x.ts);
   return check_launch("nerf_hash_encode_fwd");
+}
+
+// The operand-image forward for a point count that lives on the device (common.h; called by render_instant.hip, which has checked
+// its arguments): hash_fwd_impl's launch shape -- 2048-workgroup cap, XCD-aware placement, LDS throttle -- sized by the capacity.
+int nerf::hash_fwd_counted(const float* pts, const unsigned* count, int64_t capacity, const float* table_f32, const void* table_f16,
+                           int n_levels, const float* scale_host, const unsigned* res_host, const unsigned* size_host,
+                           const unsigned* offset_host, const unsigned* dense_host, float bound, void* out_nat, nerf_stream_t stream) {
+  NERF_REQUIRE(capacity > 0 && pts && count && out_nat && (table_f32 == nullptr) != (table_f16 == nullptr) && scale_host && res_host &&
+               size_host && offset_host && dense_host, "hash_fwd_counted: bad arguments");
+  HashLevels L;
+  if (int rc = fill_levels(L, LEVEL_ARGS); rc != NERF_OK) return rc;
+  const int64_t cap_pad = (capacity + 127) / 128 * 128;
+  int64_t blocks = (cap_pad + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  const int lds_kb = options().hash_fwd_lds_kb;                      // occupancy throttle, see hash_fwd_impl
+  const int lds = (lds_kb < 0 ? 0 : (lds_kb > 64 ? 64 : lds_kb)) * 1024;
+  const bool xcd = options().hash_xcd != 0;
+  const dim3 grid = level_chunk_grid(n_levels, blocks, xcd);
+  const int n_chunks = xcd ? (int)blocks : 0;
+  if (table_f16 != nullptr)
+    hipLaunchKernelGGL(hash_fwd_counted_kernel<half2_t>, grid, dim3(256), lds, as_stream(stream), pts, count, capacity,
+                       static_cast<const half2_t*>(table_f16), L, static_cast<__bf16*>(out_nat), n_chunks);
+  else
+    hipLaunchKernelGGL(hash_fwd_counted_kernel<float2>, grid, dim3(256), lds, as_stream(stream), pts, count, capacity,
+                       reinterpret_cast<const float2*>(table_f32), L, static_cast<__bf16*>(out_nat), n_chunks);
+  return check_launch("nerf_instant_render_rays_fwd (hash)");
 }
 
 extern "C" int nerf_hash_encode_fwd(const float* pts, int64_t n, const float* table, int n_levels,

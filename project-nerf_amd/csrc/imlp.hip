@@ -123,6 +123,21 @@ __global__ void __launch_bounds__(kIThreads) imlp_fwd_kernel(const IArgs a) {
   instant_forward<IPolicy, TRAIN>(a, smem, tid, lane, wave, col, half);
 }
 
+// The inference chain with the sample count read from DEVICE memory (nerf_instant_render_rays_fwd): the launch is sized for `capacity`
+// samples, the unchanged body runs on n = *count (clamped to the capacity) -- its tile loop strides, so surplus workgroups leave it
+// at once.  A count of 0 returns before a.n - 1 is formed; the test is uniform, so no barrier is left behind.
+__global__ void __launch_bounds__(kIThreads) imlp_fwd_counted_kernel(const IArgs a0, const unsigned* __restrict__ count, int64_t capacity) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  int64_t n = (int64_t)*count;
+  if (n == 0) return;
+  n = n < capacity ? n : capacity;
+  IArgs a = a0;
+  a.n = n;
+  a.n_pad = (n + kITile - 1) / kITile * kITile;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
+  instant_forward<IPolicy, false>(a, smem, tid, lane, wave, col, half);
+}
+
 __global__ void __launch_bounds__(kIThreads) imlp_bwd_kernel(const IArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
@@ -196,6 +211,20 @@ extern "C" int nerf_imlp_fwd(const void* packed, void* workspace, const float* d
   if (train) hipLaunchKernelGGL(imlp_fwd_kernel<true>, dim3(grid), dim3(kIThreads), kIFwdFrags * 1024, as_stream(stream), a);
   else hipLaunchKernelGGL(imlp_fwd_kernel<false>, dim3(grid), dim3(kIThreads), kIFwdFrags * 1024, as_stream(stream), a);
   return check_launch("nerf_imlp_fwd");
+}
+
+// inference on a device-side count (common.h; render_instant.hip's chain): only the operand image of the workspace layout exists
+int nerf::imlp_fwd_counted(const void* packed, const void* hash_nat, const float* dirs, const unsigned* count, int64_t capacity, float* rgb,
+                           float* sigma, nerf_stream_t stream) {
+  NERF_REQUIRE(capacity > 0 && packed && hash_nat && dirs && count && rgb && sigma, "imlp_fwd_counted: bad arguments");
+  IArgs a{};
+  a.packed = static_cast<const char*>(packed);
+  a.hash_nat = static_cast<const __bf16*>(hash_nat);
+  a.dirs = dirs; a.rgb = rgb; a.sigma = sigma;
+  const int grid = grid_for((capacity + kITile - 1) / kITile, 4);
+  if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_instant_render_rays_fwd: cannot query device");
+  hipLaunchKernelGGL(imlp_fwd_counted_kernel, dim3(grid), dim3(kIThreads), kIFwdFrags * 1024, as_stream(stream), a, count, capacity);
+  return check_launch("nerf_instant_render_rays_fwd (decoder)");
 }
 
 extern "C" int nerf_imlp_fwd_encoded(const void* packed, void* workspace, const float* x_enc, const float* d_enc, int64_t n,

@@ -230,6 +230,7 @@ class InstantNgpEngine:
         self.g_table = self._g_table_buf[:n_tab]
         self.g_net = torch.empty_like(self.net)
         self._hash_ws = None
+        self._chain_ws = {}            # render_image(chain=True): one workspace per (chunk, n_samples)
         # fp16 copy of the table for the forward gathers (tinycudann evaluates its grid from fp16 parameters next to
         # the fp32 master copy too): written by the optimiser kernel, refreshed here whenever torch code has
         # touched ``self.table`` in place (tensor version counter); cfg half_table: false keeps fp32 gathers
@@ -552,5 +553,20 @@ class InstantNgpEngine:
         return ops.composite_indexed(rgb, sigma, slots, z, rays_d, self.bg)
 
     @torch.no_grad()
-    def render_image(self, rays_o: Tensor, rays_d: Tensor, n_samples: int, chunk: int = 200000) -> Tensor:
+    def render_image(self, rays_o: Tensor, rays_d: Tensor, n_samples: int, chunk: int = 200000, chain: bool = False) -> Tensor:
+        """``chain=True``: the frame as ONE launch chain (nerf_instant_render_rays_fwd) -- the chunks' active counts stay on the
+        device, no host read and no allocation per chunk, one workspace kept per (chunk, n_samples); the same bits as the loop."""
+        if chain:
+            return self._render_image_chain(rays_o, rays_d, n_samples, chunk)
         return render_chunks(lambda o, d: self.render_rays(o, d, n_samples), rays_o, rays_d, chunk, self.device)
+
+    def _render_image_chain(self, rays_o: Tensor, rays_d: Tensor, n_samples: int, chunk: int) -> Tensor:
+        shape = rays_o.shape[:-1]
+        o, d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
+        chunk = max(1, min(int(chunk), max(o.shape[0], 1)))
+        ws = self._chain_ws.get((chunk, n_samples))
+        if ws is None:
+            ws = self._chain_ws[(chunk, n_samples)] = torch.empty(ops.instant_render_workspace_bytes(chunk, n_samples), dtype=torch.uint8, device=self.device)
+        rgb = ops.instant_render_rays_fwd(self.packed, self._gather_table(), self.levels, self.bound, self.binary_grid, self.bound, o, d,
+                                          n_samples, self.near, self.far, self.bg, chunk, workspace=ws)[0]
+        return rgb.view(*shape, 3)

@@ -42,7 +42,7 @@ def run_instant(cfg, args):
     import random
     from .core import NeuralField
     from .dataset import BlenderDataset
-    from .renderer import DensityGrid, render_rays
+    from .renderer import DensityGrid, render_rays, render_rays_instant_chain
     from .utils import compute_psnr, compute_psnr_torch
     if not args.data_dir:
         raise ValueError("Part 2 Instant requires --data_dir pointing to a NeRF dataset root.")
@@ -74,11 +74,19 @@ def run_instant(cfg, args):
         if grid is not None and "density_grid" in ckpt:
             grid.load_state_dict(ckpt["density_grid"])
 
+    # render_chain: true -- evaluation views through renderer.render_rays_instant_chain (default shape with an occupancy grid)
+    render_chain = bool(cfg.get("render_chain", False))
+    if render_chain and (grid is None or not model.decoder.fused or model.representation.n_features != 2 or model.representation.levels.n_levels != 16):
+        raise ValueError("render_chain: true needs use_density_grid and the default shape (16 levels x 2 features, hidden_dim 64)")
+
     def render_band(o, d):
         rows, width = o.shape[0], o.shape[1]
         o, d = o.reshape(-1, 3), d.reshape(-1, 3)
         if o.shape[0] == 0:
             return o.new_zeros(0, width, 3)
+        if render_chain:
+            # the band as one launch chain: no host read of the active count per chunk (renderer.render_rays_instant_chain)
+            return render_rays_instant_chain(model, o, d, near, far, render_n, grid, white_bkgd, chunk)[0].view(rows, width, 3)
         pred = torch.cat([render_rays(model, o[i:i + chunk], d[i:i + chunk], near, far, render_n, False,
                                       white_bkgd=white_bkgd, density_grid=grid)[0]
                           for i in range(0, o.shape[0], chunk)], 0)

@@ -169,5 +169,9 @@ class InstantShapeEngine(InstantNgpEngine):
         ops._lib.check(ops._lib.load().nerf_imlp_shape_bwd(P(self.packed), P(ws), P(rgb), P(sigma), P(d_rgb), P(d_sigma), n, *self.shape,
                                                            P(self.g_net), P(d_feat), ops._stream()), "nerf_imlp_shape_bwd")
 
+    def _render_image_chain(self, rays_o: Tensor, rays_d: Tensor, n_samples: int, chunk: int) -> Tensor:
+        raise NotImplementedError("render_image(chain=True): the evaluation launch chain (nerf_instant_render_rays_fwd) is wired for the "
+                                  "default shape's decoder kernel; the shape engine's chain is another kernel -- use chain=False")
+
     def enable_sharded_optimizer(self, rank: int) -> None:
         raise NotImplementedError("the sharded optimiser stays with the default shape's engine")

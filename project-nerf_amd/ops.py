@@ -983,6 +983,45 @@ def instant_decoder_encoded(net_params: Tensor, packed: Tensor, x_enc: Tensor, d
     return _InstantDecoderEncoded.apply(net_params, packed, x_enc, d_enc, train)
 
 
+def instant_render_workspace_bytes(chunk: int, n_samples: int) -> int:
+    return _lib.load().nerf_instant_render_workspace_bytes(chunk, n_samples)
+
+
+def instant_render_rays_fwd(packed: Tensor, table: Tensor, levels: HashLevelTable, hash_bound: float, binary_grid: Tensor,
+                            grid_bound: float, rays_o: Tensor, rays_d: Tensor, n_samples: int, near: float, far: float,
+                            bg: Optional[Tensor] = None, chunk: int = 65536, workspace: Optional[Tensor] = None):
+    """(rgb [R,3], depth [R], acc [R]) of the Instant-NGP field against an occupancy grid for any number of rays: one launch
+    chain over chunks of ``chunk`` rays in one reused workspace (nerf_instant_render_rays_fwd) -- the active count of a chunk
+    stays on the device, nothing is allocated or waited for between the launches.  ``table``: fp32 [entries, 2] or its fp16
+    copy; ``workspace``: uint8, at least instant_render_workspace_bytes(chunk, n_samples) bytes (allocated here otherwise);
+    its first int32 holds the last chunk's active count afterwards."""
+    lib = _lib.load()
+    rays_o, rays_d = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d")
+    grid = _dev(binary_grid, "binary_grid", torch.bool)
+    packed = _dev(packed, "packed", torch.uint8)
+    if not isinstance(table, Tensor) or table.dtype not in (torch.float32, torch.float16):
+        raise TypeError("instant_render_rays_fwd: table must be an fp32 or fp16 tensor")
+    half = table.dtype == torch.float16
+    table = _dev(table, "table", table.dtype)
+    if table.numel() < 2 * levels.entries:
+        raise ValueError(f"instant_render_rays_fwd: table of {table.numel()} values, the levels address {2 * levels.entries}")
+    R = rays_o.shape[0]
+    chunk = max(1, min(int(chunk), max(R, 1)))
+    need = lib.nerf_instant_render_workspace_bytes(chunk, n_samples)
+    if workspace is None:
+        workspace = torch.empty(need, device=rays_o.device, dtype=torch.uint8)
+    elif _dev(workspace, "workspace", torch.uint8).numel() < need:
+        raise ValueError(f"instant_render_rays_fwd: workspace of {workspace.numel()} bytes, {need} needed for chunk {chunk} x {n_samples}")
+    bg = None if bg is None else _dev(bg, "bg")
+    out = torch.empty(R, 3, device=rays_o.device)
+    depth, acc = torch.empty(R, device=rays_o.device), torch.empty(R, device=rays_o.device)
+    _lib.check(lib.nerf_instant_render_rays_fwd(_p(packed), None if half else _p(table), _p(table) if half else None, levels.n_levels,
+                                                *levels.host_args(), float(hash_bound), _p(grid), grid.shape[0], float(grid_bound),
+                                                _p(rays_o), _p(rays_d), R, n_samples, float(near), float(far), _p(bg), _bg_rows(bg), chunk,
+                                                _p(workspace), _p(out), _p(depth), _p(acc), _stream()), "nerf_instant_render_rays_fwd")
+    return out, depth, acc
+
+
 def instant_field(table: Tensor, net_params: Tensor, packed: Tensor, pts: Tensor, dirs: Tensor,
                   levels: HashLevelTable, bound: float):
     """rgb [n,3], sigma [n] for world-space points and unit view directions."""

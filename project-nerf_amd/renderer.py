@@ -166,6 +166,28 @@ def _render_rays_dynamic(model, rays_o, rays_d, near, far, n_samples, perturb, d
     return out_rgb, depth, acc
 
 
+@torch.no_grad()
+def render_rays_instant_chain(model, rays_o, rays_d, near, far, n_samples, density_grid, white_bkgd, chunk):
+    """(rgb [R,3], depth [R], acc [R]) of a part2_instant field against ``density_grid`` for any number of rays as ONE launch
+    chain (nerf_instant_render_rays_fwd): what a loop of ``render_rays(..., perturb=False, density_grid=...)`` over chunks of
+    ``chunk`` rays computes, bit for bit, without its per-chunk host read of the active count.  It gathers from the table
+    NeuralField.forward gathers from (the fp32 parameters).  One difference: a chunk without an active sample renders exactly the
+    background here; ``render_rays`` then queries sample 0 of its first ray to keep the autograd graph connected
+    (reference src/renderer.py:309-311), which has no meaning without a graph."""
+    if getattr(model, "mode", None) != "part2_instant":
+        raise ValueError(f"render_rays_instant_chain: mode {getattr(model, 'mode', None)!r} (serves part2_instant)")
+    rep, dec = model.representation, model.decoder
+    if not dec.fused or rep.n_features != 2 or rep.levels.n_levels != 16:
+        raise NotImplementedError("render_rays_instant_chain: the launch chain is wired for the default shape (16 levels x 2 features, "
+                                  "hidden_dim 64, L_embed_dir 4); use render_rays for another shape")
+    if density_grid is None:
+        raise ValueError("render_rays_instant_chain: a density_grid is required (render_rays serves the dense path)")
+    o, d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
+    bg = torch.ones(3, device=o.device) if white_bkgd else torch.zeros(3, device=o.device)
+    return ops.instant_render_rays_fwd(dec.packed_weights(), rep.table().detach(), rep.levels, rep.bound, density_grid.binary_grid,
+                                       density_grid.bound, o, d, n_samples, near, far, bg, chunk)
+
+
 def render_image(model, rays_o, rays_d, near, far, n_samples, chunk, white_bkgd):
     """reference src/renderer.py:387-418."""
     h, w = rays_o.shape[:2]
