@@ -45,7 +45,8 @@ extern "C" {
 /* 6: the vanilla NeRF decoder chain for non-default shapes, nerf_p2_*, is new. */
 /* 7: the Instant-NGP tiny-MLP chain for non-default shapes, nerf_imlp_shape_*, is new. */
 /* 8: the Instant-NGP evaluation launch chain, nerf_instant_render_*, is new. */
-#define NERF_ABI_VERSION 8
+/* 9: nerf_p4_infer_workspace_bytes, the evaluation size of the Part 4 workspace, is new. */
+#define NERF_ABI_VERSION 9
 
 typedef void* nerf_stream_t;
 
@@ -688,10 +689,14 @@ int nerf_clip_adamw_small(float* params, float* grads, float* exp_avg, float* ex
  * nerf_p4_workspace_offset(n, which): 0..2 nat images of the three deformation grids (write them with
  * nerf_hash_encode_fwd_nat(..., nat_dtype 1): the forward chains contract FP16 operands, as tinycudann's FullyFusedMLP
  * does; the backward chains and training images are bf16), 3 the canonical grid's; 4..6 d features [n,24] of the three deformation grids,
- * 7 d features [n,32] of the canonical grid (read them with nerf_hash_encode_bwd*). */
+ * 7 d features [n,32] of the canonical grid (read them with nerf_hash_encode_bwd*).
+ * Evaluation (train == 0 in nerf_p4_deform_fwd / nerf_p4_canon_fwd, no backward) reads and writes the four operand images
+ * alone, which lead the layout at the same offsets: a workspace of nerf_p4_infer_workspace_bytes(n) bytes
+ * (4 x roundup(n,128) x 64: 256 bytes per sample against ~2.9 KB) is enough for it; 0 for n <= 0. */
 int64_t nerf_p4_param_count(void);
 size_t nerf_p4_packed_bytes(void);
 size_t nerf_p4_workspace_bytes(int64_t n);
+size_t nerf_p4_infer_workspace_bytes(int64_t n);
 size_t nerf_p4_workspace_offset(int64_t n, int which);
 int nerf_p4_pack(const float* params_f32, void* packed, nerf_stream_t stream);
 /* per-sample inputs of the field (src/core.py:289-297): t' [n] = time of the sample's ray, x' [n,3] = its position; with

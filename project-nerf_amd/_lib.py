@@ -114,6 +114,7 @@ PROTOTYPES = {
     "nerf_p4_param_count": (i64, []),
     "nerf_p4_packed_bytes": (size_t, []),
     "nerf_p4_workspace_bytes": (size_t, [i64]),
+    "nerf_p4_infer_workspace_bytes": (size_t, [i64]),
     "nerf_p4_workspace_offset": (size_t, [i64, i32]),
     "nerf_p4_pack": (i32, [c_ptr, c_ptr, c_ptr]),
     "nerf_p4_sample_inputs": (i32, [c_ptr, c_ptr, c_ptr, i64, i32, f32, f32, ctypes.c_uint64, ctypes.c_uint64, i64, c_ptr, c_ptr, c_ptr]),
@@ -165,7 +166,7 @@ PROTOTYPES = {
     "nerf_adamw_clip_step_shadow": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, i64, i32, f32, f32, f32, f32, f32, c_ptr, f32, f32, c_ptr, c_ptr]),
 }
 
-ABI_VERSION = 8      # the NERF_ABI_VERSION of include/nerf_hip.h this table was written against
+ABI_VERSION = 9      # the NERF_ABI_VERSION of include/nerf_hip.h this table was written against
 
 _lib = None
 

@@ -514,6 +514,8 @@ using namespace nerf::p4;
 extern "C" int64_t nerf_p4_param_count(void) { return kParams; }
 extern "C" size_t nerf_p4_packed_bytes(void) { return kPackBytes; }
 extern "C" size_t nerf_p4_workspace_bytes(int64_t n) { return n > 0 ? layout(n).total : 0; }
+// what train == 0 touches: the four operand images lead the layout (slots 0..3); nothing behind them is read or written
+extern "C" size_t nerf_p4_infer_workspace_bytes(int64_t n) { return n > 0 ? layout(n).tc : 0; }
 extern "C" size_t nerf_p4_workspace_offset(int64_t n, int which) {
   if (n <= 0) return 0;
   const Layout l = layout(n);

@@ -57,16 +57,19 @@ def _check_count():
 
 class Workspace:
     """hash operand images, every training image, the d-feature arrays of ``n`` points (the kernels derive the layout from n);
-    ``buf``: a caller-owned buffer of at least ``Workspace.bytes(n)`` bytes to lay it out in (the engine's grow-only buffer)"""
+    ``buf``: a caller-owned buffer of at least ``Workspace.bytes(n)`` bytes to lay it out in (the engine's grow-only buffer).
+    ``train=False``: evaluation only -- the four operand images, which lead the layout (nerf_p4_infer_workspace_bytes: 256 bytes
+    per point instead of ~2.9 KB); the forward chains touch nothing else when they do not stash."""
 
     @staticmethod
-    def bytes(n: int) -> int:
-        return max(_lib.load().nerf_p4_workspace_bytes(n), 256)
-
-    def __init__(self, n: int, device, buf: Optional[Tensor] = None):
+    def bytes(n: int, train: bool = True) -> int:
         lib = _lib.load()
-        self.n = n
-        need = Workspace.bytes(n)
+        return max(lib.nerf_p4_workspace_bytes(n) if train else lib.nerf_p4_infer_workspace_bytes(n), 256)
+
+    def __init__(self, n: int, device, buf: Optional[Tensor] = None, train: bool = True):
+        lib = _lib.load()
+        self.n, self.train = n, train
+        need = Workspace.bytes(n, train)
         if buf is not None and buf.numel() < need:
             raise ValueError(f"Part 4 workspace: {need} bytes needed for {n} points, {buf.numel()} given")
         self.buf = buf if buf is not None else torch.empty(need, dtype=torch.uint8, device=device)
@@ -77,6 +80,8 @@ class Workspace:
 
     def d_feat(self, k: int) -> Tensor:                  # 0..2 [n,24], 3 [n,32]
         width = 32 if k == 3 else 24
+        if not self.train:
+            raise ValueError("Part 4 workspace: an evaluation workspace holds no d features")
         return self.buf[self._off[4 + k]:self._off[4 + k] + self.n * width * 4].view(torch.float32).view(self.n, width)
 
 
@@ -99,6 +104,8 @@ def forward_chain(packed, params, tables, levels_d, levels_c, bound, pts, x_def,
     lib = _lib.load()
     n = pts.shape[0]
     dev = pts.device
+    if train and not ws.train:
+        raise ValueError("Part 4 forward: the training chains stash into the full workspace (Workspace(n, train=True))")
     x_in = pts if x_def is None else x_def
     # the engine's three deformation tables are views of one flat fp16 buffer: one launch; separate tensors: one launch each
     if not ops.hash_encode_fwd_nat_tables(x_in, tables[:3], levels_d, bound, [ws.nat(k) for k in range(3)], fp16=True):
@@ -209,7 +216,7 @@ class _Part4Field(torch.autograd.Function):
     @staticmethod
     def forward(ctx, flat, t0, t1, t2, tc, pts, x_def, t_def, dirs, levels_d, levels_c, bound, train):
         packed = pack(flat.detach())
-        ws = Workspace(pts.shape[0], pts.device)
+        ws = Workspace(pts.shape[0], pts.device, train=train)       # evaluation: the operand images alone
         tables = [t.detach().view(-1, 2) for t in (t0, t1, t2, tc)]
         rgb, sigma, dx, xc = forward_chain(packed, flat.detach(), tables, levels_d, levels_c, bound, pts, x_def, t_def, dirs, ws, train)
         if train:
@@ -331,9 +338,10 @@ class DualHashEngine(GridEngine):
             for k, name in enumerate(GRIDS):
                 getattr(model, name).encoding.params.copy_(self.table(k))
 
-    def _workspace(self, n: int, which: str = "batch") -> Workspace:
-        """the step's workspace laid out in one grow-only buffer per use (data batch / regulariser probes)"""
-        return Workspace(n, self.device, buf=self._buf(which, Workspace.bytes(n)))
+    def _workspace(self, n: int, which: str = "batch", train: bool = True) -> Workspace:
+        """the step's workspace laid out in one grow-only buffer per use (data batch / regulariser probes); ``train=False``: the
+        evaluation size, so that a render chunk of millions of samples does not grow the buffer to the training layout"""
+        return Workspace(n, self.device, buf=self._buf(which, Workspace.bytes(n, train)), train=train)
 
     def _hash_scratch_tables(self, n: int, n_levels: int, n_tables: int) -> Tensor:
         return self._buf("hash_tables", _lib.load().nerf_hash_encode_bwd_tables_workspace_bytes(n, n_levels, n_tables))
@@ -527,7 +535,7 @@ class DualHashEngine(GridEngine):
     def field(self, pts: Tensor, dirs: Tensor, t: Tensor):
         """(rgb, sigma, delta_x) at points with per-point times, evaluation mode (no noise)"""
         n = pts.shape[0]
-        ws = self._workspace(n)
+        ws = self._workspace(n, train=False)
         rgb, sigma, dx, _ = forward_chain(self.packed, self.net, self._tables_for_forward(), self.levels_d, self.levels_c, self.bound,
                                           pts.contiguous(), None, t.reshape(-1).contiguous(), dirs.contiguous(), ws, False)
         return rgb, sigma, dx
