@@ -46,7 +46,8 @@ extern "C" {
 /* 7: the Instant-NGP tiny-MLP chain for non-default shapes, nerf_imlp_shape_*, is new. */
 /* 8: the Instant-NGP evaluation launch chain, nerf_instant_render_*, is new. */
 /* 9: nerf_p4_infer_workspace_bytes, the evaluation size of the Part 4 workspace, is new. */
-#define NERF_ABI_VERSION 9
+/* 10: the vanilla field's evaluation through an occupancy grid as one launch chain, nerf_render_rays_grid_*, is new. */
+#define NERF_ABI_VERSION 10
 
 typedef void* nerf_stream_t;
 
@@ -564,6 +565,37 @@ int nerf_instant_render_rays_fwd(const void* imlp_packed, const float* table_f32
                                  float near_plane, float far_plane, const float* bg, int64_t bg_rows,
                                  int64_t chunk_rays, void* workspace, float* out_rgb, float* out_depth, float* out_acc,
                                  nerf_stream_t stream);
+
+/* ---- a1-a6 + a10 + a11: evaluation of the vanilla field through an occupancy grid as one launch chain ----
+ * replaces render_rays(perturb=False) with a density_grid and render_image's chunk loop
+ * (src/renderer.py:240-384, 387-418; the masked branch is 303-343) for mode part2_nerf, the field query being
+ * src/core.py:354-359 (Fourier codes -> NeRFDecoder).  Per chunk of `chunk_rays` rays, on the caller's stream:
+ * clear the count word -> nerf_sample_compact (plain depths) -> the 8x256 inference chain in point mode on
+ * the compact rows -> nerf_composite_fwd_indexed.  The chain reads the compaction's active count from DEVICE
+ * memory, so the host never does: no allocation, no host read, no event, no synchronisation; the whole frame
+ * can be captured in a hipGraph.  Results are bit-identical to the same steps called one by one with the
+ * count read back (nerf_sample_compact, nerf_mlp_fwd in point mode, nerf_composite_fwd_indexed): a sample's
+ * value does not depend on its compact slot.
+ *   packed: nerf_mlp_pack's image (the inference stream), 256-byte aligned.  binary_grid [res,res,res] bytes, grid_resolution in
+ *   1..32768, grid_bound: as nerf_sample_compact.  rays_o / rays_d [n_rays,3]; 2 <= n_samples <= 1024; bg /
+ *   bg_rows as nerf_composite_fwd (bg_rows in {1, n_rays}); chunk_rays * n_samples < 2^31.
+ *   workspace: nerf_render_rays_grid_workspace_bytes(chunk_rays, n_samples) bytes, 256-byte aligned, contents
+ *   irrelevant.  With n = chunk_rays * n_samples, every piece rounded up to 256 bytes: 256 (the count word),
+ *   z n*4, slots n*4, pts n*12, dirs n*12, rgb n*12, sigma n*4 -- 48 bytes per sample.  The query returns 0 for
+ *   non-positive arguments.  After the call the count word holds the LAST chunk's active count.
+ * Semantics: a skipped sample contributes sigma = 0 and rgb = 0; a chunk without an active sample renders
+ * the background, depth 0 and acc 0 (the decoder launch returns at once).  One difference from the reference:
+ * its forced query of sample 0 of the first ray when nothing is active (src/renderer.py:309-311) keeps an
+ * autograd graph connected; there is no graph here and the step is not reproduced.  n_rays == 0 is a
+ * successful no-op.  Only the default inference kernel (64 samples per wave) has a counted form: with option
+ * "chain_legacy" or "infer_shape32" set, or "infer64" cleared, the call returns NERF_EINVAL and names the
+ * option, so its results equal nerf_mlp_fwd's bit for bit or it refuses. */
+size_t nerf_render_rays_grid_workspace_bytes(int64_t chunk_rays, int n_samples);
+int nerf_render_rays_grid_fwd(const void* packed, const uint8_t* binary_grid, int grid_resolution, float grid_bound,
+                              const float* rays_o, const float* rays_d, int64_t n_rays, int n_samples,
+                              float near_plane, float far_plane, const float* bg, int64_t bg_rows,
+                              int64_t chunk_rays, void* workspace, float* out_rgb, float* out_depth, float* out_acc,
+                              nerf_stream_t stream);
 
 /* ---- a9 + a14: compositing fused with the MSE loss and its backward --------------------------
  * replaces, for one training step, volume_render (src/renderer.py:204-237), nn.MSELoss

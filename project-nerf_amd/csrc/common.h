@@ -66,6 +66,10 @@ int hash_fwd_counted(const float* pts, const unsigned* count, int64_t capacity, 
                      const unsigned* offset_host, const unsigned* dense_host, float bound, void* out_nat, nerf_stream_t stream);
 int imlp_fwd_counted(const void* packed, const void* hash_nat, const float* dirs, const unsigned* count, int64_t capacity, float* rgb,
                      float* sigma, nerf_stream_t stream);
+// mlp_fwd.hip: the 8x256 inference chain in point mode (64 samples per wave) on the first *count rows of pts / dirs, for
+// render_grid.hip's launch chain
+int mlp_fwd_counted(const void* packed, const float* pts, const float* dirs, const unsigned* count, int64_t capacity, float* rgb,
+                    float* sigma, nerf_stream_t stream);
 
 #define NERF_REQUIRE(cond, ...) \
   do {                          \

@@ -53,7 +53,7 @@ def unflatten(flat: Tensor, prefix: str = "decoder.") -> Dict[str, Tensor]:
 class VanillaNerfEngine:
     def __init__(self, params: Optional[Tensor] = None, device: str = "cuda", lr: float = 5e-4,
                  near: float = 2.0, far: float = 6.0, white_bkgd: bool = True, seed: int = 0,
-                 world_size: int = 1):
+                 world_size: int = 1, grid_resolution: int = 128, bound: float = 1.5, grid_threshold: float = 0.01):
         self.device = torch.device(device)
         flat = default_init(seed) if params is None else params.detach().float().reshape(-1)
         assert flat.numel() == ops.MLP_PARAM_COUNT
@@ -73,6 +73,11 @@ class VanillaNerfEngine:
         self._scalars = torch.zeros(2, 1024, device=self.device)
         self._slots = LapSlots(self._scalars)
         self._infer_stale = False
+        # occupancy grid (opt-in: update_grid / render_image(grid=...)); nothing is allocated until update_grid or a caller sets it
+        self.grid_resolution, self.bound, self.grid_threshold = int(grid_resolution), float(bound), float(grid_threshold)
+        self.grid: Optional[Tensor] = None
+        self.binary_grid: Optional[Tensor] = None
+        self._grid_ws: Dict[Tuple[int, int], Tensor] = {}      # render_image(grid=True): one workspace per (chunk, n_samples)
         self.repack()
 
     # -- weights ---------------------------------------------------------------
@@ -182,8 +187,67 @@ class VanillaNerfEngine:
         c, depth, acc, _, _ = ops.composite_fwd(rgb.view(R, S, 3), sigma.view(R, S), z_all, rays_d, self.bg)
         return c, depth, acc
 
+    # -- occupancy grid (reference DensityGrid.update, src/renderer.py:35-132; the masked render_rays, 303-343) --
     @torch.no_grad()
-    def render_image(self, rays_o: Tensor, rays_d: Tensor, n_samples: int, chunk: int = 65536, n_fine: int = 0) -> Tensor:
+    def update_grid(self) -> float:
+        """DensityGrid.update for a static field: sigma on the lattice (zero view directions, 2^18-point batches), thresholded."""
+        res = self.grid_resolution
+        pts = ops.grid_lattice(self.bound, res, self.device)
+        sig = torch.empty(res ** 3, device=self.device)
+        zeros = torch.zeros(2 ** 18, 3, device=self.device)
+        packed = self._inference_weights()
+        for i in range(0, pts.shape[0], 2 ** 18):
+            p = pts[i:i + 2 ** 18]
+            sig[i:i + 2 ** 18] = ops.mlp_fwd(packed, p, zeros[:p.shape[0]], None)[1]
+        self.grid = sig.view(res, res, res)
+        self.binary_grid, ratio = ops.grid_threshold(self.grid, self.grid_threshold)
+        return ratio
+
+    def _require_grid(self, what: str) -> Tensor:
+        if self.binary_grid is None:
+            raise ValueError(f"{what}: no occupancy grid (call update_grid() or set binary_grid first)")
+        return self.binary_grid
+
+    @torch.no_grad()
+    def render_rays_grid(self, rays_o: Tensor, rays_d: Tensor, n_samples: int):
+        """One chunk through the occupancy grid on the host-counted path: compaction (one host read of the active count), the
+        inference chain in point mode on the active samples, indexed compositing; the background when nothing is active."""
+        grid = self._require_grid("render_rays_grid")
+        z, slots, pts, dirs = ops.sample_compact(rays_o, rays_d, self.near, self.far, n_samples, grid, self.bound)
+        R = rays_o.shape[0]
+        if pts.shape[0] == 0:
+            bg = self.bg.expand(R, 3).clone() if self.bg.dim() == 1 else self.bg.clone()
+            return bg, torch.zeros(R, device=self.device), torch.zeros(R, device=self.device)
+        rgb, sigma = ops.mlp_fwd(self._inference_weights(), pts, dirs, None)
+        return ops.composite_indexed(rgb, sigma, slots, z, rays_d, self.bg)
+
+    def _render_image_grid_chain(self, rays_o: Tensor, rays_d: Tensor, n_samples: int, chunk: int) -> Tensor:
+        grid = self._require_grid("render_image(grid=True)")
+        shape = rays_o.shape[:-1]
+        o, d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
+        chunk = max(1, min(int(chunk), max(o.shape[0], 1)))
+        ws = self._grid_ws.get((chunk, n_samples))
+        if ws is None:
+            ws = self._grid_ws[(chunk, n_samples)] = torch.empty(ops.render_rays_grid_workspace_bytes(chunk, n_samples), dtype=torch.uint8,
+                                                                 device=self.device)
+        rgb = ops.render_rays_grid_fwd(self._inference_weights(), grid, self.bound, o, d, n_samples, self.near, self.far, self.bg, chunk,
+                                       workspace=ws)[0]
+        return rgb.view(*shape, 3)
+
+    @torch.no_grad()
+    def render_image(self, rays_o: Tensor, rays_d: Tensor, n_samples: int, chunk: int = 65536, n_fine: int = 0, grid=False) -> Tensor:
+        """``grid=True``: the frame through the occupancy grid as ONE launch chain (nerf_render_rays_grid_fwd) -- only active samples
+        reach the decoder, the chunks' active counts stay on the device, one workspace kept per (chunk, n_samples);
+        ``grid="loop"``: the same frame chunk by chunk on the host-counted path (render_rays_grid), the same bits."""
+        if grid:
+            if grid is not True and grid != "loop":
+                raise ValueError(f"render_image: grid={grid!r} (False, True or 'loop')")
+            if n_fine > 0:
+                raise ValueError("render_image: hierarchical sampling (n_fine > 0) is not combined with the occupancy grid")
+            self._require_grid(f"render_image(grid={grid!r})")
+            if grid is True:
+                return self._render_image_grid_chain(rays_o, rays_d, n_samples, chunk)
+            return render_chunks(lambda o, d: self.render_rays_grid(o, d, n_samples), rays_o, rays_d, chunk, self.device)
         if n_fine == 0:
             shape = rays_o.shape[:-1]
             o, d = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3)

@@ -542,6 +542,37 @@ def render_rays_fwd(packed: Tensor, rays_o: Tensor, rays_d: Tensor, n_samples: i
     return out, depth, acc
 
 
+def render_rays_grid_workspace_bytes(chunk: int, n_samples: int) -> int:
+    return _lib.load().nerf_render_rays_grid_workspace_bytes(chunk, n_samples)
+
+
+def render_rays_grid_fwd(packed: Tensor, binary_grid: Tensor, grid_bound: float, rays_o: Tensor, rays_d: Tensor, n_samples: int,
+                         near: float, far: float, bg: Optional[Tensor] = None, chunk: int = 65536, workspace: Optional[Tensor] = None):
+    """(rgb [R,3], depth [R], acc [R]) of the vanilla field against an occupancy grid for any number of rays: one launch chain
+    over chunks of ``chunk`` rays in one reused workspace (nerf_render_rays_grid_fwd) -- compaction, the inference chain in point
+    mode on the active samples alone, indexed compositing; the active count of a chunk stays on the device, nothing is allocated
+    or waited for between the launches.  ``workspace``: uint8, at least render_rays_grid_workspace_bytes(chunk, n_samples) bytes
+    (allocated here otherwise); its first int32 holds the last chunk's active count afterwards."""
+    lib = _lib.load()
+    rays_o, rays_d = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d")
+    grid = _dev(binary_grid, "binary_grid", torch.bool)
+    packed = _dev(packed, "packed", torch.uint8)
+    R = rays_o.shape[0]
+    chunk = max(1, min(int(chunk), max(R, 1)))
+    need = lib.nerf_render_rays_grid_workspace_bytes(chunk, n_samples)
+    if workspace is None:
+        workspace = torch.empty(need, device=rays_o.device, dtype=torch.uint8)
+    elif _dev(workspace, "workspace", torch.uint8).numel() < need:
+        raise ValueError(f"render_rays_grid_fwd: workspace of {workspace.numel()} bytes, {need} needed for chunk {chunk} x {n_samples}")
+    bg = None if bg is None else _dev(bg, "bg")
+    out = torch.empty(R, 3, device=rays_o.device)
+    depth, acc = torch.empty(R, device=rays_o.device), torch.empty(R, device=rays_o.device)
+    _lib.check(lib.nerf_render_rays_grid_fwd(_p(packed), _p(grid), grid.shape[0], float(grid_bound), _p(rays_o), _p(rays_d), R, n_samples,
+                                             float(near), float(far), _p(bg), _bg_rows(bg), chunk, _p(workspace), _p(out), _p(depth),
+                                             _p(acc), _stream()), "nerf_render_rays_grid_fwd")
+    return out, depth, acc
+
+
 def mlp_bwd_workspace_bytes(n: int) -> int:
     return _lib.load().nerf_mlp_bwd_workspace_bytes(n)
 

@@ -188,6 +188,27 @@ def render_rays_instant_chain(model, rays_o, rays_d, near, far, n_samples, densi
                                        density_grid.bound, o, d, n_samples, near, far, bg, chunk)
 
 
+@torch.no_grad()
+def render_rays_nerf_grid_chain(model, rays_o, rays_d, near, far, n_samples, density_grid, white_bkgd, chunk):
+    """(rgb [R,3], depth [R], acc [R]) of a part2_nerf field against ``density_grid`` for any number of rays as ONE launch chain
+    (nerf_render_rays_grid_fwd): what a loop of ``render_rays(..., perturb=False, density_grid=...)`` over chunks of ``chunk``
+    rays computes, bit for bit, without its per-chunk host read of the active count and with only the active samples in the
+    decoder.  One difference: a chunk without an active sample renders exactly the background here; ``render_rays`` then queries
+    sample 0 of its first ray to keep the autograd graph connected (reference src/renderer.py:309-311), which has no meaning
+    without a graph."""
+    if getattr(model, "mode", None) != "part2_nerf":
+        raise ValueError(f"render_rays_nerf_grid_chain: mode {getattr(model, 'mode', None)!r} (serves part2_nerf)")
+    dec = model.decoder
+    if not getattr(dec, "fused", False):
+        raise NotImplementedError("render_rays_nerf_grid_chain: the launch chain is wired for the fused decoder shape (hidden 256, 8 layers, "
+                                  "skip 4, view 128); use render_rays for another shape")
+    if density_grid is None:
+        raise ValueError("render_rays_nerf_grid_chain: a density_grid is required (render_image serves the dense path)")
+    o, d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
+    bg = torch.ones(3, device=o.device) if white_bkgd else torch.zeros(3, device=o.device)
+    return ops.render_rays_grid_fwd(dec.packed_weights(), density_grid.binary_grid, density_grid.bound, o, d, n_samples, near, far, bg, chunk)
+
+
 def render_image(model, rays_o, rays_d, near, far, n_samples, chunk, white_bkgd):
     """reference src/renderer.py:387-418."""
     h, w = rays_o.shape[:2]

@@ -25,7 +25,7 @@ import yaml
 
 from src.core import NeuralField
 from src.dataset import BlenderDataset
-from src.renderer import render_image, render_rays
+from src.renderer import DensityGrid, render_image, render_rays, render_rays_nerf_grid_chain
 from src.utils import TensorBoardLogger, compute_psnr, compute_psnr_torch, render_image_safe
 
 
@@ -63,9 +63,35 @@ def run_part2(cfg, args):
     test_set = BlenderDataset(args.data_dir, test_split, downscale, white_bkgd, scene_scale)
 
     model = NeuralField(cfg).to(device)
+    # use_density_grid: true (default false for this mode) -- an occupancy grid of the trained field, saved with the checkpoints in
+    # the reference's format; evaluation then pushes only the active samples through the decoder (render_rays_nerf_grid_chain)
+    grid, grid_loaded = None, False
+    if cfg.get("use_density_grid", False):
+        if not getattr(model.decoder, "fused", False):
+            raise ValueError("use_density_grid: true needs the default decoder shape (hidden 256, 8 layers, skip 4, view 128)")
+        grid = DensityGrid(cfg.get("grid_resolution", 128), cfg.get("scene_bound", 1.5), cfg.get("grid_threshold", 0.01)).to(device)
     if args.checkpoint:
-        model.load_state_dict(torch.load(args.checkpoint, map_location=device)["model_state_dict"])
+        ckpt = torch.load(args.checkpoint, map_location=device)
+        model.load_state_dict(ckpt["model_state_dict"])
         say(f">>> Loaded checkpoint: {args.checkpoint}")
+        if grid is not None and "density_grid" in ckpt:
+            grid.load_state_dict(ckpt["density_grid"])
+            grid_loaded = True
+            say(f">>> Density grid: loaded from the checkpoint ({float(grid.binary_grid.float().mean()) * 100:.1f} % of the cells occupied)")
+        del ckpt
+
+    def refresh_grid():
+        """the grid of the model's current weights (DensityGrid.update, reference src/renderer.py:35-132)"""
+        ratio = grid.update(model, device=device)
+        say(f">>> Density grid: rebuilt from the model ({ratio * 100:.1f} % of the cells occupied)")
+
+    def save_checkpoint(path):
+        """reference format; with a grid: refreshed from the weights being saved and stored under "density_grid" """
+        out = {"model_state_dict": model.state_dict(), "config": cfg}
+        if grid is not None:
+            refresh_grid()
+            out["density_grid"] = grid.state_dict()
+        torch.save(out, path)
     local_batch = parallel.check_global_batch(batch_size, world)   # this rank's shard of the global batch
     parallel.broadcast_([p.data for p in model.parameters()])       # replicas start from rank 0's weights whatever the seeds did
     first_ray = rank * local_batch
@@ -120,11 +146,10 @@ def run_part2(cfg, args):
                     tb.log_scalar("Train/PSNR", psnr, step)
             if save_every and step % save_every == 0 and main_rank:
                 sync_model()
-                torch.save({"model_state_dict": model.state_dict(), "config": cfg},
-                           os.path.join(ckpt_dir, f"model_step_{step:06d}.pth"))
+                save_checkpoint(os.path.join(ckpt_dir, f"model_step_{step:06d}.pth"))
         sync_model()
         if main_rank:
-            torch.save({"model_state_dict": model.state_dict(), "config": cfg}, os.path.join(ckpt_dir, "model_final.pth"))
+            save_checkpoint(os.path.join(ckpt_dir, "model_final.pth"))
             tb.close()
     elif p2_eng is not None:
         tb = TensorBoardLogger(os.path.join(log_dir, "tensorboard"))
@@ -149,10 +174,9 @@ def run_part2(cfg, args):
                 tb.log_scalar("Train/PSNR", psnr, step)
             if save_every and step % save_every == 0:
                 sync_model()
-                torch.save({"model_state_dict": model.state_dict(), "config": cfg},
-                           os.path.join(ckpt_dir, f"model_step_{step:06d}.pth"))
+                save_checkpoint(os.path.join(ckpt_dir, f"model_step_{step:06d}.pth"))
         sync_model()
-        torch.save({"model_state_dict": model.state_dict(), "config": cfg}, os.path.join(ckpt_dir, "model_final.pth"))
+        save_checkpoint(os.path.join(ckpt_dir, "model_final.pth"))
         tb.close()
     elif not args.eval_only:
         tb = TensorBoardLogger(os.path.join(log_dir, "tensorboard")) if main_rank else None
@@ -178,20 +202,32 @@ def run_part2(cfg, args):
                     tb.log_scalar("Train/Loss", loss_val, step)
                     tb.log_scalar("Train/PSNR", psnr, step)
             if save_every and step % save_every == 0 and main_rank:
-                torch.save({"model_state_dict": model.state_dict(), "config": cfg},
-                           os.path.join(ckpt_dir, f"model_step_{step:06d}.pth"))
+                save_checkpoint(os.path.join(ckpt_dir, f"model_step_{step:06d}.pth"))
         if main_rank:
-            torch.save({"model_state_dict": model.state_dict(), "config": cfg}, os.path.join(ckpt_dir, "model_final.pth"))
+            save_checkpoint(os.path.join(ckpt_dir, "model_final.pth"))
             tb.close()
 
     model.eval()
+    if grid is not None and not (args.eval_only and grid_loaded) and (args.eval_only or not main_rank):
+        refresh_grid()          # (after training, rank 0 refreshed it when it wrote the final checkpoint)
+
+    def render_grid_band(o, d):
+        """a band of rows through the occupancy grid as one launch chain (renderer.render_rays_nerf_grid_chain)"""
+        rows, width = o.shape[0], o.shape[1]
+        if rows * width == 0:
+            return o.new_zeros(0, width, 3)
+        return render_rays_nerf_grid_chain(model, o.reshape(-1, 3), d.reshape(-1, 3), near, far, render_n_samples, grid, white_bkgd,
+                                           chunk)[0].view(rows, width, 3)
+
     psnrs = []
     n_eval = len(test_set) if args.render_n in (None, -1) else min(args.render_n, len(test_set))
     with torch.no_grad():
         for idx in range(n_eval):
             rays_o, rays_d, target = test_set.get_image_rays(idx, device)
             # row bands over the ranks, gathered on rank 0 (one rank: the whole frame)
-            if p2_eng is not None:       # single rank: the whole frame through the engine's inference chain
+            if grid is not None:         # only the active samples reach the decoder; no host read of their count
+                pred = parallel.render_row_bands(render_grid_band, rays_o, rays_d)
+            elif p2_eng is not None:     # single rank: the whole frame through the engine's inference chain
                 pred = p2_eng.render_image(rays_o, rays_d, render_n_samples, chunk)
             else:
                 pred = parallel.render_row_bands(
