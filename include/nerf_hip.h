@@ -47,7 +47,8 @@ extern "C" {
 /* 8: the Instant-NGP evaluation launch chain, nerf_instant_render_*, is new. */
 /* 9: nerf_p4_infer_workspace_bytes, the evaluation size of the Part 4 workspace, is new. */
 /* 10: the vanilla field's evaluation through an occupancy grid as one launch chain, nerf_render_rays_grid_*, is new. */
-#define NERF_ABI_VERSION 10
+/* 11: the data side of a training step through the occupancy grid in one launch, nerf_train_batch_compact*, is new. */
+#define NERF_ABI_VERSION 11
 
 typedef void* nerf_stream_t;
 
@@ -178,6 +179,33 @@ int nerf_sample_compact_jitter_chain(const float* rays_o, const float* rays_d, u
                                      const uint8_t* binary_grid, int resolution, float bound, float* z_out,
                                      int* slot_of_sample, float* pts_compact, float* dirs_compact,
                                      unsigned* chain_state, int turn, unsigned* count_host, unsigned seq, nerf_stream_t stream);
+
+/* ---- f1 + a1-a4: the data side of one training step THROUGH the occupancy grid in one kernel ----
+ * nerf_train_batch_shard followed by nerf_sample_compact_jitter_shard (same seed, counter, first_ray) in ONE launch: no
+ * [batch, n_samples] depth array between them that the compaction never reads, no second read of the rays.  Every output equals
+ * the two calls' bit for bit (the compact rows up to the slot order, which is arbitrary in both):
+ *   rays_o / rays_d [batch,3], target [batch,3] (with bg [3]) and/or rgba [batch,4] as nerf_train_batch_shard writes them;
+ *   z_out [batch,n_samples], slot_of_sample [batch*n_samples], pts_compact / dirs_compact [capacity >= batch*n_samples rows, 3]
+ *   (only the first *active_count rows are written), active_count (device u32, cleared by the call) as
+ *   nerf_sample_compact_jitter_shard writes them.
+ * batch >= 0 (0: a successful no-op, nothing is read or written); 2 <= n_samples; batch * n_samples < 2^31; counter < 2^24;
+ * (first_ray + batch) * n_samples < 2^39; resolution in 1..32768; bound > 0; images / rgba 16-byte aligned. */
+int nerf_train_batch_compact(const float* images, const float* poses, int n_images, int H, int W, float focal,
+                             float scene_scale, const float* bg, uint64_t seed, uint64_t counter, int64_t first_ray,
+                             int64_t batch, int n_samples, float near_plane, float far_plane,
+                             const uint8_t* binary_grid, int resolution, float bound, float* rays_o, float* rays_d,
+                             float* rgba, float* target, float* z_out, int* slot_of_sample, float* pts_compact,
+                             float* dirs_compact, unsigned* active_count, nerf_stream_t stream);
+/* ... as a link of a chain: chain_state / turn / count_host / seq exactly as in nerf_sample_compact_jitter_chain (this call
+ * counts in word `turn`, clears word `turn ^ 1`, the last workgroup writes the count and then `seq` to count_host behind a
+ * system-scope fence; count_host NULL: no publication).  Links of both entries may alternate on one chain_state. */
+int nerf_train_batch_compact_chain(const float* images, const float* poses, int n_images, int H, int W, float focal,
+                                   float scene_scale, const float* bg, uint64_t seed, uint64_t counter, int64_t first_ray,
+                                   int64_t batch, int n_samples, float near_plane, float far_plane,
+                                   const uint8_t* binary_grid, int resolution, float bound, float* rays_o, float* rays_d,
+                                   float* rgba, float* target, float* z_out, int* slot_of_sample, float* pts_compact,
+                                   float* dirs_compact, unsigned* chain_state, int turn, unsigned* count_host, unsigned seq,
+                                   nerf_stream_t stream);
 
 /* the same compaction with the slots in SAMPLE ORDER (option "deterministic": the single-pass kernels reserve slots with a returning
  * atomic per 4096 samples, so the order of the compact arrays -- and with it the order of every later sum over samples -- depends

@@ -39,6 +39,11 @@ PROTOTYPES = {
                                                c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "nerf_sample_compact_jitter_chain": (i32, [c_ptr, c_ptr, ctypes.c_uint64, ctypes.c_uint64, i64, i64, i32, f32, f32, c_ptr, i32, f32,
                                                c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, i32, c_ptr, ctypes.c_uint32, c_ptr]),
+    "nerf_train_batch_compact": (i32, [c_ptr, c_ptr, i32, i32, i32, f32, f32, c_ptr, ctypes.c_uint64, ctypes.c_uint64, i64, i64, i32, f32, f32,
+                                       c_ptr, i32, f32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "nerf_train_batch_compact_chain": (i32, [c_ptr, c_ptr, i32, i32, i32, f32, f32, c_ptr, ctypes.c_uint64, ctypes.c_uint64, i64, i64, i32, f32,
+                                             f32, c_ptr, i32, f32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, i32, c_ptr,
+                                             ctypes.c_uint32, c_ptr]),
     "nerf_composite_fwd_indexed": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, i64, i64, i32, c_ptr, c_ptr, c_ptr, c_ptr]),
     "nerf_composite_bwd_indexed": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, i64, c_ptr, c_ptr, c_ptr, i64, i32, c_ptr, c_ptr, c_ptr]),
     "nerf_sample_pdf": (i32, [c_ptr, c_ptr, c_ptr, i64, i32, i32, c_ptr, c_ptr]),
@@ -169,7 +174,7 @@ PROTOTYPES = {
     "nerf_adamw_clip_step_shadow": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, i64, i32, f32, f32, f32, f32, f32, c_ptr, f32, f32, c_ptr, c_ptr]),
 }
 
-ABI_VERSION = 10     # the NERF_ABI_VERSION of include/nerf_hip.h this table was written against
+ABI_VERSION = 11     # the NERF_ABI_VERSION of include/nerf_hip.h this table was written against
 
 _lib = None
 

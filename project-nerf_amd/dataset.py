@@ -88,6 +88,14 @@ class BlenderDataset:
         return ops.train_batch(self.images, self.poses, self.focal, batch_size, n_samples, near, far, seed, counter, bg=bg,
                                scene_scale=self.scene_scale, perturb=perturb, first_ray=first_ray)
 
+    def train_batch_compact(self, batch_size, n_samples, near, far, bg, seed, counter, binary_grid, bound, first_ray=0):
+        """(rays_o, rays_d, target, CompactedSamples) of one training step THROUGH an occupancy grid from one kernel
+        (ops.train_batch_compact): ``train_batch``'s rays and targets, and its jittered depths compacted against
+        ``binary_grid`` without a wait -- the batch a grid step of VanillaNerfEngine takes as ``prepared``."""
+        from . import ops
+        return ops.train_batch_compact(self.images, self.poses, self.focal, batch_size, n_samples, near, far, seed, counter, binary_grid,
+                                       bound, bg=bg, scene_scale=self.scene_scale, first_ray=first_ray)
+
     @classmethod
     def from_tensors(cls, images, poses, camera_angle_x, white_bkgd=True, scene_scale=1.0):
         """Dataset over frames that are already tensors ([n,H,W,4] RGBA in [0,1], [n,4,4] camera-to-world)."""

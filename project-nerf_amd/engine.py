@@ -78,6 +78,11 @@ class VanillaNerfEngine:
         self.grid: Optional[Tensor] = None
         self.binary_grid: Optional[Tensor] = None
         self._grid_ws: Dict[Tuple[int, int], Tensor] = {}      # render_image(grid=True): one workspace per (chunk, n_samples)
+        # training through the grid (prepare_batch / compute_gradients(grid=True | prepared=...)): the in-kernel jitter's generator
+        # state and ONE grow-only buffer per use -- the active count changes every step, _buf's exact-size keys would keep a buffer
+        # per count (the stash is 5.4 KB per sample)
+        self.seed, self._jitter_counter = int(seed), 0
+        self._grid_train_ws: Dict[str, Tensor] = {}
         self.repack()
 
     # -- weights ---------------------------------------------------------------
@@ -106,14 +111,91 @@ class VanillaNerfEngine:
             self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return self._ws[key]
 
+    GRID_SLACK = (1.25, 1 << 20)     # growth of the grid step's buffers: factor and bytes on top of what a step asks for
+
+    def _grid_buf(self, kind: str, nbytes: int) -> Tensor:
+        """ONE grow-only byte buffer per use of the grid step (the pattern of DynamicEngine._buf)"""
+        buf = self._grid_train_ws.get(kind)
+        if buf is None or buf.numel() < nbytes:
+            buf = None
+            self._grid_train_ws.pop(kind, None)              # release before growing
+            buf = self._grid_train_ws[kind] = torch.empty(int(nbytes * self.GRID_SLACK[0]) + self.GRID_SLACK[1], dtype=torch.uint8,
+                                                          device=self.device)
+        return buf
+
+    def prepare_batch(self, rays_o: Tensor, rays_d: Tensor, n_samples: int = 64, u: Optional[Tensor] = None, first_ray: int = 0):
+        """Queues the data-only front of a grid step -- stratified depths, occupancy test, compaction -- and the read-back of the
+        active count WITHOUT waiting for it (InstantNgpEngine.prepare_batch): a loop that prepares batch i + 1 before it runs step i
+        never stalls on the count.  The jitter is drawn in the kernel from (seed, a counter of this engine) or read from ``u``
+        [R, n_samples].  The batch is compacted against the grid as it is now: prepare again after ``update_grid``.
+        BlenderDataset.train_batch_compact returns the same object together with the rays it drew, from one kernel."""
+        grid = self._require_grid("prepare_batch")
+        jitter = None
+        if u is None:
+            self._jitter_counter += 1
+            jitter = (self.seed, self._jitter_counter)
+        return ops.sample_compact_async(rays_o, rays_d, self.near, self.far, n_samples, grid, self.bound, u=u, jitter=jitter,
+                                        first_ray=first_ray)
+
+    def _grid_gradients(self, rays_o: Tensor, rays_d: Tensor, target: Tensor, n_samples: int, u, sync_grads, sync_grads_async, mark,
+                        prepared) -> Tensor:
+        """The step of compute_gradients on the ACTIVE samples alone: the training forward in point mode on the compact rows,
+        compositing + loss + their backward through the slot map (a skipped sample is sigma = 0, rgb = 0: the reference's
+        zero-filled scatter, src/renderer.py:325-343), the backward chains at the active count.  Same kernels, same phases,
+        same collectives as the dense step."""
+        mark = mark or (lambda name: None)
+        if prepared is None:
+            prepared = self.prepare_batch(rays_o, rays_d, n_samples, u=u)
+        z, slots, pts, dirs = prepared.get()                 # (waits for the active count alone)
+        mark("sample")
+        R, n = rays_o.shape[0], pts.shape[0]
+        if n == 0:
+            # no active sample (on THIS rank): zero gradients, the background's loss, and exactly the collectives a rank with
+            # samples issues -- the same views in the same order (mismatched collectives across ranks hang in RCCL)
+            self.grads.zero_()
+            loss = ((self.bg.expand(R, 3) - target) ** 2).mean()
+            mark("fwd")
+            mark("loss")
+            mark("dgrad")
+            if sync_grads_async is not None:
+                split = ops._lib.load().nerf_mlp_wgrad_part_split()
+                for h in [sync_grads_async(view) for view in (self.grads[split:], self.grads[:split])]:
+                    if h is not None:
+                        h.wait()
+            mark("wgrad")
+            if sync_grads is not None:
+                sync_grads(self.grads)
+            return loss
+        stash = self._grid_buf("stash", ops.mlp_stash_bytes(n))
+        rgb, sigma = ops.mlp_fwd(self.packed, pts, dirs, None, stash)
+        mark("fwd")
+        loss, amax = self._slots.take()
+        d_rgb, d_sigma, _ = ops.composite_mse_bwd(rgb, sigma, z, rays_d, self.bg, target, loss, slots=slots, amax_accum=amax)
+        mark("loss")
+        ws = self._grid_buf("bwd", ops.mlp_bwd_workspace_bytes(n))
+        if sync_grads_async is not None:
+            ops.mlp_bwd_overlapped(self.packed, stash, rgb, sigma, d_rgb, d_sigma, self.grads, ws, sync_grads_async, amax=amax, mark=mark)
+        else:
+            ops.mlp_bwd(self.packed, stash, rgb, sigma, d_rgb, d_sigma, self.grads, ws, amax=amax, mark=mark)
+        mark("wgrad")
+        if sync_grads is not None:
+            sync_grads(self.grads)
+        return LapSlots.keep(loss)
+
     # -- training step (reference run.py:314-338) ------------------------------
     def compute_gradients(self, rays_o: Tensor, rays_d: Tensor, target: Tensor, n_samples: int = 64,
                    u: Optional[Tensor] = None, sync_grads=None, sync_grads_async=None, mark=None,
-                   z: Optional[Tensor] = None) -> Tensor:
+                   z: Optional[Tensor] = None, grid: bool = False, prepared=None) -> Tensor:
         """``z`` [R, n_samples]: jittered depths the caller already has (BlenderDataset.train_batch draws them
         together with the rays); otherwise they are drawn here (``u`` or torch.rand).
         ``mark(name)`` (optional) is called after each phase has been enqueued -- bench.py records a HIP
-        event there, which times the kernels inside the step without serialising anything."""
+        event there, which times the kernels inside the step without serialising anything.
+        ``prepared`` (from prepare_batch / BlenderDataset.train_batch_compact; implies ``grid``) or ``grid=True`` (compacts here
+        and waits for the count): the step through the occupancy grid -- only the active samples reach the decoder."""
+        if grid or prepared is not None:
+            if z is not None:
+                raise ValueError("compute_gradients: the grid step draws its own depths (z is for the dense step)")
+            return self._grid_gradients(rays_o, rays_d, target, n_samples, u, sync_grads, sync_grads_async, mark, prepared)
         mark = mark or (lambda name: None)
         R = rays_o.shape[0]
         n = R * n_samples
@@ -154,11 +236,11 @@ class VanillaNerfEngine:
 
     def train_step(self, rays_o: Tensor, rays_d: Tensor, target: Tensor, n_samples: int = 64,
                    u: Optional[Tensor] = None, sync_grads=None, sync_grads_async=None, mark=None,
-                   z: Optional[Tensor] = None) -> Tensor:
+                   z: Optional[Tensor] = None, grid: bool = False, prepared=None) -> Tensor:
         """One step of reference run.py:314-338: gradients of the local batch (``self.grads``; summed over
-        ranks by the ``sync_grads*`` callbacks), then Adam and the weight repack."""
+        ranks by the ``sync_grads*`` callbacks), then Adam and the weight repack.  ``grid`` / ``prepared``: see compute_gradients."""
         loss = self.compute_gradients(rays_o, rays_d, target, n_samples, u=u, sync_grads=sync_grads,
-                                      sync_grads_async=sync_grads_async, mark=mark, z=z)
+                                      sync_grads_async=sync_grads_async, mark=mark, z=z, grid=grid, prepared=prepared)
         self.apply_gradients()
         if mark is not None:
             mark("adam+pack")
@@ -199,8 +281,12 @@ class VanillaNerfEngine:
         for i in range(0, pts.shape[0], 2 ** 18):
             p = pts[i:i + 2 ** 18]
             sig[i:i + 2 ** 18] = ops.mlp_fwd(packed, p, zeros[:p.shape[0]], None)[1]
-        self.grid = sig.view(res, res, res)
-        self.binary_grid, ratio = ops.grid_threshold(self.grid, self.grid_threshold)
+        binary, ratio = ops.grid_threshold(sig.view(res, res, res), self.grid_threshold)
+        if ratio <= 0.0:
+            # no cell above the threshold (a field on the dead-density plateau): a grid step through such a
+            # grid has no sample and no gradient, the field would prune itself for good -- the previous grid stays
+            return 0.0
+        self.grid, self.binary_grid = sig.view(res, res, res), binary
         return ratio
 
     def _require_grid(self, what: str) -> Tensor:

@@ -19,6 +19,20 @@ def cosine_lr(base: float, eta_min: float, step: int, t_max: int) -> float:
     return eta_min + (base - eta_min) * (1 + math.cos(math.pi * step / t_max)) / 2
 
 
+def grid_refresh_due(step: int, iters: int, warm: int, stop: float = 0.9) -> bool:
+    """Whether a training loop that goes through its occupancy grid refreshes the grid AFTER step ``step`` (1-based) of ``iters``:
+    the first refresh after step ``warm`` (the steps up to it are dense), then the reference's schedule (run.py:621-627) -- every
+    32 steps in the first tenth of the run, every 128 up to half of it, every 512 after that, none from ``stop`` * iters on."""
+    if step < max(warm, 1):
+        return False
+    if step == max(warm, 1):
+        return True
+    if step >= iters * stop:
+        return False
+    interval = 32 if step < iters * 0.1 else (128 if step < iters * 0.5 else 512)
+    return step % interval == 0
+
+
 def render_chunks(render_rays, rays_o: Tensor, rays_d: Tensor, chunk: int, device) -> Tensor:
     """[..., 3] colours of rays [..., 3]: ``render_rays(o, d)[0]`` over ``chunk`` rays at a time"""
     shape = rays_o.shape[:-1]

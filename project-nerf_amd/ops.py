@@ -308,6 +308,48 @@ def sample_compact_async(rays_o: Tensor, rays_d: Tensor, near: float, far: float
     return CompactedSamples(z, slots, pts, dirs, count_host, event)
 
 
+def train_batch_compact(images: Tensor, poses: Tensor, focal: float, batch: int, n_samples: int, near: float, far: float,
+                        seed: int, counter: int, binary_grid: Tensor, bound: float, bg: Optional[Tensor] = None,
+                        scene_scale: float = 1.0, first_ray: int = 0, want_rgba: bool = False):
+    """The data side of one training step THROUGH the occupancy grid as ONE kernel (nerf_train_batch_compact_chain):
+    (rays_o, rays_d, target or rgba, CompactedSamples) -- what ``train_batch`` followed by ``sample_compact_async(...,
+    jitter=(seed, counter), first_ray=first_ray)`` returns, bit for bit, without the [batch, S] depths of the first call that the
+    second never reads.  Nothing is waited for.  The call is a link of the SAME chain per (device, stream) as
+    ``sample_compact_async``'s (the two counter words alternate across both entries).  Under option ``deterministic`` (slots in
+    sample order: the ordered compaction has no fused form) or NERF_NO_COMPACT_CHAIN it IS those two calls."""
+    lib = _lib.load()
+    images, poses = _dev(images, "images"), _dev(poses, "poses")
+    grid = _dev(binary_grid, "binary_grid", torch.bool)
+    counter = int(counter) & 0xFFFFFF
+    if deterministic() or _NO_CHAIN or batch == 0:
+        o, d, tgt, _ = train_batch(images, poses, focal, batch, n_samples, near, far, seed, counter, bg=bg, scene_scale=scene_scale,
+                                   want_rgba=want_rgba, first_ray=first_ray)
+        return o, d, tgt, sample_compact_async(o, d, near, far, n_samples, grid, bound, jitter=(seed, counter), first_ray=first_ray)
+    n_img, H, W, _ = images.shape
+    dev = images.device
+    n = batch * n_samples
+    o, d = torch.empty(batch, 3, device=dev), torch.empty(batch, 3, device=dev)
+    rgba = torch.empty(batch, 4, device=dev) if (want_rgba or bg is None) else None
+    target = torch.empty(batch, 3, device=dev) if bg is not None else None
+    z = torch.empty(batch, n_samples, device=dev)
+    slots = torch.empty(n, device=dev, dtype=torch.int32)
+    pts, dirs = torch.empty(n, 3, device=dev), torch.empty(n, 3, device=dev)
+    key = (dev, _stream())
+    chain = _COMPACT_CHAIN.get(key)
+    if chain is None:
+        chain = _COMPACT_CHAIN[key] = _CompactChain(dev)
+    turn, slot, seq = chain.next()
+    _lib.check(lib.nerf_train_batch_compact_chain(_p(images), _p(poses), n_img, H, W, float(focal), float(scene_scale),
+                                                  _p(None if bg is None else _dev(bg, "bg")), int(seed), counter, int(first_ray), batch,
+                                                  n_samples, float(near), float(far), _p(grid), grid.shape[0], float(bound), _p(o), _p(d),
+                                                  _p(rgba), _p(target), _p(z), _p(slots), _p(pts), _p(dirs), _p(chain.state), turn,
+                                                  chain.host[slot].data_ptr(), seq, _stream()), "nerf_train_batch_compact_chain")
+    import weakref
+    out = CompactedSamples(z, slots, pts, dirs, chain.host_np[slot], None, seq=seq)
+    chain.owner[slot] = weakref.ref(out)
+    return o, d, (target if bg is not None else rgba), out
+
+
 class _CompositeIndexed(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rgb_c, sigma_c, slots, z, rays_d, bg):

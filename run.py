@@ -29,6 +29,9 @@ from src.renderer import DensityGrid, render_image, render_rays, render_rays_ner
 from src.utils import TensorBoardLogger, compute_psnr, compute_psnr_torch, render_image_safe
 
 
+GRID_FUSED_BATCH = True      # train_density_grid: the grid step's batch from nerf_train_batch_compact
+
+
 def _target(rgba, bg):
     rgb, a = rgba[:, :3], rgba[:, 3:4]
     return rgb * a + bg * (1.0 - a)
@@ -70,6 +73,12 @@ def run_part2(cfg, args):
         if not getattr(model.decoder, "fused", False):
             raise ValueError("use_density_grid: true needs the default decoder shape (hidden 256, 8 layers, skip 4, view 128)")
         grid = DensityGrid(cfg.get("grid_resolution", 128), cfg.get("scene_bound", 1.5), cfg.get("grid_threshold", 0.01)).to(device)
+    # train_density_grid: true (default false) -- after grid_warmup_iters dense steps the training steps go through the grid too:
+    # only the active samples reach the decoder's forward and backward (VanillaNerfEngine's grid step)
+    train_grid = bool(cfg.get("train_density_grid", False)) and not args.eval_only
+    if train_grid and grid is None:
+        raise ValueError("train_density_grid: true needs use_density_grid: true (the steps go through the grid that is saved with the "
+                         "checkpoints and used for evaluation)")
     if args.checkpoint:
         ckpt = torch.load(args.checkpoint, map_location=device)
         model.load_state_dict(ckpt["model_state_dict"])
@@ -117,7 +126,80 @@ def run_part2(cfg, args):
             say(f">>> Part 2 on the fused HIP shape engine ({p2_eng.params.numel()} parameters)")
         else:
             say(f">>> Part 2 engine not used: {why}; training on the module path")
-    if use_engine:
+    if train_grid and p2_eng is not None:
+        raise ValueError("train_density_grid: true: the shape engine (engine: true at a non-default decoder shape) has no grid step; "
+                         "only the default-shape engine trains through the grid")
+    if train_grid and not use_engine:
+        raise ValueError("train_density_grid: true: the module path (engine: false, or a non-default decoder shape) has no grid step; "
+                         "only the default-shape engine trains through the grid")
+    if use_engine and train_grid:
+        from project_nerf_amd.engine import VanillaNerfEngine
+        from project_nerf_amd.flat_engine import grid_refresh_due
+        tb = TensorBoardLogger(os.path.join(log_dir, "tensorboard")) if main_rank else None
+        seed = int(cfg.get("seed", 0) or 0)
+        eng = VanillaNerfEngine(params=dec.flat_parameters(), device=str(device), lr=lr, near=near, far=far, white_bkgd=white_bkgd,
+                                seed=seed, world_size=world, grid_resolution=grid.resolution, bound=grid.bound,
+                                grid_threshold=grid.threshold)
+        sync_async = parallel.allreduce_sum_async if world > 1 else None
+        warm, stop = cfg.get("grid_warmup_iters", 256), cfg.get("grid_stop_ratio", 0.9)
+        # the batch of a grid step from ONE kernel (train_batch_compact) or from two (train_batch + prepare_batch): DESIGN.md 4.21
+        # has both timings; `grid_fused_batch:` overrides the default
+        fused_batch = bool(cfg.get("grid_fused_batch", GRID_FUSED_BATCH))
+
+        def sync_model():
+            model.load_state_dict({**model.state_dict(), **eng.state_dict("decoder.")})
+            if eng.binary_grid is not None:      # (save_checkpoint refreshes the DensityGrid from the weights it saves)
+                grid.grid, grid.binary_grid = eng.grid.clone(), eng.binary_grid.clone()
+
+        def draw(counter):
+            # every rank forms and compacts rays [first_ray, first_ray + local_batch) of the step's global batch
+            if fused_batch:
+                return train_set.train_batch_compact(local_batch, n_samples, near, far, eng.bg, seed, counter, eng.binary_grid, eng.bound,
+                                                     first_ray=first_ray)
+            o, d, target, _ = train_set.train_batch(local_batch, n_samples, near, far, eng.bg, seed=seed, counter=counter,
+                                                    first_ray=first_ray)
+            return o, d, target, eng.prepare_batch(o, d, n_samples, first_ray=first_ray)
+
+        active, ahead = 1.0, []
+        for step in range(1, train_iters + 1):
+            through_grid = eng.binary_grid is not None
+            if through_grid:
+                # the batch was drawn and compacted ONE step ahead: its active count arrived while the previous step computed
+                if not ahead:
+                    ahead.append(draw(step))
+                rays_o, rays_d, target, prepared = ahead.pop()
+                if step < train_iters:
+                    ahead.append(draw(step + 1))
+                loss = eng.train_step(rays_o, rays_d, target, n_samples, prepared=prepared, sync_grads_async=sync_async)
+            else:
+                rays_o, rays_d, target, z = train_set.train_batch(local_batch, n_samples, near, far, eng.bg, seed=seed, counter=step,
+                                                                  first_ray=first_ray)
+                loss = eng.train_step(rays_o, rays_d, target, n_samples, z=z, sync_grads_async=sync_async)
+            if step % log_every == 0:
+                loss_val = parallel.mean_over_ranks(loss).item()
+                psnr = compute_psnr(loss_val)
+                say(f">>> Step {step}/{train_iters} | Loss {loss_val:.6f} | PSNR {psnr:.2f} dB"
+                    + (f" | Skip: {(1 - active) * 100:.1f}%" if through_grid else " | dense"))
+                if tb is not None:
+                    tb.log_scalar("Train/Loss", loss_val, step)
+                    tb.log_scalar("Train/PSNR", psnr, step)
+            if grid_refresh_due(step, train_iters, warm, stop):
+                ratio = eng.update_grid()       # (replicated: every rank holds the same weights)
+                ahead.clear()                   # the waiting batch was compacted against the previous grid
+                if ratio > 0.0:
+                    active = ratio
+                    say(f">>> Density grid: refreshed after step {step} ({ratio * 100:.1f} % of the cells occupied)")
+                else:
+                    say(f">>> Density grid: no cell above the threshold after step {step}; the previous grid stays"
+                        + ("" if eng.binary_grid is not None else " (dense steps go on)"))
+            if save_every and step % save_every == 0 and main_rank:
+                sync_model()
+                save_checkpoint(os.path.join(ckpt_dir, f"model_step_{step:06d}.pth"))
+        sync_model()
+        if main_rank:
+            save_checkpoint(os.path.join(ckpt_dir, "model_final.pth"))
+            tb.close()
+    elif use_engine:
         from project_nerf_amd.engine import VanillaNerfEngine
         tb = TensorBoardLogger(os.path.join(log_dir, "tensorboard")) if main_rank else None
         eng = VanillaNerfEngine(params=dec.flat_parameters(), device=str(device), lr=lr, near=near, far=far, white_bkgd=white_bkgd,
