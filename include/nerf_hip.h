@@ -48,7 +48,8 @@ extern "C" {
 /* 9: nerf_p4_infer_workspace_bytes, the evaluation size of the Part 4 workspace, is new. */
 /* 10: the vanilla field's evaluation through an occupancy grid as one launch chain, nerf_render_rays_grid_*, is new. */
 /* 11: the data side of a training step through the occupancy grid in one launch, nerf_train_batch_compact*, is new. */
-#define NERF_ABI_VERSION 11
+/* 12: the Instant-NGP occupancy-grid refresh as one density-only launch chain, nerf_instant_grid_update*, is new. */
+#define NERF_ABI_VERSION 12
 
 typedef void* nerf_stream_t;
 
@@ -239,6 +240,38 @@ int nerf_grid_lattice(float bound, int resolution, float* pts_out, nerf_stream_t
 int nerf_grid_update(const float* sigma, float* grid, uint8_t* binary_grid, int64_t n_cells,
                      float decay, int dynamic, float threshold, unsigned long long* active_count,
                      nerf_stream_t stream);
+
+/* ---- a12 + a7 + a8: refresh of the Instant-NGP field's occupancy grid as one density-only launch chain ----
+ * replaces DensityGrid.update around the hash-grid field (src/renderer.py:35-132), the density query being
+ * the sigma-net part of InstantNeRFDecoder.forward (src/decoders.py:148-153) behind the hash encoding.  On the caller's
+ * stream: clear *active_count, then per slab of `slab_cells` cells: hash gather into a bf16 operand image ->
+ * sigma-net chain (S1, S2 of nerf_imlp_fwd only) whose epilogue folds sigma into grid / binary_grid and
+ * counts the active cells.  2 * ceil(n_cells / slab_cells) + 1 enqueues, no lattice tensor, no rgb, no view
+ * directions, no allocation, no host read: the call can be captured in a hipGraph as a linear chain.
+ * After the call grid, binary_grid and *active_count hold the same BITS as nerf_grid_lattice ->
+ * nerf_hash_encode_fwd* (bf16 operand image) -> nerf_imlp_fwd(train = 0) -> nerf_grid_update leave, for
+ * either table type, either fold and any slab size: the same arithmetic on the same values in the same order.
+ *   packed: nerf_imlp_pack's image.  table_f32 / table_f16 (exactly one), n_levels (16: the default-shape
+ *   chain is the one wired) ... dense_host, hash_bound: as nerf_hash_encode_fwd_nat.
+ *   Point source.  pts == NULL: cell c is node (c / res^2, (c / res) % res, c % res) of nerf_grid_lattice's
+ *   lattice for `resolution` (2..32768) and grid_bound; n_cells must equal resolution^3.  pts != NULL:
+ *   [n_cells,3] points (a dynamic field's deformed lattice); resolution must be 0, grid_bound is unused;
+ *   n_cells == 0 is then a successful no-op.
+ *   grid [n_cells] in/out: overwritten (dynamic == 0: never read), or max(grid * decay, sigma); binary_grid
+ *   [n_cells] bytes = grid > threshold; *active_count (device u64) = number of set cells.
+ *   slab_cells: a positive multiple of 128 with slab_cells * 32 < 2^31.
+ *   workspace: nerf_instant_grid_update_workspace_bytes(slab_cells) bytes, 256-byte aligned, contents
+ *   irrelevant: ONE slab's operand image [roundup(slab_cells,128), 32] bf16 (64 bytes per cell), rounded up to
+ *   256 bytes, reused by every slab of the call (stream order serialises them).  The query returns 0 for
+ *   slab_cells <= 0. */
+size_t nerf_instant_grid_update_workspace_bytes(int64_t slab_cells);
+int nerf_instant_grid_update(const void* packed, const float* table_f32, const void* table_f16, int n_levels,
+                             const float* scale_host, const unsigned* res_host, const unsigned* size_host,
+                             const unsigned* offset_host, const unsigned* dense_host, float hash_bound,
+                             const float* pts, int64_t n_cells, int resolution, float grid_bound,
+                             float* grid, uint8_t* binary_grid, float decay, int dynamic, float threshold,
+                             unsigned long long* active_count, int64_t slab_cells, void* workspace,
+                             nerf_stream_t stream);
 
 /* ---- a5: Fourier features ---------------------------------------------------
  * replaces FourierRepresentation.forward (src/embeddings.py:22-32).

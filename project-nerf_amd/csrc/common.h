@@ -66,6 +66,15 @@ int hash_fwd_counted(const float* pts, const unsigned* count, int64_t capacity, 
                      const unsigned* offset_host, const unsigned* dense_host, float bound, void* out_nat, nerf_stream_t stream);
 int imlp_fwd_counted(const void* packed, const void* hash_nat, const float* dirs, const unsigned* count, int64_t capacity, float* rgb,
                      float* sigma, nerf_stream_t stream);
+// The two launches of nerf_instant_grid_update (grid.hip) per slab of occupancy-grid cells.  hashgrid.hip: bf16 operand image
+// [roundup(n_cells, 128), 32] of cells cell0 .. cell0 + n_cells - 1 of the res^3 lattice, the points formed from the cell index;
+// imlp.hip: the sigma-net alone on that image, folded into grid / binary_grid (already offset to the slab's first cell) with
+// nerf_grid_update's arithmetic, active cells added to *active_count (cleared by the caller).
+int hash_fwd_lattice(int64_t cell0, int64_t n_cells, int resolution, float grid_bound, const float* table_f32, const void* table_f16,
+                     int n_levels, const float* scale_host, const unsigned* res_host, const unsigned* size_host,
+                     const unsigned* offset_host, const unsigned* dense_host, float bound, void* out_nat, nerf_stream_t stream);
+int imlp_sigma_grid(const void* packed, const void* hash_nat, int64_t n_cells, float* grid, uint8_t* binary_grid, float decay, int dynamic,
+                    float threshold, unsigned long long* active_count, nerf_stream_t stream);
 // mlp_fwd.hip: the 8x256 inference chain in point mode (64 samples per wave) on the first *count rows of pts / dirs, for
 // render_grid.hip's launch chain
 int mlp_fwd_counted(const void* packed, const float* pts, const float* dirs, const unsigned* count, int64_t capacity, float* rgb,

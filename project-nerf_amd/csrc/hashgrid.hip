@@ -13,6 +13,7 @@
 // Infinity Cache.  Backward: 16 float atomics per (point, level).
 #include <stdlib.h>
 #include "common.h"
+#include "lattice.h"
 
 namespace nerf {
 
@@ -229,6 +230,42 @@ hash_fwd_counted_kernel(const float* __restrict__ pts, const unsigned* __restric
   for (int64_t p = lc.chunk * (int64_t)blockDim.x + threadIdx.x; p < n_pad; p += (int64_t)lc.chunks * blockDim.x) {
     const int64_t ps = p < n ? p : n - 1;
     const Corner c = corners_of(L, lvl, pts[ps * 3 + 0], pts[ps * 3 + 1], pts[ps * 3 + 2]);
+    float f0 = 0.0f, f1 = 0.0f;
+    float2 v[8];
+    gather_cell(table, c, v);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {                           // the sums run over the corners in the reference's order
+      f0 += c.w[k] * v[k].x;
+      f1 += c.w[k] * v[k].y;
+    }
+    const int f = 2 * lvl, ks = f >> 4, h = (f >> 3) & 1, j = f & 7;
+    const int64_t wt = p >> 5;
+    const int col = (int)(p & 31);
+    const int n_ks = (2 * L.n_levels + 15) / 16;
+    __bf16* dst = out_nat + ((wt * n_ks + ks) * 64 + 2 * col + h) * 8 + j;
+    dst[0] = (__bf16)f0;
+    dst[1] = (__bf16)f1;
+  }
+}
+
+// hash_fwd_counted_kernel's bf16 operand image for points that are never written out: point p of the slab is cell cell0 + p of the
+// occupancy grid's 'ij' lattice (nerf_instant_grid_update; lattice.h gives the node coordinates nerf_grid_lattice would store).
+// n (> 0) cells, known to the host; pad rows up to the 128-row tile repeat the slab's last cell.  Same corners, same gathers, same
+// eight-term sums in the same order, same rounding and operand address as hash_fwd_kernel.
+template <class TableT>
+__global__ void __launch_bounds__(256)
+hash_fwd_lattice_kernel(int64_t cell0, int64_t n, int res, float grid_bound, float step, const TableT* __restrict__ table,
+                        HashLevels L, __bf16* __restrict__ out_nat, int n_chunks) {
+  const int64_t n_pad = (n + 127) / 128 * 128;
+  const LevelChunk lc = level_chunk(L.n_levels, n_chunks);
+  if (lc.lvl >= L.n_levels) return;
+  const int lvl = lc.lvl;
+  for (int64_t p = lc.chunk * (int64_t)blockDim.x + threadIdx.x; p < n_pad; p += (int64_t)lc.chunks * blockDim.x) {
+    const int64_t ps = p < n ? p : n - 1;
+    int ix, iy, iz;
+    lattice_cell(cell0 + ps, res, ix, iy, iz);
+    const Corner c = corners_of(L, lvl, lattice_node(ix, res, grid_bound, step), lattice_node(iy, res, grid_bound, step),
+                                lattice_node(iz, res, grid_bound, step));
     float f0 = 0.0f, f1 = 0.0f;
     float2 v[8];
     gather_cell(table, c, v);
@@ -1300,6 +1337,33 @@ int nerf::hash_fwd_counted(const float* pts, const unsigned* count, int64_t capa
     hipLaunchKernelGGL(hash_fwd_counted_kernel<float2>, grid, dim3(256), lds, as_stream(stream), pts, count, capacity,
                        reinterpret_cast<const float2*>(table_f32), L, static_cast<__bf16*>(out_nat), n_chunks);
   return check_launch("nerf_instant_render_rays_fwd (hash)");
+}
+
+// The operand-image forward of a slab of occupancy-grid cells (common.h; called by grid.hip's nerf_instant_grid_update, which has
+// checked its arguments): hash_fwd_impl's launch shape, sized by the slab.
+int nerf::hash_fwd_lattice(int64_t cell0, int64_t n_cells, int resolution, float grid_bound, const float* table_f32, const void* table_f16,
+                           int n_levels, const float* scale_host, const unsigned* res_host, const unsigned* size_host,
+                           const unsigned* offset_host, const unsigned* dense_host, float bound, void* out_nat, nerf_stream_t stream) {
+  NERF_REQUIRE(cell0 >= 0 && n_cells > 0 && resolution >= 2 && out_nat && (table_f32 == nullptr) != (table_f16 == nullptr) && scale_host &&
+               res_host && size_host && offset_host && dense_host, "hash_fwd_lattice: bad arguments");
+  HashLevels L;
+  if (int rc = fill_levels(L, LEVEL_ARGS); rc != NERF_OK) return rc;
+  const int64_t n_pad = (n_cells + 127) / 128 * 128;
+  int64_t blocks = (n_pad + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  const int lds_kb = options().hash_fwd_lds_kb;                      // occupancy throttle, see hash_fwd_impl
+  const int lds = (lds_kb < 0 ? 0 : (lds_kb > 64 ? 64 : lds_kb)) * 1024;
+  const bool xcd = options().hash_xcd != 0;
+  const dim3 grid = level_chunk_grid(n_levels, blocks, xcd);
+  const int n_chunks = xcd ? (int)blocks : 0;
+  const float step = lattice_step(grid_bound, resolution);
+  if (table_f16 != nullptr)
+    hipLaunchKernelGGL(hash_fwd_lattice_kernel<half2_t>, grid, dim3(256), lds, as_stream(stream), cell0, n_cells, resolution, grid_bound, step,
+                       static_cast<const half2_t*>(table_f16), L, static_cast<__bf16*>(out_nat), n_chunks);
+  else
+    hipLaunchKernelGGL(hash_fwd_lattice_kernel<float2>, grid, dim3(256), lds, as_stream(stream), cell0, n_cells, resolution, grid_bound, step,
+                       reinterpret_cast<const float2*>(table_f32), L, static_cast<__bf16*>(out_nat), n_chunks);
+  return check_launch("nerf_instant_grid_update (hash)");
 }
 
 extern "C" int nerf_hash_encode_fwd(const float* pts, int64_t n, const float* table, int n_levels,

@@ -8,8 +8,9 @@
 //
 // The resident-weight register chain of resident_chain.h: 32 samples per wave on the MFMA
 // column, activations carried as accumulator tiles -> bf16 B fragments.  All 26 (forward) /
-// 20 (transposed) weight fragments stay resident in LDS for the whole launch.  The two kernel
-// bodies are instant_chain_body.h's (shared with p4mlp.hip's canonical chain) under IPolicy.
+// 20 (transposed) weight fragments stay resident in LDS for the whole launch.  The kernel
+// bodies are instant_chain_body.h's (shared with p4mlp.hip's canonical chain) under IPolicy; its
+// density-only body (S1, S2: 8 fragments) is the chain of nerf_instant_grid_update.
 // Parameter vector (fp32, [out,in] row-major, bias-free):
 //   sigma_net : W1 [64,32] | W2 [16,64]                       = 3072
 //   color_net : W1 [64,48] (cols 43..47 unused) | W2 [64,64] | W3 [16,64] (rows 3..15 unused) = 8192
@@ -94,6 +95,12 @@ struct IPolicy {
   static constexpr bool kZeroGrads = true, kFence = true;
   using V = bf16x8;
   using Mfma = MfmaBf;
+  // the sigma-net's input alone (instant_sigma): the two natural k-steps of the hash operand image
+  template <class A>
+  static __device__ __forceinline__ void sigma_operands(const A& a, int64_t wt, int col, int half, bf16x8 (&hin)[2]) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) hin[ks] = load_nat<bf16x8>(a.hash_nat, wt, 2, ks, col, half);
+  }
   template <bool TRAIN>
   static __device__ __forceinline__ void operands(const IArgs& a, int64_t wt, int64_t nc, int col, int half, bf16x8 (&hin)[2], bf16x8 (&denc)[2]) {
     if (a.x_enc != nullptr) {
@@ -136,6 +143,24 @@ __global__ void __launch_bounds__(kIThreads) imlp_fwd_counted_kernel(const IArgs
   a.n_pad = (n + kITile - 1) / kITile * kITile;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
   instant_forward<IPolicy, false>(a, smem, tid, lane, wave, col, half);
+}
+
+// The occupancy-grid refresh's chain (nerf_instant_grid_update): sigma-net only on a slab's operand image, folded into the grid
+struct ISigmaArgs {
+  const char* packed;
+  const __bf16* hash_nat;   // nat blocks [n_pad,32] of the slab's cells
+  int64_t n, n_pad;
+  float* grid;              // [n] in/out, the slab's cells
+  uint8_t* binary;          // [n]
+  float decay; int dynamic; float threshold;
+  unsigned long long* count;
+};
+constexpr int kISigmaFrags = istep(2).frag0;     // S1 and S2: the first 8 of the 26 forward fragments
+
+__global__ void __launch_bounds__(kIThreads) imlp_sigma_grid_kernel(const ISigmaArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
+  instant_sigma<IPolicy>(a, smem, tid, lane, wave, col, half);
 }
 
 __global__ void __launch_bounds__(kIThreads) imlp_bwd_kernel(const IArgs a) {
@@ -225,6 +250,23 @@ int nerf::imlp_fwd_counted(const void* packed, const void* hash_nat, const float
   if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_instant_render_rays_fwd: cannot query device");
   hipLaunchKernelGGL(imlp_fwd_counted_kernel, dim3(grid), dim3(kIThreads), kIFwdFrags * 1024, as_stream(stream), a, count, capacity);
   return check_launch("nerf_instant_render_rays_fwd (decoder)");
+}
+
+// the density-only chain of one slab of grid cells (common.h; grid.hip's nerf_instant_grid_update has checked its arguments)
+int nerf::imlp_sigma_grid(const void* packed, const void* hash_nat, int64_t n_cells, float* grid, uint8_t* binary_grid, float decay, int dynamic,
+                          float threshold, unsigned long long* active_count, nerf_stream_t stream) {
+  NERF_REQUIRE(n_cells > 0 && packed && hash_nat && grid && binary_grid && active_count, "imlp_sigma_grid: bad arguments");
+  ISigmaArgs a{};
+  a.packed = static_cast<const char*>(packed);
+  a.hash_nat = static_cast<const __bf16*>(hash_nat);
+  a.n = n_cells; a.n_pad = (n_cells + kITile - 1) / kITile * kITile;
+  a.grid = grid; a.binary = binary_grid; a.decay = decay; a.dynamic = dynamic; a.threshold = threshold; a.count = active_count;
+  // two workgroups per CU: every workgroup ends with one atomic on the count word, and those retire one after the other (~11 ns each) --
+  // measured on a 2^18-cell slab: 1 per CU 13.5 us, 2: 12.8, 4: 17.3, 8: 28.7
+  const int wgs = grid_for(a.n_pad / kITile, 2);
+  if (wgs <= 0) return fail(NERF_ELAUNCH, "nerf_instant_grid_update: cannot query device");
+  hipLaunchKernelGGL(imlp_sigma_grid_kernel, dim3(wgs), dim3(kIThreads), kISigmaFrags * 1024, as_stream(stream), a);
+  return check_launch("nerf_instant_grid_update (sigma-net)");
 }
 
 extern "C" int nerf_imlp_fwd_encoded(const void* packed, void* workspace, const float* x_enc, const float* d_enc, int64_t n,

@@ -1,4 +1,4 @@
-// The two kernel bodies of the Instant-NGP decoder at its default shape (sigma-net 64 -> 16, colour-net [16 | 32] -> 64 -> 64 -> 3),
+// The kernel bodies (forward, density only, dgrad) of the Instant-NGP decoder at its default shape (sigma-net 64 -> 16, colour-net [16 | 32] -> 64 -> 64 -> 3),
 // on the blocks of resident_chain.h.  imlp.hip (Part 2, bf16 operands, hash features only) and p4mlp.hip's canonical chain (Part 4,
 // fp16 forward operands, [hash | time code] into the sigma-net) instantiate them; each keeps its __global__ wrappers, argument
 // struct, step table and C entries.  imlp_shapes.hip (row-major images, wider masks, run-time widths) keeps its own bodies.
@@ -9,6 +9,7 @@
 //   P::V, P::Mfma                    forward operand vector and MFMA (bf16x8 / MfmaBf, f16x8 / Mfma16)
 //   P::kSigmaKs                      natural k-steps of the sigma-net's input
 //   P::operands<TRAIN>(a, wt, nc, col, half, sin, denc)   forms both inputs and (TRAIN) writes their bf16 images
+//   P::sigma_operands(a, wt, col, half, sin)              forms the sigma-net's input alone (instant_sigma; only where it is instantiated)
 //   P::kFence                        forward: run_step's FENCE (one m-tile at a time)
 //   P::kZeroGrads (P::kParams)       the dgrad kernel clears a.zero_grads[0, kParams) for the weight-gradient launch behind it
 // The argument struct is passed BY VALUE and tid .. half are formed in the __global__ wrapper (by reference, the
@@ -53,6 +54,59 @@ __device__ __forceinline__ void instant_forward(const A a, char* smem, int tid, 
       if (live && half == 0) head_rgb_store(a.rgb, n, acc);
     });
     if constexpr (TRAIN) a.mask[tile * kInstantThreads + tid] = make_uint4(mw[0], mw[1], mw[2], 0);
+  }
+}
+
+// Density only, folded into an occupancy grid (nerf_instant_grid_update): instant_forward's geometry, S1 and S2 alone -- the same
+// operands, MFMAs and fence, so h0 is the forward's bit for bit; no direction code, no colour-net, no stash, no mask.  Only the
+// fragments of S1 and S2 are resident: the prefix of the forward fragment stream (P::step_of(S2) ends it).  Row n of the image is
+// cell n of a.grid / a.binary (the caller offsets both to the slab's first cell).  Epilogue = grid_update_kernel's arithmetic
+// (grid.hip; reference src/renderer.py:118-132) on the lane that owns acc[0] of a live row; every thread counts its active cells
+// over its whole tile loop: one reduction and one 64-bit atomic per workgroup at the kernel's end, none per tile.
+// P adds: P::sigma_operands(a, wt, col, half, sin) forms the sigma-net's input alone.
+// A: packed, n, n_pad, grid, binary, decay, dynamic, threshold, count (+ what P::sigma_operands reads).
+template <class P, class A>
+__device__ __forceinline__ void instant_sigma(const A a, char* smem, int tid, int lane, int wave, int col, int half) {
+  using V = typename P::V;
+  const typename P::Mfma mfma{};
+  constexpr Step s2 = P::step_of(P::S2);
+  constexpr int kFrags = s2.frag0 + s2.mt * (s2.ks_acc + s2.ks_nat) - P::kFwd0;
+  static_assert(P::step_of(P::S1).frag0 == P::kFwd0 && kFrags > 0 && kFrags <= P::kFwdN, "S1, S2 lead the forward fragment stream");
+  const char* wbase = resident_weights<kInstantThreads>(smem, a.packed, P::kFwd0, kFrags, tid, lane);
+  __syncthreads();
+  const int64_t n_tiles = a.n_pad / kInstantTile;
+  unsigned long long active = 0;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const int64_t wt = tile * 4 + wave, n = wt * 32 + col;
+    const bool live = n < a.n;
+    V sin[P::kSigmaKs];
+    P::sigma_operands(a, wt, col, half, sin);
+    uint32_t mw = 0;
+    V hs1[4];
+    run_step<P::step_of, P::S1, P::kSigmaKs, P::kFence>(wbase, sin, nullptr, mfma, relu_epilogue<false>(hs1, (__bf16*)nullptr, mw, wt, col, half));
+    float h0 = 0.0f;
+    run_step<P::step_of, P::S2, 4, P::kFence>(wbase, hs1, nullptr, mfma, [&](auto, f32x16 acc) { h0 = acc[0]; });
+    if (live && half == 0) {
+      float v = head_sigma(h0);
+      if (a.dynamic) v = fmaxf(a.grid[n] * a.decay, v);
+      a.grid[n] = v;
+      const bool on = v > a.threshold;
+      a.binary[n] = on ? 1 : 0;
+      active += on ? 1 : 0;
+    }
+  }
+  // one wave reduction, then ONE 64-bit atomic per workgroup: with one per wave (grid_update_kernel's form) the 4096 same-address
+  // atomics of a 2^18-cell slab, retiring one after the other in L2, were the kernel -- 53.8 us against 17.6 us for the whole decoder
+  // on the same rows
+  for (int off = 32; off > 0; off >>= 1) active += __shfl_xor(active, off);
+  __shared__ unsigned long long wave_active[kInstantThreads / 64];
+  if (lane == 0) wave_active[wave] = active;
+  __syncthreads();
+  if (tid == 0) {
+    unsigned long long total = 0;
+#pragma unroll
+    for (int w = 0; w < kInstantThreads / 64; ++w) total += wave_active[w];
+    if (total) atomicAdd(a.count, total);
   }
 }
 

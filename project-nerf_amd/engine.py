@@ -381,6 +381,7 @@ class InstantNgpEngine:
         self.g_net = torch.empty_like(self.net)
         self._hash_ws = None
         self._chain_ws = {}            # render_image(chain=True): one workspace per (chunk, n_samples)
+        self._grid_ws = None           # update_grid(chain=True): one slab's operand image
         # fp16 copy of the table for the forward gathers (tinycudann evaluates its grid from fp16 parameters next to
         # the fp32 master copy too): written by the optimiser kernel, refreshed here whenever torch code has
         # touched ``self.table`` in place (tensor version counter); cfg half_table: false keeps fp32 gathers
@@ -680,8 +681,12 @@ class InstantNgpEngine:
         return loss
 
     @torch.no_grad()
-    def update_grid(self) -> float:
-        """DensityGrid.update for a static field (reference src/renderer.py:35-132)."""
+    def update_grid(self, chain: bool = False) -> float:
+        """DensityGrid.update for a static field (reference src/renderer.py:35-132).  ``chain=True``: the refresh as ONE
+        density-only launch chain (nerf_instant_grid_update) -- no lattice tensor, no colour-net, one workspace kept on the
+        engine; the same bits as the loop."""
+        if chain:
+            return self._update_grid_chain()
         res = self.grid.shape[0]
         pts = ops.grid_lattice(self.bound, res, self.device)
         sig = torch.empty(res ** 3, device=self.device)
@@ -692,6 +697,19 @@ class InstantNgpEngine:
         self.grid = sig.view(res, res, res)
         self.binary_grid, ratio = ops.grid_threshold(self.grid, self.grid_threshold)
         return ratio
+
+    _GRID_SLAB = 2 ** 18       # cells per slab of the chain refresh: the loop form's batch
+
+    def _update_grid_chain(self) -> float:
+        res = self.grid.shape[0]
+        if self._grid_ws is None:
+            self._grid_ws = torch.empty(ops.instant_grid_update_workspace_bytes(self._GRID_SLAB), dtype=torch.uint8, device=self.device)
+        # NEW grid tensors, allocated while the old ones are alive: the speculative hash backward recognises a new grid by
+        # (data_ptr, _version) of binary_grid, and a raw kernel store into the old tensor would change neither
+        grid, binary, count = ops.instant_grid_update(self.packed, self._gather_table(), self.levels, self.bound, res, self.bound,
+                                                      self.grid_threshold, slab_cells=self._GRID_SLAB, workspace=self._grid_ws)
+        self.grid, self.binary_grid = grid, binary
+        return float(count.item()) / binary.numel()      # the one host sync the loop form also has
 
     @torch.no_grad()
     def render_rays(self, rays_o: Tensor, rays_d: Tensor, n_samples: int):

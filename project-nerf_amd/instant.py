@@ -126,6 +126,11 @@ def run_instant(cfg, args):
                 f"{cfg.get('hidden_dim', 64)}, L_embed_dir {cfg.get('L_embed_dir', 4)})")
         else:
             say(f">>> Part 2 Instant shape engine not used: {why}; training on the module path")
+    # grid_update_chain: true -- occupancy-grid refreshes through InstantNgpEngine.update_grid(chain=True), one density-only launch chain
+    grid_chain = bool(cfg.get("grid_update_chain", False))
+    if grid_chain and not args.eval_only and not use_engine:
+        raise ValueError("grid_update_chain: true needs engine: true, use_density_grid and the default shape (16 levels x 2 features, "
+                         "hidden_dim 64): the refresh chain is the flat-parameter engine's")
     if use_engine or shape_engine:
         from .engine import InstantNgpEngine
         if shape_engine:
@@ -187,7 +192,7 @@ def run_instant(cfg, args):
             if step < iters * stop:
                 interval = 32 if step < iters * 0.1 else (128 if step < iters * 0.5 else 512)
                 if step >= warm and step % interval == 0:
-                    active = eng.update_grid()
+                    active = eng.update_grid(chain=grid_chain)
                     ahead.clear()                           # the waiting batch was compacted against the previous grid
             if step % log_every == 0:
                 loss_val = parallel.mean_over_ranks(loss_rgb).item()

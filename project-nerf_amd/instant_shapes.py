@@ -173,5 +173,9 @@ class InstantShapeEngine(InstantNgpEngine):
         raise NotImplementedError("render_image(chain=True): the evaluation launch chain (nerf_instant_render_rays_fwd) is wired for the "
                                   "default shape's decoder kernel; the shape engine's chain is another kernel -- use chain=False")
 
+    def _update_grid_chain(self) -> float:
+        raise NotImplementedError("update_grid(chain=True): the density-only refresh chain (nerf_instant_grid_update) is wired for the "
+                                  "default shape's sigma-net kernel; the shape engine's chain is another kernel -- use chain=False")
+
     def enable_sharded_optimizer(self, rank: int) -> None:
         raise NotImplementedError("the sharded optimiser stays with the default shape's engine")

@@ -1095,6 +1095,64 @@ def instant_render_rays_fwd(packed: Tensor, table: Tensor, levels: HashLevelTabl
     return out, depth, acc
 
 
+def instant_grid_update_workspace_bytes(slab_cells: int) -> int:
+    return _lib.load().nerf_instant_grid_update_workspace_bytes(slab_cells)
+
+
+def instant_grid_update(packed: Tensor, table: Tensor, levels: HashLevelTable, hash_bound: float, source, grid_bound: float,
+                        threshold: float, prev: Optional[Tensor] = None, decay: float = 1.0, slab_cells: int = 2 ** 18,
+                        workspace: Optional[Tensor] = None):
+    """Occupancy-grid refresh of the Instant-NGP field as one density-only launch chain (nerf_instant_grid_update): per slab of
+    ``slab_cells`` cells a hash gather and the sigma-net chain, whose epilogue thresholds and counts -- no lattice tensor, no rgb,
+    no allocation or host read between the launches.  ``source``: an int, the grid's resolution (the cells are the nodes of
+    grid_lattice(grid_bound, resolution)), or a [n,3] tensor of points (a dynamic field's deformed lattice).  ``table``: fp32
+    [entries, 2] or its fp16 copy.  ``prev``: running maximum max(prev * decay, sigma), updated IN PLACE as grid_threshold does;
+    without it new tensors are allocated.  ``workspace``: uint8, at least instant_grid_update_workspace_bytes(slab_cells) bytes.
+    Returns (grid fp32, binary_grid bool, count int64 [1] on the device: no host sync here); grids are [res, res, res] or [n]."""
+    lib = _lib.load()
+    packed = _dev(packed, "packed", torch.uint8)
+    if not isinstance(table, Tensor) or table.dtype not in (torch.float32, torch.float16):
+        raise TypeError("instant_grid_update: table must be an fp32 or fp16 tensor")
+    half = table.dtype == torch.float16
+    table = _dev(table, "table", table.dtype)
+    if table.numel() < 2 * levels.entries:
+        raise ValueError(f"instant_grid_update: table of {table.numel()} values, the levels address {2 * levels.entries}")
+    if isinstance(source, Tensor):
+        pts = _dev(source, "pts")
+        if pts.dim() != 2 or pts.shape[1] != 3:
+            raise ValueError(f"instant_grid_update: pts of shape {tuple(pts.shape)}, expected [n, 3]")
+        res, shape = 0, (pts.shape[0],)
+    else:
+        pts, res = None, int(source)
+        if res < 2:
+            raise ValueError(f"instant_grid_update: resolution {res} (at least 2)")
+        shape = (res, res, res)
+    n = 1
+    for s in shape:
+        n *= s
+    slab_cells = int(slab_cells)
+    need = lib.nerf_instant_grid_update_workspace_bytes(slab_cells)
+    if prev is not None:
+        grid = _dev(prev, "prev")
+        if grid is not prev or grid.numel() != n:
+            raise ValueError("instant_grid_update: prev must be a contiguous tensor of one value per cell (it is updated in place)")
+    else:
+        grid = torch.empty(shape, device=packed.device, dtype=torch.float32)
+    if workspace is None:
+        workspace = torch.empty(need, device=packed.device, dtype=torch.uint8)
+    elif _dev(workspace, "workspace", torch.uint8).numel() < need:
+        raise ValueError(f"instant_grid_update: workspace of {workspace.numel()} bytes, {need} needed for slabs of {slab_cells} cells")
+    binary = torch.empty(shape, device=packed.device, dtype=torch.bool)
+    if n == 0:               # an empty point buffer (its data pointer is NULL: the entry would take it for the lattice source)
+        return grid, binary, torch.zeros(1, device=packed.device, dtype=torch.int64)
+    count = torch.empty(1, device=packed.device, dtype=torch.int64)      # cleared by the call
+    _lib.check(lib.nerf_instant_grid_update(_p(packed), None if half else _p(table), _p(table) if half else None, levels.n_levels,
+                                            *levels.host_args(), float(hash_bound), _p(pts), n, res, float(grid_bound), _p(grid), _p(binary),
+                                            float(decay), 0 if prev is None else 1, float(threshold), _p(count), slab_cells, _p(workspace),
+                                            _stream()), "nerf_instant_grid_update")
+    return grid, binary, count
+
+
 def instant_field(table: Tensor, net_params: Tensor, packed: Tensor, pts: Tensor, dirs: Tensor,
                   levels: HashLevelTable, bound: float):
     """rgb [n,3], sigma [n] for world-space points and unit view directions."""
