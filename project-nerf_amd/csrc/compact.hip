@@ -10,36 +10,58 @@
 // atomics serialise in L2 (one per wave: ~16 k per 2 M samples, most of the kernel's time in round 1;
 // one per 1024 samples: still 2048 of them, about half of the 38 us the kernel took).  Slot order is
 // arbitrary but consistent within a call.
-#include "common.h"
+// Depth, voxel test, slot reservation, row store and count hand-off are ray_front.h's, shared with sample.hip and
+// train_compact.hip.
+#include "ray_front.h"
 
 namespace nerf {
 
-__device__ __forceinline__ float lin01(int i, int n, float step) {
-  if (i < n / 2) return mul_rn(step, (float)i);
-  return __builtin_fmaf(-step, (float)(n - 1 - i), 1.0f);
-}
-__device__ __forceinline__ float depth_plain(int i, int n, float step, float near_p, float far_p) {
-  const float t = lin01(i, n, step);
-  return add_rn(mul_rn(near_p, sub_rn(1.0f, t)), mul_rn(far_p, t));
+// what the kernels below need of a call to form its samples
+struct CompactSampling {
+  const float* rays_o;
+  const float* rays_d;
+  const float* u;                 // [R, S] uniforms, or NULL
+  const uint8_t* grid;
+  float* z_out;
+  uint64_t key, counter, first_sample;
+  int S, res, draw;               // draw: the jitter comes from the counter-based generator (common.h) instead of u
+  float near_p, far_p, step, bound, scale;
+  bool small;                     // fewer than 2^31 samples: 64-bit division is emulated, ~100 instructions
+};
+
+__device__ __forceinline__ int64_t ray_of(int64_t g, int S, bool small) {
+  return small ? (int64_t)((unsigned)g / (unsigned)S) : g / S;
 }
 
-constexpr int kCompactThreads = 1024;
-constexpr int kCompactPer = 4;                          // samples per thread and pass: 4096 samples share one atomic
-constexpr int kCompactWaves = kCompactThreads / 64;
-static_assert(kCompactPer * kCompactWaves == 64, "the (k, wave) counts of a pass are scanned by one wave");
+// sample g of the call: its depth (stored to z_out), its point, and whether the point's voxel is occupied
+__device__ __forceinline__ bool compact_sample(const CompactSampling& c, int64_t g, float& px, float& py, float& pz) {
+  const float* __restrict__ rays_o = c.rays_o;
+  const float* __restrict__ rays_d = c.rays_d;
+  const int64_t r = ray_of(g, c.S, c.small);
+  const int s = (int)(g - r * c.S);
+  float z = plain_depth(s, c.S, c.step, c.near_p, c.far_p);
+  if (c.u != nullptr || c.draw)
+    z = jitter_depth(z, s, c.S, c.step, c.near_p, c.far_p,
+                     c.u != nullptr ? c.u[g] : squares_uniform(c.counter, c.first_sample + (uint64_t)g, c.key));
+  c.z_out[g] = z;
+  px = add_rn(rays_o[r * 3 + 0], mul_rn(rays_d[r * 3 + 0], z));
+  py = add_rn(rays_o[r * 3 + 1], mul_rn(rays_d[r * 3 + 1], z));
+  pz = add_rn(rays_o[r * 3 + 2], mul_rn(rays_d[r * 3 + 2], z));
+  return voxel_active(c.grid, c.res, c.bound, c.scale, px, py, pz);
+}
+
 __global__ void __launch_bounds__(kCompactThreads)
-sample_compact_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d, const float* __restrict__ u,
-                      int64_t n_rays, int S, float near_p, float far_p, float step,
-                      const uint8_t* __restrict__ grid, int res, float bound, float scale,
-                      float* __restrict__ z_out, int* __restrict__ slot_of_sample,
-                      float* __restrict__ pts_c, float* __restrict__ dirs_c, unsigned* __restrict__ count,
-                      uint64_t key, uint64_t counter, int draw, uint64_t first_sample, unsigned* __restrict__ zero_out,
+sample_compact_kernel(const CompactSampling call, int64_t total, int* __restrict__ slot_of_sample, float* __restrict__ pts_c,
+                      float* __restrict__ dirs_c, unsigned* __restrict__ count, unsigned* __restrict__ zero_out,
                       unsigned* __restrict__ tickets, unsigned* __restrict__ count_host, unsigned seq) {
   if (zero_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *zero_out = 0u;      // the NEXT call's counter (chained form)
-  const int64_t total = n_rays * (int64_t)S;
+  // The arguments, the generator's 64-bit constants and the loop bounds fill the scalar file to its last register; the fp32
+  // constants live in vector registers instead (59 of the 64 that 8 waves per SIMD would allow), which keeps every scalar out of
+  // spill lanes (train_compact.hip does the same, DESIGN 4.21 "Resources").
+  CompactSampling c = call;
+  asm volatile("" : "+v"(c.near_p), "+v"(c.far_p), "+v"(c.step), "+v"(c.bound), "+v"(c.scale));
   const int64_t span = (int64_t)kCompactThreads * kCompactPer;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool small = total < (int64_t)1 << 31;
   __shared__ unsigned seg[64];                          // per (k, wave): active count, then first slot
   // uniform trip count so that every lane takes part in the ballots
   for (int64_t g0 = blockIdx.x * span; g0 < total; g0 += (int64_t)gridDim.x * span) {
@@ -50,80 +72,28 @@ sample_compact_kernel(const float* __restrict__ rays_o, const float* __restrict_
       const int64_t g = g0 + (int64_t)k * kCompactThreads + threadIdx.x;
       bool active = false;
       px[k] = py[k] = pz[k] = 0.f;
-      if (g < total) {
-        const int64_t r = small ? (int64_t)((unsigned)g / (unsigned)S) : g / S;     // 64-bit division is emulated: ~100 instructions
-        const int s = (int)(g - r * S);
-        float z = depth_plain(s, S, step, near_p, far_p);
-        if (u != nullptr || draw) {
-          // draw: the jitter comes from the counter-based generator (common.h) instead of a [R,S] tensor of uniforms
-          const float uu = u != nullptr ? u[g] : squares_uniform(counter, first_sample + (uint64_t)g, key);
-          float lo = z, hi = z;
-          if (s > 0) lo = mul_rn(0.5f, add_rn(z, depth_plain(s - 1, S, step, near_p, far_p)));
-          if (s < S - 1) hi = mul_rn(0.5f, add_rn(depth_plain(s + 1, S, step, near_p, far_p), z));
-          z = add_rn(lo, mul_rn(sub_rn(hi, lo), uu));
-        }
-        z_out[g] = z;
-        px[k] = add_rn(rays_o[r * 3 + 0], mul_rn(rays_d[r * 3 + 0], z));
-        py[k] = add_rn(rays_o[r * 3 + 1], mul_rn(rays_d[r * 3 + 1], z));
-        pz[k] = add_rn(rays_o[r * 3 + 2], mul_rn(rays_d[r * 3 + 2], z));
-        // .long() truncates toward zero: (-1, res) is exactly the range of values whose index lands in [0, res)
-        const float fx = mul_rn(add_rn(px[k], bound), scale), fy = mul_rn(add_rn(py[k], bound), scale),
-                    fz = mul_rn(add_rn(pz[k], bound), scale), fres = (float)res;
-        if (fx > -1.0f && fx < fres && fy > -1.0f && fy < fres && fz > -1.0f && fz < fres)
-          active = grid[((int64_t)((int)fx * res + (int)fy)) * res + (int)fz] != 0;
-      }
+      if (g < total) active = compact_sample(c, g, px[k], py[k], pz[k]);
       ballot[k] = __ballot(active);
       if (lane == 0) seg[k * kCompactWaves + wave] = (unsigned)__popcll(ballot[k]);
     }
-    __syncthreads();
-    if (wave == 0) {                                    // exclusive scan of the 64 counts; ONE returning atomic per pass
-      const unsigned mine = seg[lane];
-      unsigned incl = mine;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const unsigned v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-      }
-      unsigned base = 0;
-      if (lane == 63 && incl != 0) base = atomicAdd(count, incl);
-      base = __shfl(base, 63);
-      seg[lane] = base + incl - mine;
-    }
-    __syncthreads();
+    reserve_slots(seg, count, lane, wave);
 #pragma unroll
     for (int k = 0; k < kCompactPer; ++k) {
       const int64_t g = g0 + (int64_t)k * kCompactThreads + threadIdx.x;
       if (g < total) {
         int slot = -1;
         if ((ballot[k] >> lane) & 1ull) {
-          slot = (int)(seg[k * kCompactWaves + wave] + (unsigned)__popcll(ballot[k] & ((1ull << lane) - 1ull)));
-          const int64_t r = small ? (int64_t)((unsigned)g / (unsigned)S) : g / S;
-          const float dx = rays_d[r * 3 + 0], dy = rays_d[r * 3 + 1], dz = rays_d[r * 3 + 2];
-          const float nrm = sqrtf(add_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)), mul_rn(dz, dz)));
-          pts_c[(size_t)slot * 3 + 0] = px[k]; pts_c[(size_t)slot * 3 + 1] = py[k]; pts_c[(size_t)slot * 3 + 2] = pz[k];
-          dirs_c[(size_t)slot * 3 + 0] = dx / nrm; dirs_c[(size_t)slot * 3 + 1] = dy / nrm; dirs_c[(size_t)slot * 3 + 2] = dz / nrm;
+          slot = (int)(seg[k * kCompactWaves + wave] + ballot_rank(ballot[k], lane));
+          const int64_t r = ray_of(g, c.S, c.small);
+          const float* __restrict__ rays_d = c.rays_d;
+          store_compact_row(pts_c, dirs_c, slot, px[k], py[k], pz[k], rays_d[r * 3 + 0], rays_d[r * 3 + 1], rays_d[r * 3 + 2]);
         }
         slot_of_sample[g] = slot;
       }
     }
     __syncthreads();                                    // seg is rewritten by the next pass
   }
-  // chained form: the workgroup that finishes last hands the count to the host -- two words of host-mapped pinned memory, the call's
-  // sequence number written last behind a system-scope fence -- instead of a copy launch and an event behind the kernel (each of those
-  // packets cost the stream a ~5-us gap of its own).  Tickets in two stages (32 groups: same-address atomics retire serially).
-  if (tickets != nullptr && threadIdx.x == 0) {       // (this workgroup's atomics on *count have returned: their values were used)
-    const unsigned B = gridDim.x, g = blockIdx.x % 32u, in_group = (B - g + 31u) / 32u;
-    if (atomicAdd(&tickets[1 + g], 1u) == in_group - 1) {
-      atomicExch(&tickets[1 + g], 0u);
-      if (atomicAdd(&tickets[0], 1u) == (B < 32u ? B : 32u) - 1) {
-        atomicExch(&tickets[0], 0u);
-        volatile unsigned* host = count_host;
-        host[0] = atomicOr(count, 0u);
-        __threadfence_system();
-        host[1] = seq;
-      }
-    }
-  }
+  if (tickets != nullptr && threadIdx.x == 0) publish_count(tickets, count, count_host, seq);      // chained form
 }
 
 // ---- ordered form (option "deterministic"): slots in SAMPLE ORDER, whatever the order the workgroups ran in ----
@@ -134,14 +104,9 @@ sample_compact_kernel(const float* __restrict__ rays_o, const float* __restrict_
 // samples; (2) one workgroup scans the segment counts in order; (3) slots = segment start + rank inside the wave's
 // ballot, points recomputed from the stored depth (the same two rounded operations: the same bits).
 __global__ void __launch_bounds__(kCompactThreads)
-sample_compact_count_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d, const float* __restrict__ u,
-                            int64_t n_rays, int S, float near_p, float far_p, float step, const uint8_t* __restrict__ grid, int res,
-                            float bound, float scale, float* __restrict__ z_out, int* __restrict__ slot_of_sample,
-                            unsigned* __restrict__ seg_count, uint64_t key, uint64_t counter, int draw, uint64_t first_sample) {
-  const int64_t total = n_rays * (int64_t)S;
+sample_compact_count_kernel(const CompactSampling c, int64_t total, int* __restrict__ slot_of_sample, unsigned* __restrict__ seg_count) {
   const int64_t span = (int64_t)kCompactThreads * kCompactPer;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool small = total < (int64_t)1 << 31;
   for (int64_t g0 = blockIdx.x * span; g0 < total; g0 += (int64_t)gridDim.x * span) {
     const int64_t pass = g0 / span;
 #pragma unroll
@@ -149,24 +114,8 @@ sample_compact_count_kernel(const float* __restrict__ rays_o, const float* __res
       const int64_t g = g0 + (int64_t)k * kCompactThreads + threadIdx.x;
       bool active = false;
       if (g < total) {
-        const int64_t r = small ? (int64_t)((unsigned)g / (unsigned)S) : g / S;
-        const int s = (int)(g - r * S);
-        float z = depth_plain(s, S, step, near_p, far_p);
-        if (u != nullptr || draw) {
-          const float uu = u != nullptr ? u[g] : squares_uniform(counter, first_sample + (uint64_t)g, key);
-          float lo = z, hi = z;
-          if (s > 0) lo = mul_rn(0.5f, add_rn(z, depth_plain(s - 1, S, step, near_p, far_p)));
-          if (s < S - 1) hi = mul_rn(0.5f, add_rn(depth_plain(s + 1, S, step, near_p, far_p), z));
-          z = add_rn(lo, mul_rn(sub_rn(hi, lo), uu));
-        }
-        z_out[g] = z;
-        const float px = add_rn(rays_o[r * 3 + 0], mul_rn(rays_d[r * 3 + 0], z));
-        const float py = add_rn(rays_o[r * 3 + 1], mul_rn(rays_d[r * 3 + 1], z));
-        const float pz = add_rn(rays_o[r * 3 + 2], mul_rn(rays_d[r * 3 + 2], z));
-        const float fx = mul_rn(add_rn(px, bound), scale), fy = mul_rn(add_rn(py, bound), scale),
-                    fz = mul_rn(add_rn(pz, bound), scale), fres = (float)res;
-        if (fx > -1.0f && fx < fres && fy > -1.0f && fy < fres && fz > -1.0f && fz < fres)
-          active = grid[((int64_t)((int)fx * res + (int)fy)) * res + (int)fz] != 0;
+        float px, py, pz;
+        active = compact_sample(c, g, px, py, pz);
         slot_of_sample[g] = active ? 0 : -1;
       }
       const unsigned long long ballot = __ballot(active);
@@ -219,15 +168,12 @@ sample_compact_place_kernel(const float* __restrict__ rays_o, const float* __res
       const bool active = g < total && slot_of_sample[g] == 0;
       const unsigned long long ballot = __ballot(active);
       if (!active) continue;
-      const int slot = (int)(seg_start[pass * 64 + k * kCompactWaves + wave] + (unsigned)__popcll(ballot & ((1ull << lane) - 1ull)));
-      const int64_t r = small ? (int64_t)((unsigned)g / (unsigned)S) : g / S;
+      const int slot = (int)(seg_start[pass * 64 + k * kCompactWaves + wave] + ballot_rank(ballot, lane));
+      const int64_t r = ray_of(g, S, small);
       const float zz = z[g];
       const float dx = rays_d[r * 3 + 0], dy = rays_d[r * 3 + 1], dz = rays_d[r * 3 + 2];
-      const float nrm = sqrtf(add_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)), mul_rn(dz, dz)));
-      pts_c[(size_t)slot * 3 + 0] = add_rn(rays_o[r * 3 + 0], mul_rn(dx, zz));
-      pts_c[(size_t)slot * 3 + 1] = add_rn(rays_o[r * 3 + 1], mul_rn(dy, zz));
-      pts_c[(size_t)slot * 3 + 2] = add_rn(rays_o[r * 3 + 2], mul_rn(dz, zz));
-      dirs_c[(size_t)slot * 3 + 0] = dx / nrm; dirs_c[(size_t)slot * 3 + 1] = dy / nrm; dirs_c[(size_t)slot * 3 + 2] = dz / nrm;
+      store_compact_row(pts_c, dirs_c, slot, add_rn(rays_o[r * 3 + 0], mul_rn(dx, zz)), add_rn(rays_o[r * 3 + 1], mul_rn(dy, zz)),
+                        add_rn(rays_o[r * 3 + 2], mul_rn(dz, zz)), dx, dy, dz);
       slot_of_sample[g] = slot;
     }
   }
@@ -257,10 +203,12 @@ static int sample_compact_impl(const float* rays_o, const float* rays_d, const f
   }                                                    // (publishing form with no rays: one workgroup that publishes a count of zero)
   NERF_REQUIRE(n_rays == 0 || (rays_o && rays_d && binary_grid && z_out && slot_of_sample && pts_compact && dirs_compact),
                "nerf_sample_compact: NULL pointer");
-  const float step = 1.0f / (float)(n_samples - 1);
-  const float scale = (float)((double)resolution / (2.0 * (double)bound));
+  const int64_t total = n_rays * (int64_t)n_samples;
+  const CompactSampling c{rays_o, rays_d, u, binary_grid, z_out, key, counter, first_sample, n_samples, resolution, draw,
+                          near_plane, far_plane, 1.0f / (float)(n_samples - 1), bound, voxel_scale(resolution, bound),
+                          total < (int64_t)1 << 31};
   const int64_t span = (int64_t)kCompactThreads * kCompactPer;
-  int64_t blocks = (n_rays * n_samples + span - 1) / span;
+  int64_t blocks = (total + span - 1) / span;
   const int64_t n_seg = blocks * 64;                     // before the cap: one (k, wave) segment per 64 samples of every pass
   if (blocks > 1024) blocks = 1024;
   if (blocks < 1) blocks = 1;
@@ -268,17 +216,15 @@ static int sample_compact_impl(const float* rays_o, const float* rays_d, const f
     NERF_REQUIRE(scratch_bytes >= (size_t)n_seg * sizeof(unsigned) && ((uintptr_t)scratch & 3) == 0,
                  "nerf_sample_compact_ordered: scratch of %zu bytes, %zu needed", scratch_bytes, (size_t)n_seg * sizeof(unsigned));
     unsigned* seg = static_cast<unsigned*>(scratch);
-    hipLaunchKernelGGL(sample_compact_count_kernel, dim3((int)blocks), dim3(kCompactThreads), 0, as_stream(stream), rays_o, rays_d, u, n_rays,
-                       n_samples, near_plane, far_plane, step, binary_grid, resolution, bound, scale, z_out, slot_of_sample, seg, key, counter,
-                       draw, first_sample);
+    hipLaunchKernelGGL(sample_compact_count_kernel, dim3((int)blocks), dim3(kCompactThreads), 0, as_stream(stream), c, total, slot_of_sample,
+                       seg);
     hipLaunchKernelGGL(sample_compact_scan_kernel, dim3(1), dim3(1024), 0, as_stream(stream), seg, n_seg, active_count);
     hipLaunchKernelGGL(sample_compact_place_kernel, dim3((int)blocks), dim3(kCompactThreads), 0, as_stream(stream), rays_o, rays_d, n_rays,
                        n_samples, z_out, slot_of_sample, seg, pts_compact, dirs_compact);
     return check_launch("nerf_sample_compact_ordered");
   }
-  hipLaunchKernelGGL(sample_compact_kernel, dim3((int)blocks), dim3(kCompactThreads), 0, as_stream(stream), rays_o, rays_d, u, n_rays,
-                     n_samples, near_plane, far_plane, step, binary_grid, resolution, bound, scale, z_out, slot_of_sample,
-                     pts_compact, dirs_compact, active_count, key, counter, draw, first_sample, next_count, tickets, count_host, seq);
+  hipLaunchKernelGGL(sample_compact_kernel, dim3((int)blocks), dim3(kCompactThreads), 0, as_stream(stream), c, total, slot_of_sample,
+                     pts_compact, dirs_compact, active_count, next_count, tickets, count_host, seq);
   return check_launch("nerf_sample_compact");
 }
 

@@ -1,36 +1,15 @@
 // Stratified depths, ray points and occupancy lookup.
 // Built with -ffp-contract=off: the reference's eager ops round after every
-// multiply and add, and sample / voxel indices must match it bit for bit.
-#include "common.h"
+// multiply and add, and sample / voxel indices must match it bit for bit.  Depth, pixel ray and composited target come from
+// ray_front.h, which spells every rounding out and so does not depend on that flag.
+#include "ray_front.h"
 
 namespace nerf {
 
-// torch.linspace(0,1,S) on CPU: step = 1/(S-1) in fp32; the lower half walks up
-// from 0, the upper half walks down from 1, each with ONE rounding.
-__device__ __forceinline__ float linspace01(int i, int n, float step) {
-  if (i < n / 2) return mul_rn(step, (float)i);
-  return __builtin_fmaf(-step, (float)(n - 1 - i), 1.0f);
-}
-
-__device__ __forceinline__ float plain_depth(int i, int n, float step, float near_p, float far_p) {
-  const float t = linspace01(i, n, step);
-  // near*(1-t) + far*t, three roundings (src/renderer.py:190)
-  return add_rn(mul_rn(near_p, sub_rn(1.0f, t)), mul_rn(far_p, t));
-}
-
-// jittered depth of sample i given its uniform draw u (src/renderer.py:195-199: mids / upper / lower)
-__device__ __forceinline__ float jitter_depth(int i, int n, float step, float near_p, float far_p, float u) {
-  const float zi = plain_depth(i, n, step, near_p, far_p);
-  float lo = zi, hi = zi;
-  if (i > 0) lo = mul_rn(0.5f, add_rn(zi, plain_depth(i - 1, n, step, near_p, far_p)));
-  if (i < n - 1) hi = mul_rn(0.5f, add_rn(plain_depth(i + 1, n, step, near_p, far_p), zi));
-  return add_rn(lo, mul_rn(sub_rn(hi, lo), u));
-}
-
 __device__ __forceinline__ float sample_depth(int i, int n, float step, float near_p, float far_p,
                                               const float* u_row) {
-  if (u_row == nullptr) return plain_depth(i, n, step, near_p, far_p);
-  return jitter_depth(i, n, step, near_p, far_p, u_row[i]);
+  const float zi = plain_depth(i, n, step, near_p, far_p);
+  return u_row == nullptr ? zi : jitter_depth(zi, i, n, step, near_p, far_p, u_row[i]);
 }
 
 __global__ void __launch_bounds__(256)
@@ -114,32 +93,16 @@ __device__ __forceinline__ void gather_one(const GatherArgs& a, int64_t r, int64
   const float* __restrict__ bg = a.bg;
   const int H = a.H, W = a.W;
   const float half_w = a.half_w, half_h = a.half_h, focal = a.focal, scene_scale = a.scene_scale;
-  {
-    const float* c2w = poses + im * 16;
-    const float x = sub_rn((float)px, half_w) / focal;
-    const float y = -(sub_rn((float)py, half_h) / focal);
-    const float z = -1.0f;
-    float d[3];
+  float d[3], o[3];
+  pixel_ray(poses + im * 16, px, py, half_w, half_h, focal, scene_scale, d, o);
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
-      d[i] = add_rn(add_rn(mul_rn(c2w[4 * i + 0], x), mul_rn(c2w[4 * i + 1], y)), mul_rn(c2w[4 * i + 2], z));
-    const float nrm = sqrtf(add_rn(add_rn(mul_rn(d[0], d[0]), mul_rn(d[1], d[1])), mul_rn(d[2], d[2])));
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      rays_d[r * 3 + i] = d[i] / nrm;
-      const float o = c2w[4 * i + 3];
-      rays_o[r * 3 + i] = scene_scale != 1.0f ? mul_rn(o, scene_scale) : o;
-    }
-    const float4 c = *reinterpret_cast<const float4*>(images + ((im * H + py) * W + px) * 4);
-    if (rgba != nullptr) *reinterpret_cast<float4*>(rgba + r * 4) = c;
-    if (target != nullptr) {
-      // target = rgb * a + bg * (1 - a), every product and sum rounded on its own (run.py:317-322)
-      const float rest = sub_rn(1.0f, c.w);
-      target[r * 3 + 0] = add_rn(mul_rn(c.x, c.w), mul_rn(bg[0], rest));
-      target[r * 3 + 1] = add_rn(mul_rn(c.y, c.w), mul_rn(bg[1], rest));
-      target[r * 3 + 2] = add_rn(mul_rn(c.z, c.w), mul_rn(bg[2], rest));
-    }
+  for (int i = 0; i < 3; ++i) {
+    rays_d[r * 3 + i] = d[i];
+    rays_o[r * 3 + i] = o[i];
   }
+  const float4 c = *reinterpret_cast<const float4*>(images + ((im * H + py) * W + px) * 4);
+  if (rgba != nullptr) *reinterpret_cast<float4*>(rgba + r * 4) = c;
+  if (target != nullptr) composite_target(target + r * 3, c, bg);
 }
 
 __global__ void __launch_bounds__(256)
@@ -169,7 +132,7 @@ train_batch_kernel(const GatherArgs a, uint64_t n_pixels, uint64_t key, uint64_t
     if (perturb) {
       const uint64_t gg = (uint64_t)(g + first_ray * n_samples);
       const float u = (float)(squares32((counter << 40) + gg, key) >> 8) * 5.9604644775390625e-08f;   // [0, 1), 24 bits
-      z_out[g] = jitter_depth(s, n_samples, step, near_p, far_p, u);
+      z_out[g] = jitter_depth(plain_depth(s, n_samples, step, near_p, far_p), s, n_samples, step, near_p, far_p, u);
     } else {
       z_out[g] = plain_depth(s, n_samples, step, near_p, far_p);
     }
@@ -216,8 +179,7 @@ extern "C" int nerf_active_mask(const float* pts, int64_t n, const uint8_t* bina
   NERF_REQUIRE(n >= 0 && resolution > 0 && bound > 0.0f, "nerf_active_mask: bad sizes");
   NERF_REQUIRE(n == 0 || (pts && binary_grid && mask_out), "nerf_active_mask: NULL pointer");
   if (n == 0) return NERF_OK;
-  // the Python double res/(2*bound) is demoted to fp32 before the multiply
-  const float scale = (float)((double)resolution / (2.0 * (double)bound));
+  const float scale = voxel_scale(resolution, bound);
   hipLaunchKernelGGL(active_mask_kernel, dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), pts,
                      n, binary_grid, resolution, bound, scale, mask_out, idx_out);
   return check_launch("nerf_active_mask");

@@ -3,31 +3,17 @@
 // of the first that the second never reads and without the second's re-read of the rays.  Thread per (ray, sample), as in the
 // compaction.  EVERY thread re-forms its ray from the pixel draw and the pose -- two generator draws, one 3x3 rotation, one
 // normalisation: about a hundred instructions, no LDS staging, no dependence on another workgroup's stores -- and only the
-// thread of sample 0 fetches the pixel and writes rays_o / rays_d / rgba / target.  Depth, point, voxel test and slot
-// reservation restate sample_compact_kernel line by line (draw = 1, first_sample = first_ray * n_samples), the ray restates
-// gather_one: the same separately rounded operations, the same divisions, so every output equals the two-call form's bit for
-// bit (the compact rows up to the arbitrary slot order both share).  The compaction normalises the unit direction it reads
-// from rays_d a SECOND time; so does this kernel.  Slots: wave ballots -> 64 counts in LDS -> one wave scans -> ONE returning
-// atomic per workgroup and pass of 4096 samples.  Count publication: compact.hip's, word for word (plain form: a device word
-// the call clears; chain form: two counters used alternately, tickets, (count, seq) in host-mapped memory).
-#include "common.h"
+// thread of sample 0 fetches the pixel and writes rays_o / rays_d / rgba / target.  The pixel ray and the composited target, the
+// jittered depth, the voxel test, the slot reservation (wave ballots -> 64 counts in LDS -> one wave scans -> ONE returning atomic
+// per workgroup and pass of 4096 samples), the compact-row store and the count hand-off are ray_front.h's, the very functions
+// sample.hip and compact.hip call (draw = 1, first_sample = first_ray * n_samples), so every output equals the two-call form's
+// bit for bit (the compact rows up to the arbitrary slot order both share).  The compaction normalises the unit direction it
+// reads from rays_d a SECOND time; so does the row store here.  Count publication -- plain form: a device word the call clears;
+// chain form: two counters used alternately, tickets, (count, seq) in host-mapped memory -- follows compact.hip's protocol, and
+// links of both entries alternate on one chain_state.
+#include "ray_front.h"
 
 namespace nerf {
-
-// (restated from compact.hip: a shared helper would recompile sample_compact_kernel)
-__device__ __forceinline__ float tc_lin01(int i, int n, float step) {
-  if (i < n / 2) return mul_rn(step, (float)i);
-  return __builtin_fmaf(-step, (float)(n - 1 - i), 1.0f);
-}
-__device__ __forceinline__ float tc_depth_plain(int i, int n, float step, float near_p, float far_p) {
-  const float t = tc_lin01(i, n, step);
-  return add_rn(mul_rn(near_p, sub_rn(1.0f, t)), mul_rn(far_p, t));
-}
-
-constexpr int kTcThreads = 1024;
-constexpr int kTcPer = 4;                               // samples per thread and pass: 4096 samples share one atomic
-constexpr int kTcWaves = kTcThreads / 64;
-static_assert(kTcPer * kTcWaves == 64, "the (k, wave) counts of a pass are scanned by one wave");
 
 struct TrainCompactArgs {
   const float* images;
@@ -51,7 +37,7 @@ struct TrainCompactArgs {
   float half_w, half_h, focal, scene_scale, near_p, far_p, step, bound, scale;
 };
 
-__global__ void __launch_bounds__(kTcThreads) train_batch_compact_kernel(const TrainCompactArgs a) {
+__global__ void __launch_bounds__(kCompactThreads) train_batch_compact_kernel(const TrainCompactArgs a) {
   if (a.chain_state != nullptr && blockIdx.x == 0 && threadIdx.x == 0) a.chain_state[a.turn ^ 1] = 0u;  // the NEXT link's counter
   const float* __restrict__ poses = a.poses;
   const uint8_t* __restrict__ grid = a.grid;
@@ -69,17 +55,17 @@ __global__ void __launch_bounds__(kTcThreads) train_batch_compact_kernel(const T
   asm volatile("" : "+v"(half_w), "+v"(half_h), "+v"(focal), "+v"(scene_scale), "+v"(near_p), "+v"(far_p), "+v"(step), "+v"(bound),
                "+v"(scale));
   const unsigned total = a.total;                       // < 2^31: 32-bit sample indices throughout
-  const unsigned span = (unsigned)kTcThreads * kTcPer;
+  const unsigned span = (unsigned)kCompactThreads * kCompactPer;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int S = a.S, res = a.res;
   __shared__ unsigned seg[64];                          // per (k, wave): active count, then first slot
   // uniform trip count so that every lane takes part in the ballots
   for (unsigned g0 = blockIdx.x * span; g0 < total; g0 += gridDim.x * span) {
-    float px[kTcPer], py[kTcPer], pz[kTcPer], ux[kTcPer], uy[kTcPer], uz[kTcPer];
-    unsigned long long ballot[kTcPer];
+    float px[kCompactPer], py[kCompactPer], pz[kCompactPer], ux[kCompactPer], uy[kCompactPer], uz[kCompactPer];
+    unsigned long long ballot[kCompactPer];
 #pragma unroll
-    for (int k = 0; k < kTcPer; ++k) {
-      const unsigned g = g0 + (unsigned)k * kTcThreads + threadIdx.x;
+    for (int k = 0; k < kCompactPer; ++k) {
+      const unsigned g = g0 + (unsigned)k * kCompactThreads + threadIdx.x;
       bool active = false;
       px[k] = py[k] = pz[k] = ux[k] = uy[k] = uz[k] = 0.f;
       if (g < total) {
@@ -93,104 +79,46 @@ __global__ void __launch_bounds__(kTcThreads) train_batch_compact_kernel(const T
         const unsigned idx = (unsigned)__umul64hi(r64, (uint64_t)a.n_pixels);        // uniform over [0, n_pixels)
         const unsigned row = idx / (unsigned)a.W, frame = row / (unsigned)a.H;
         const int64_t ix = (int64_t)(idx - row * (unsigned)a.W), iy = (int64_t)(row - frame * (unsigned)a.H), im = (int64_t)frame;
-        const float* c2w = poses + im * 16;
-        const float x = sub_rn((float)ix, half_w) / focal;
-        const float y = -(sub_rn((float)iy, half_h) / focal);
-        const float zc = -1.0f;
         float d[3], o[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-          d[i] = add_rn(add_rn(mul_rn(c2w[4 * i + 0], x), mul_rn(c2w[4 * i + 1], y)), mul_rn(c2w[4 * i + 2], zc));
-          const float t = c2w[4 * i + 3];
-          o[i] = scene_scale != 1.0f ? mul_rn(t, scene_scale) : t;
-        }
-        const float nrm = sqrtf(add_rn(add_rn(mul_rn(d[0], d[0]), mul_rn(d[1], d[1])), mul_rn(d[2], d[2])));
-        ux[k] = d[0] / nrm; uy[k] = d[1] / nrm; uz[k] = d[2] / nrm;
+        pixel_ray(poses + im * 16, ix, iy, half_w, half_h, focal, scene_scale, d, o);
+        ux[k] = d[0]; uy[k] = d[1]; uz[k] = d[2];
         if (s == 0) {
           rays_d[(size_t)r * 3 + 0] = ux[k]; rays_d[(size_t)r * 3 + 1] = uy[k]; rays_d[(size_t)r * 3 + 2] = uz[k];
           rays_o[(size_t)r * 3 + 0] = o[0]; rays_o[(size_t)r * 3 + 1] = o[1]; rays_o[(size_t)r * 3 + 2] = o[2];
           const float4 c = *reinterpret_cast<const float4*>(images + ((im * a.H + iy) * a.W + ix) * 4);
           if (rgba != nullptr) *reinterpret_cast<float4*>(rgba + (size_t)r * 4) = c;
-          if (target != nullptr) {
-            // target = rgb * a + bg * (1 - a), every product and sum rounded on its own
-            const float rest = sub_rn(1.0f, c.w);
-            target[(size_t)r * 3 + 0] = add_rn(mul_rn(c.x, c.w), mul_rn(bg[0], rest));
-            target[(size_t)r * 3 + 1] = add_rn(mul_rn(c.y, c.w), mul_rn(bg[1], rest));
-            target[(size_t)r * 3 + 2] = add_rn(mul_rn(c.z, c.w), mul_rn(bg[2], rest));
-          }
+          if (target != nullptr) composite_target(target + (size_t)r * 3, c, bg);
         }
-        // ---- the sample (sample_compact_kernel, draw = 1): jittered depth, point, voxel test
-        float z = tc_depth_plain(s, S, step, near_p, far_p);
-        {
-          // squares_uniform(counter, first_ray * n_samples + g, key)
-          const float uu = (float)(squares32(a.sample_ctr + (uint64_t)g, a.key) >> 8) * 5.9604644775390625e-08f;
-          float lo = z, hi = z;
-          if (s > 0) lo = mul_rn(0.5f, add_rn(z, tc_depth_plain(s - 1, S, step, near_p, far_p)));
-          if (s < S - 1) hi = mul_rn(0.5f, add_rn(tc_depth_plain(s + 1, S, step, near_p, far_p), z));
-          z = add_rn(lo, mul_rn(sub_rn(hi, lo), uu));
-        }
+        // ---- the sample (sample_compact_kernel, draw = 1): jittered depth from squares_uniform(counter, first_ray * n_samples + g,
+        // key), point, voxel test
+        const float z = jitter_depth(plain_depth(s, S, step, near_p, far_p), s, S, step, near_p, far_p,
+                                     (float)(squares32(a.sample_ctr + (uint64_t)g, a.key) >> 8) * 5.9604644775390625e-08f);
         a.z_out[g] = z;
         px[k] = add_rn(o[0], mul_rn(ux[k], z));
         py[k] = add_rn(o[1], mul_rn(uy[k], z));
         pz[k] = add_rn(o[2], mul_rn(uz[k], z));
-        // .long() truncates toward zero: (-1, res) is exactly the range of values whose index lands in [0, res)
-        const float fx = mul_rn(add_rn(px[k], bound), scale), fy = mul_rn(add_rn(py[k], bound), scale),
-                    fz = mul_rn(add_rn(pz[k], bound), scale), fres = (float)res;
-        if (fx > -1.0f && fx < fres && fy > -1.0f && fy < fres && fz > -1.0f && fz < fres)
-          active = grid[((int64_t)((int)fx * res + (int)fy)) * res + (int)fz] != 0;
+        active = voxel_active(grid, res, bound, scale, px[k], py[k], pz[k]);
       }
       ballot[k] = __ballot(active);
-      if (lane == 0) seg[k * kTcWaves + wave] = (unsigned)__popcll(ballot[k]);
+      if (lane == 0) seg[k * kCompactWaves + wave] = (unsigned)__popcll(ballot[k]);
     }
-    __syncthreads();
-    if (wave == 0) {                                    // exclusive scan of the 64 counts; ONE returning atomic per pass
-      const unsigned mine = seg[lane];
-      unsigned incl = mine;
+    reserve_slots(seg, a.count, lane, wave);
 #pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const unsigned v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-      }
-      unsigned base = 0;
-      if (lane == 63 && incl != 0) base = atomicAdd(a.count, incl);
-      base = __shfl(base, 63);
-      seg[lane] = base + incl - mine;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < kTcPer; ++k) {
-      const unsigned g = g0 + (unsigned)k * kTcThreads + threadIdx.x;
+    for (int k = 0; k < kCompactPer; ++k) {
+      const unsigned g = g0 + (unsigned)k * kCompactThreads + threadIdx.x;
       if (g < total) {
         int slot = -1;
         if ((ballot[k] >> lane) & 1ull) {
-          // slot < total (the active count never exceeds the sample count): inside the capacity of pts_c / dirs_c
-          slot = (int)(seg[k * kTcWaves + wave] + (unsigned)__popcll(ballot[k] & ((1ull << lane) - 1ull)));
-          const float dx = ux[k], dy = uy[k], dz = uz[k];          // the compaction normalises the unit direction again
-          const float nrm = sqrtf(add_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)), mul_rn(dz, dz)));
-          pts_c[(size_t)slot * 3 + 0] = px[k]; pts_c[(size_t)slot * 3 + 1] = py[k]; pts_c[(size_t)slot * 3 + 2] = pz[k];
-          dirs_c[(size_t)slot * 3 + 0] = dx / nrm; dirs_c[(size_t)slot * 3 + 1] = dy / nrm; dirs_c[(size_t)slot * 3 + 2] = dz / nrm;
+          slot = (int)(seg[k * kCompactWaves + wave] + ballot_rank(ballot[k], lane));
+          store_compact_row(pts_c, dirs_c, slot, px[k], py[k], pz[k], ux[k], uy[k], uz[k]);
         }
         slot_of_sample[g] = slot;
       }
     }
     __syncthreads();                                    // seg is rewritten by the next pass
   }
-  // chain form (compact.hip): the workgroup that finishes last hands the count to the host -- the count, then the call's sequence
-  // number behind a system-scope fence, in host-mapped pinned memory.  Tickets in two stages (32 groups).
-  if (a.chain_state != nullptr && a.count_host != nullptr && threadIdx.x == 0) {     // (this workgroup's atomics on *count have returned)
-    unsigned* tickets = a.chain_state + 2;
-    const unsigned B = gridDim.x, g = blockIdx.x % 32u, in_group = (B - g + 31u) / 32u;
-    if (atomicAdd(&tickets[1 + g], 1u) == in_group - 1) {
-      atomicExch(&tickets[1 + g], 0u);
-      if (atomicAdd(&tickets[0], 1u) == (B < 32u ? B : 32u) - 1) {
-        atomicExch(&tickets[0], 0u);
-        volatile unsigned* host = a.count_host;
-        host[0] = atomicOr(a.count, 0u);
-        __threadfence_system();
-        host[1] = a.seq;
-      }
-    }
-  }
+  if (a.chain_state != nullptr && a.count_host != nullptr && threadIdx.x == 0)       // chain form
+    publish_count(a.chain_state + 2, a.count, a.count_host, a.seq);
 }
 
 }  // namespace nerf
@@ -250,11 +178,11 @@ static int train_batch_compact_impl(const char* what, const float* images, const
   a.H = H; a.W = W; a.S = n_samples; a.res = resolution;
   a.half_w = (float)(W * 0.5); a.half_h = (float)(H * 0.5); a.focal = focal; a.scene_scale = scene_scale;
   a.near_p = near_plane; a.far_p = far_plane; a.step = 1.0f / (float)(n_samples - 1);
-  a.bound = bound; a.scale = (float)((double)resolution / (2.0 * (double)bound));
-  const int64_t span = (int64_t)kTcThreads * kTcPer;
+  a.bound = bound; a.scale = voxel_scale(resolution, bound);
+  const int64_t span = (int64_t)kCompactThreads * kCompactPer;
   int64_t blocks = ((int64_t)a.total + span - 1) / span;
   if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(train_batch_compact_kernel, dim3((int)blocks), dim3(kTcThreads), 0, as_stream(stream), a);
+  hipLaunchKernelGGL(train_batch_compact_kernel, dim3((int)blocks), dim3(kCompactThreads), 0, as_stream(stream), a);
   return check_launch(what);
 }
 

@@ -19,7 +19,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import flat_params, ops
-from .flat_engine import LapSlots, ViewSlots, cosine_lr, render_chunks
+from .flat_engine import LapSlots, ViewSlots, cosine_lr, render_chunks, render_counted_chain
 
 Tensor = torch.Tensor
 
@@ -309,16 +309,10 @@ class VanillaNerfEngine:
 
     def _render_image_grid_chain(self, rays_o: Tensor, rays_d: Tensor, n_samples: int, chunk: int) -> Tensor:
         grid = self._require_grid("render_image(grid=True)")
-        shape = rays_o.shape[:-1]
-        o, d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
-        chunk = max(1, min(int(chunk), max(o.shape[0], 1)))
-        ws = self._grid_ws.get((chunk, n_samples))
-        if ws is None:
-            ws = self._grid_ws[(chunk, n_samples)] = torch.empty(ops.render_rays_grid_workspace_bytes(chunk, n_samples), dtype=torch.uint8,
-                                                                 device=self.device)
-        rgb = ops.render_rays_grid_fwd(self._inference_weights(), grid, self.bound, o, d, n_samples, self.near, self.far, self.bg, chunk,
-                                       workspace=ws)[0]
-        return rgb.view(*shape, 3)
+        return render_counted_chain(
+            lambda o, d, chunk, ws: ops.render_rays_grid_fwd(self._inference_weights(), grid, self.bound, o, d, n_samples, self.near, self.far,
+                                                             self.bg, chunk, workspace=ws),
+            ops.render_rays_grid_workspace_bytes, self._grid_ws, rays_o, rays_d, n_samples, chunk, self.device)
 
     @torch.no_grad()
     def render_image(self, rays_o: Tensor, rays_d: Tensor, n_samples: int, chunk: int = 65536, n_fine: int = 0, grid=False) -> Tensor:
@@ -729,12 +723,7 @@ class InstantNgpEngine:
         return render_chunks(lambda o, d: self.render_rays(o, d, n_samples), rays_o, rays_d, chunk, self.device)
 
     def _render_image_chain(self, rays_o: Tensor, rays_d: Tensor, n_samples: int, chunk: int) -> Tensor:
-        shape = rays_o.shape[:-1]
-        o, d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
-        chunk = max(1, min(int(chunk), max(o.shape[0], 1)))
-        ws = self._chain_ws.get((chunk, n_samples))
-        if ws is None:
-            ws = self._chain_ws[(chunk, n_samples)] = torch.empty(ops.instant_render_workspace_bytes(chunk, n_samples), dtype=torch.uint8, device=self.device)
-        rgb = ops.instant_render_rays_fwd(self.packed, self._gather_table(), self.levels, self.bound, self.binary_grid, self.bound, o, d,
-                                          n_samples, self.near, self.far, self.bg, chunk, workspace=ws)[0]
-        return rgb.view(*shape, 3)
+        return render_counted_chain(
+            lambda o, d, chunk, ws: ops.instant_render_rays_fwd(self.packed, self._gather_table(), self.levels, self.bound, self.binary_grid,
+                                                                self.bound, o, d, n_samples, self.near, self.far, self.bg, chunk, workspace=ws),
+            ops.instant_render_workspace_bytes, self._chain_ws, rays_o, rays_d, n_samples, chunk, self.device)

@@ -43,6 +43,19 @@ def render_chunks(render_rays, rays_o: Tensor, rays_d: Tensor, chunk: int, devic
     return out.view(*shape, 3)
 
 
+def render_counted_chain(render, workspace_bytes, kept: Dict, rays_o: Tensor, rays_d: Tensor, n_samples: int, chunk: int, device) -> Tensor:
+    """[..., 3] colours of rays [..., 3] through a counted render chain (ops.render_rays_grid_fwd, ops.instant_render_rays_fwd):
+    ``render(o, d, chunk, workspace)[0]`` for all rays in one call, ``chunk`` clamped to [1, number of rays], ONE workspace of
+    ``workspace_bytes(chunk, n_samples)`` bytes kept in ``kept`` per (chunk, n_samples)"""
+    shape = rays_o.shape[:-1]
+    o, d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
+    chunk = max(1, min(int(chunk), max(o.shape[0], 1)))
+    ws = kept.get((chunk, n_samples))
+    if ws is None:
+        ws = kept[(chunk, n_samples)] = torch.empty(workspace_bytes(chunk, n_samples), dtype=torch.uint8, device=device)
+    return render(o, d, chunk, ws)[0].view(*shape, 3)
+
+
 # --------------------------------------------------------------------------------------------------- per-step scalar slots
 class ViewSlots:
     """A fresh zeroed row per call out of a zeroed ring [slots, width], with no fill launch and no copy launch per step: the row

@@ -7,6 +7,7 @@ or eager fallback.
 """
 from __future__ import annotations
 
+import weakref
 from typing import Optional, Tuple
 
 import torch
@@ -193,26 +194,32 @@ class _CompactChain:
         self.host_np[slot, 1] = 0                 # (a seq is never 0)
         return turn, slot, self.seq & 0x7FFFFFFF or 1
 
+    @classmethod
+    def of(cls, device) -> "_CompactChain":
+        """the chain of (device, current stream), created on first use"""
+        key = (device, _stream())
+        chain = _COMPACT_CHAIN.get(key)
+        if chain is None:
+            chain = _COMPACT_CHAIN[key] = cls(device)
+        return chain
+
+    def result(self, slot, seq, z, slots, pts, dirs) -> "CompactedSamples":
+        """the result of the link that publishes (count, seq) into ring slot ``slot``; the ring keeps a weak reference to it"""
+        out = CompactedSamples(z, slots, pts, dirs, self.host_np[slot], None, seq=seq)
+        self.owner[slot] = weakref.ref(out)
+        return out
+
+
+def _jitter_draw(u, jitter):
+    """(draw, seed, counter): whether the kernel draws the jitter itself (``jitter=(seed, counter)`` and no tensor of uniforms)"""
+    draw = u is None and jitter is not None
+    return (draw,) + ((int(jitter[0]), int(jitter[1]) & 0xFFFFFF) if draw else (0, 0))
+
 
 def _compact_launch(lib, rays_o, rays_d, u, jitter, first_ray, R, n_samples, near, far, grid, bound, z, slots, pts, dirs, count):
-    """the compaction launch of sample_compact / sample_compact_async: ordered slots when deterministic.  ``count`` None (the
-    asynchronous path with in-kernel jitter): nerf_sample_compact_jitter_chain -- no fill launch, no copy launch, no event: returns
-    (host block as numpy [2], seq) to poll; otherwise returns the device counter the call used."""
-    draw = u is None and jitter is not None
-    seed, counter = (int(jitter[0]), int(jitter[1]) & 0xFFFFFF) if draw else (0, 0)
-    if count is None:
-        if draw and not deterministic() and not _NO_CHAIN:
-            key = (rays_o.device, _stream())
-            chain = _COMPACT_CHAIN.get(key)
-            if chain is None:
-                chain = _COMPACT_CHAIN[key] = _CompactChain(rays_o.device)
-            turn, slot, seq = chain.next()
-            _lib.check(lib.nerf_sample_compact_jitter_chain(_p(rays_o), _p(rays_d), seed, counter, int(first_ray), R, n_samples, near, far,
-                                                            _p(grid), grid.shape[0], float(bound), _p(z), _p(slots), _p(pts), _p(dirs),
-                                                            _p(chain.state), turn, chain.host[slot].data_ptr(), seq, _stream()),
-                       "nerf_sample_compact_jitter_chain")
-            return chain.host_np[slot], seq, chain, slot
-        count = torch.empty(1, device=rays_o.device, dtype=torch.int32)          # cleared by the library call itself
+    """the compaction launch of sample_compact / sample_compact_async that counts in the device word ``count`` (the call clears it):
+    ordered slots when deterministic"""
+    draw, seed, counter = _jitter_draw(u, jitter)
     if deterministic():
         scratch = torch.empty(max(lib.nerf_sample_compact_ordered_scratch_bytes(R, n_samples), 4), dtype=torch.uint8, device=rays_o.device)
         _lib.check(lib.nerf_sample_compact_ordered(_p(rays_o), _p(rays_d), _p(u), 1 if draw else 0, seed, counter, int(first_ray), R, n_samples,
@@ -226,7 +233,6 @@ def _compact_launch(lib, rays_o, rays_d, u, jitter, first_ray, R, n_samples, nea
         _lib.check(lib.nerf_sample_compact(_p(rays_o), _p(rays_d), _p(u), R, n_samples, near, far, _p(grid), grid.shape[0],
                                            float(bound), _p(z), _p(slots), _p(pts), _p(dirs), _p(count), _stream()),
                    "nerf_sample_compact")
-    return count
 
 
 # --------------------------------------------------------------------------- a1-a4 fused
@@ -295,12 +301,18 @@ def sample_compact_async(rays_o: Tensor, rays_d: Tensor, near: float, far: float
     of a larger batch (data-parallel shards of one global batch draw the jitter one GPU would draw)."""
     lib = _lib.load()
     rays_o, rays_d, grid, u, R, z, slots, pts, dirs = _compact_outputs(rays_o, rays_d, n_samples, binary_grid, u)
-    count = _compact_launch(lib, rays_o, rays_d, u, jitter, first_ray, R, n_samples, near, far, grid, bound, z, slots, pts, dirs, None)
-    if isinstance(count, tuple):                                       # chained form: (host block, seq) to poll
-        import weakref
-        out = CompactedSamples(z, slots, pts, dirs, count[0], None, seq=count[1])
-        count[2].owner[count[3]] = weakref.ref(out)
-        return out
+    draw, seed, counter = _jitter_draw(u, jitter)
+    if draw and not deterministic() and not _NO_CHAIN:
+        # a link of the chain: no fill launch, no copy launch, no event -- the kernel publishes (count, seq) for the host to poll
+        chain = _CompactChain.of(rays_o.device)
+        turn, slot, seq = chain.next()
+        _lib.check(lib.nerf_sample_compact_jitter_chain(_p(rays_o), _p(rays_d), seed, counter, int(first_ray), R, n_samples, near, far,
+                                                        _p(grid), grid.shape[0], float(bound), _p(z), _p(slots), _p(pts), _p(dirs),
+                                                        _p(chain.state), turn, chain.host[slot].data_ptr(), seq, _stream()),
+                   "nerf_sample_compact_jitter_chain")
+        return chain.result(slot, seq, z, slots, pts, dirs)
+    count = torch.empty(1, device=rays_o.device, dtype=torch.int32)          # cleared by the library call itself
+    _compact_launch(lib, rays_o, rays_d, u, jitter, first_ray, R, n_samples, near, far, grid, bound, z, slots, pts, dirs, count)
     count_host = torch.empty(1, dtype=torch.int32, pin_memory=True)
     count_host.copy_(count, non_blocking=True)
     event = torch.cuda.Event()
@@ -334,20 +346,14 @@ def train_batch_compact(images: Tensor, poses: Tensor, focal: float, batch: int,
     z = torch.empty(batch, n_samples, device=dev)
     slots = torch.empty(n, device=dev, dtype=torch.int32)
     pts, dirs = torch.empty(n, 3, device=dev), torch.empty(n, 3, device=dev)
-    key = (dev, _stream())
-    chain = _COMPACT_CHAIN.get(key)
-    if chain is None:
-        chain = _COMPACT_CHAIN[key] = _CompactChain(dev)
+    chain = _CompactChain.of(dev)
     turn, slot, seq = chain.next()
     _lib.check(lib.nerf_train_batch_compact_chain(_p(images), _p(poses), n_img, H, W, float(focal), float(scene_scale),
                                                   _p(None if bg is None else _dev(bg, "bg")), int(seed), counter, int(first_ray), batch,
                                                   n_samples, float(near), float(far), _p(grid), grid.shape[0], float(bound), _p(o), _p(d),
                                                   _p(rgba), _p(target), _p(z), _p(slots), _p(pts), _p(dirs), _p(chain.state), turn,
                                                   chain.host[slot].data_ptr(), seq, _stream()), "nerf_train_batch_compact_chain")
-    import weakref
-    out = CompactedSamples(z, slots, pts, dirs, chain.host_np[slot], None, seq=seq)
-    chain.owner[slot] = weakref.ref(out)
-    return o, d, (target if bg is not None else rgba), out
+    return o, d, (target if bg is not None else rgba), chain.result(slot, seq, z, slots, pts, dirs)
 
 
 class _CompositeIndexed(torch.autograd.Function):
@@ -588,6 +594,26 @@ def render_rays_grid_workspace_bytes(chunk: int, n_samples: int) -> int:
     return _lib.load().nerf_render_rays_grid_workspace_bytes(chunk, n_samples)
 
 
+def _counted_render_args(name: str, workspace_bytes, packed, binary_grid, rays_o, rays_d, n_samples, bg, chunk, workspace):
+    """the checked arguments and the allocated outputs of the two counted render chains (``name``: the entry, for the messages;
+    ``workspace_bytes``: its size query): (packed, grid, rays_o, rays_d, R, bg, bg_rows, chunk clamped to [1, R], workspace,
+    rgb [R,3], depth [R], acc [R])"""
+    rays_o, rays_d = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d")
+    grid = _dev(binary_grid, "binary_grid", torch.bool)
+    packed = _dev(packed, "packed", torch.uint8)
+    R = rays_o.shape[0]
+    chunk = max(1, min(int(chunk), max(R, 1)))
+    need = workspace_bytes(chunk, n_samples)
+    if workspace is None:
+        workspace = torch.empty(need, device=rays_o.device, dtype=torch.uint8)
+    elif _dev(workspace, "workspace", torch.uint8).numel() < need:
+        raise ValueError(f"{name}: workspace of {workspace.numel()} bytes, {need} needed for chunk {chunk} x {n_samples}")
+    bg = None if bg is None else _dev(bg, "bg")
+    out = torch.empty(R, 3, device=rays_o.device)
+    depth, acc = torch.empty(R, device=rays_o.device), torch.empty(R, device=rays_o.device)
+    return packed, grid, rays_o, rays_d, R, bg, _bg_rows(bg), chunk, workspace, out, depth, acc
+
+
 def render_rays_grid_fwd(packed: Tensor, binary_grid: Tensor, grid_bound: float, rays_o: Tensor, rays_d: Tensor, n_samples: int,
                          near: float, far: float, bg: Optional[Tensor] = None, chunk: int = 65536, workspace: Optional[Tensor] = None):
     """(rgb [R,3], depth [R], acc [R]) of the vanilla field against an occupancy grid for any number of rays: one launch chain
@@ -596,21 +622,10 @@ def render_rays_grid_fwd(packed: Tensor, binary_grid: Tensor, grid_bound: float,
     or waited for between the launches.  ``workspace``: uint8, at least render_rays_grid_workspace_bytes(chunk, n_samples) bytes
     (allocated here otherwise); its first int32 holds the last chunk's active count afterwards."""
     lib = _lib.load()
-    rays_o, rays_d = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d")
-    grid = _dev(binary_grid, "binary_grid", torch.bool)
-    packed = _dev(packed, "packed", torch.uint8)
-    R = rays_o.shape[0]
-    chunk = max(1, min(int(chunk), max(R, 1)))
-    need = lib.nerf_render_rays_grid_workspace_bytes(chunk, n_samples)
-    if workspace is None:
-        workspace = torch.empty(need, device=rays_o.device, dtype=torch.uint8)
-    elif _dev(workspace, "workspace", torch.uint8).numel() < need:
-        raise ValueError(f"render_rays_grid_fwd: workspace of {workspace.numel()} bytes, {need} needed for chunk {chunk} x {n_samples}")
-    bg = None if bg is None else _dev(bg, "bg")
-    out = torch.empty(R, 3, device=rays_o.device)
-    depth, acc = torch.empty(R, device=rays_o.device), torch.empty(R, device=rays_o.device)
+    packed, grid, rays_o, rays_d, R, bg, bg_rows, chunk, workspace, out, depth, acc = _counted_render_args(
+        "render_rays_grid_fwd", lib.nerf_render_rays_grid_workspace_bytes, packed, binary_grid, rays_o, rays_d, n_samples, bg, chunk, workspace)
     _lib.check(lib.nerf_render_rays_grid_fwd(_p(packed), _p(grid), grid.shape[0], float(grid_bound), _p(rays_o), _p(rays_d), R, n_samples,
-                                             float(near), float(far), _p(bg), _bg_rows(bg), chunk, _p(workspace), _p(out), _p(depth),
+                                             float(near), float(far), _p(bg), bg_rows, chunk, _p(workspace), _p(out), _p(depth),
                                              _p(acc), _stream()), "nerf_render_rays_grid_fwd")
     return out, depth, acc
 
@@ -1056,6 +1071,17 @@ def instant_decoder_encoded(net_params: Tensor, packed: Tensor, x_enc: Tensor, d
     return _InstantDecoderEncoded.apply(net_params, packed, x_enc, d_enc, train)
 
 
+def _table_arg(name: str, table, levels: HashLevelTable):
+    """(table, table_f32, table_f16) for the entries that take the hash table as fp32 [entries, 2] or as its fp16 copy: the checked
+    tensor -- the caller holds it until its launch is queued: a non-contiguous table is a fresh copy here -- and the pointer pair"""
+    if not isinstance(table, Tensor) or table.dtype not in (torch.float32, torch.float16):
+        raise TypeError(f"{name}: table must be an fp32 or fp16 tensor")
+    table = _dev(table, "table", table.dtype)
+    if table.numel() < 2 * levels.entries:
+        raise ValueError(f"{name}: table of {table.numel()} values, the levels address {2 * levels.entries}")
+    return (table, None, _p(table)) if table.dtype == torch.float16 else (table, _p(table), None)
+
+
 def instant_render_workspace_bytes(chunk: int, n_samples: int) -> int:
     return _lib.load().nerf_instant_render_workspace_bytes(chunk, n_samples)
 
@@ -1069,28 +1095,12 @@ def instant_render_rays_fwd(packed: Tensor, table: Tensor, levels: HashLevelTabl
     copy; ``workspace``: uint8, at least instant_render_workspace_bytes(chunk, n_samples) bytes (allocated here otherwise);
     its first int32 holds the last chunk's active count afterwards."""
     lib = _lib.load()
-    rays_o, rays_d = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d")
-    grid = _dev(binary_grid, "binary_grid", torch.bool)
-    packed = _dev(packed, "packed", torch.uint8)
-    if not isinstance(table, Tensor) or table.dtype not in (torch.float32, torch.float16):
-        raise TypeError("instant_render_rays_fwd: table must be an fp32 or fp16 tensor")
-    half = table.dtype == torch.float16
-    table = _dev(table, "table", table.dtype)
-    if table.numel() < 2 * levels.entries:
-        raise ValueError(f"instant_render_rays_fwd: table of {table.numel()} values, the levels address {2 * levels.entries}")
-    R = rays_o.shape[0]
-    chunk = max(1, min(int(chunk), max(R, 1)))
-    need = lib.nerf_instant_render_workspace_bytes(chunk, n_samples)
-    if workspace is None:
-        workspace = torch.empty(need, device=rays_o.device, dtype=torch.uint8)
-    elif _dev(workspace, "workspace", torch.uint8).numel() < need:
-        raise ValueError(f"instant_render_rays_fwd: workspace of {workspace.numel()} bytes, {need} needed for chunk {chunk} x {n_samples}")
-    bg = None if bg is None else _dev(bg, "bg")
-    out = torch.empty(R, 3, device=rays_o.device)
-    depth, acc = torch.empty(R, device=rays_o.device), torch.empty(R, device=rays_o.device)
-    _lib.check(lib.nerf_instant_render_rays_fwd(_p(packed), None if half else _p(table), _p(table) if half else None, levels.n_levels,
+    packed, grid, rays_o, rays_d, R, bg, bg_rows, chunk, workspace, out, depth, acc = _counted_render_args(
+        "instant_render_rays_fwd", lib.nerf_instant_render_workspace_bytes, packed, binary_grid, rays_o, rays_d, n_samples, bg, chunk, workspace)
+    table, table_f32, table_f16 = _table_arg("instant_render_rays_fwd", table, levels)
+    _lib.check(lib.nerf_instant_render_rays_fwd(_p(packed), table_f32, table_f16, levels.n_levels,
                                                 *levels.host_args(), float(hash_bound), _p(grid), grid.shape[0], float(grid_bound),
-                                                _p(rays_o), _p(rays_d), R, n_samples, float(near), float(far), _p(bg), _bg_rows(bg), chunk,
+                                                _p(rays_o), _p(rays_d), R, n_samples, float(near), float(far), _p(bg), bg_rows, chunk,
                                                 _p(workspace), _p(out), _p(depth), _p(acc), _stream()), "nerf_instant_render_rays_fwd")
     return out, depth, acc
 
@@ -1111,12 +1121,7 @@ def instant_grid_update(packed: Tensor, table: Tensor, levels: HashLevelTable, h
     Returns (grid fp32, binary_grid bool, count int64 [1] on the device: no host sync here); grids are [res, res, res] or [n]."""
     lib = _lib.load()
     packed = _dev(packed, "packed", torch.uint8)
-    if not isinstance(table, Tensor) or table.dtype not in (torch.float32, torch.float16):
-        raise TypeError("instant_grid_update: table must be an fp32 or fp16 tensor")
-    half = table.dtype == torch.float16
-    table = _dev(table, "table", table.dtype)
-    if table.numel() < 2 * levels.entries:
-        raise ValueError(f"instant_grid_update: table of {table.numel()} values, the levels address {2 * levels.entries}")
+    table, table_f32, table_f16 = _table_arg("instant_grid_update", table, levels)
     if isinstance(source, Tensor):
         pts = _dev(source, "pts")
         if pts.dim() != 2 or pts.shape[1] != 3:
@@ -1146,7 +1151,7 @@ def instant_grid_update(packed: Tensor, table: Tensor, levels: HashLevelTable, h
     if n == 0:               # an empty point buffer (its data pointer is NULL: the entry would take it for the lattice source)
         return grid, binary, torch.zeros(1, device=packed.device, dtype=torch.int64)
     count = torch.empty(1, device=packed.device, dtype=torch.int64)      # cleared by the call
-    _lib.check(lib.nerf_instant_grid_update(_p(packed), None if half else _p(table), _p(table) if half else None, levels.n_levels,
+    _lib.check(lib.nerf_instant_grid_update(_p(packed), table_f32, table_f16, levels.n_levels,
                                             *levels.host_args(), float(hash_bound), _p(pts), n, res, float(grid_bound), _p(grid), _p(binary),
                                             float(decay), 0 if prev is None else 1, float(threshold), _p(count), slab_cells, _p(workspace),
                                             _stream()), "nerf_instant_grid_update")

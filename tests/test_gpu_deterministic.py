@@ -71,6 +71,26 @@ def test_ordered_compaction_puts_the_slots_in_sample_order(det):
     assert none[2].shape[0] == 0 and bool((none[1] == -1).all())
 
 
+def test_ordered_compaction_past_the_workgroup_cap(det):
+    """33001 x 128 = 4,224,128 samples: 1032 passes for at most 1024 workgroups, so the count and place kernels take a second trip of
+    their grid-stride loops and index the segment table by pass = g0 / span there"""
+    ops = det
+    R, S = 33001, 128
+    o, d, _, g = _rays(R, 3)
+    u = torch.rand(R, S, generator=g).cuda()
+    grid = _sphere(64)
+    z1, s1, p1, v1 = ops.sample_compact(o, d, 2.0, 6.0, S, grid, 1.5, u=u)
+    ops.set_deterministic(False)
+    z0, s0, p0, v0 = ops.sample_compact(o, d, 2.0, 6.0, S, grid, 1.5, u=u)
+    ops.set_deterministic(True)
+    assert torch.equal(z0, z1) and p0.shape == p1.shape and p1.shape[0] > 0
+    assert torch.equal(s0 >= 0, s1 >= 0)
+    act = s1 >= 0
+    assert 0 < int(act[1024 * 4096:].sum()) < int(act.sum())                                 # both trips hold active samples
+    assert torch.equal(s1[act].long(), torch.arange(int(act.sum()), device="cuda"))          # sample order
+    assert torch.equal(p1, p0[s0[act].long()]) and torch.equal(v1, v0[s0[act].long()])       # the same points and directions, reordered
+
+
 def test_squared_norm_is_an_ordered_sum():
     """nerf_tv_normsq*: one partial per workgroup, added in workgroup order (every mode): the same bits on every launch"""
     import project_nerf_amd  # noqa: F401

@@ -123,6 +123,23 @@ def test_lattice_source_equals_the_loop_form(field, res, slab, half):
 
 
 @pytest.mark.parametrize("half", [False, True], ids=["fp32", "fp16"])
+def test_non_contiguous_table_is_copied_and_kept_until_the_launch(field, half):
+    """a strided view of the table: the wrapper's contiguous copy must outlive the grid, workspace and count it allocates after
+    making it (nothing else holds the copy), so the result is the contiguous table's"""
+    table = field.tab(half)
+    wide = torch.zeros(table.shape[0], 4, dtype=table.dtype, device="cuda")
+    wide[:, :2] = table
+    view = wide[:, :2]
+    assert not view.is_contiguous() and torch.equal(view, table)
+    from project_nerf_amd import ops
+    sigma = field.loop_sigma(33, half)
+    thr = median_threshold(sigma)
+    want = loop_threshold(sigma, thr)
+    got = ops.instant_grid_update(field.packed, view, field.levels, BOUND, 33, BOUND, thr, slab_cells=4096)
+    assert_same_grids(got, want, "res 33, strided table")
+
+
+@pytest.mark.parametrize("half", [False, True], ids=["fp32", "fp16"])
 def test_grid_wider_than_the_hash_box(field, half):
     """grid_bound 2.0 > hash_bound 1.5: the outer lattice nodes lie outside the encoder's box and are clamped by it"""
     sigma = field.loop_sigma(17, half, grid_bound=2.0, hash_bound=1.5)

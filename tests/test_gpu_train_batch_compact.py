@@ -14,8 +14,12 @@ pytestmark = pytest.mark.gpu
 NEAR, FAR, BOUND, RES, SEED = 2.0, 6.0, 1.5, 8, 11
 # (batch, n_samples, first_ray)
 CASES = {"smallest": (1, 2, 0), "one-pass": (64, 64, 0), "4095-straddle": (63, 65, 0), "4097-second-pass": (241, 17, 0),
-         "several-workgroups-shard": (700, 64, 1300)}
+         "several-workgroups-shard": (700, 64, 1300),
+         # 4,194,432 samples: one pass more than the 1024-workgroup cap covers, so workgroup 0 takes a second, ragged trip of the
+         # grid-stride loop (the smallest such count); the "seeded" grid only
+         "past-the-workgroup-cap": (32769, 128, 0)}
 GRIDS = ("ones", "zeros", "seeded")
+PLAIN_FORM = [(case, kind) for case in CASES for kind in GRIDS if case != "past-the-workgroup-cap" or kind == "seeded"]
 
 
 @pytest.fixture(scope="module")
@@ -121,8 +125,7 @@ def check_against_reference(out, count, ref):
     assert is_filled(out["pts"][count:]) and is_filled(out["dirs"][count:])      # nothing is written from row `count` on
 
 
-@pytest.mark.parametrize("kind", GRIDS)
-@pytest.mark.parametrize("case", list(CASES))
+@pytest.mark.parametrize("case,kind", PLAIN_FORM)
 def test_plain_form_equals_the_two_calls(ops, lib, scene, case, kind):
     ref = reference(ops, lib, scene, case, kind)
     batch, S, _ = CASES[case]
