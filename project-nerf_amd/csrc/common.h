@@ -45,7 +45,7 @@ struct Options {
   int composite_wgs_per_cu = 2;  // fused compositing + loss backward: workgroups per CU.  Every workgroup ends with same-address atomics (loss, regulariser,
                                  // maximum), which retire one after the other in L2: 8 per CU 58 us, 4: 35, 2: 27, 1: 29 (8192 rays x 64, Part 4 step)
   int hash_xcd = 1;              // 1: hash-grid gather kernels launch XCD-aware (levels x and x + 8 on XCD x); 0: level-major 2-D launch (A/B)
-  int hash_fwd_lds_kb = 36;      // dynamic LDS per hash-forward workgroup (occupancy throttle, see nerf_hash_encode_fwd); 0: none
+  int hash_fwd_lds_kb = 36;      // dynamic LDS per hash-forward workgroup (occupancy throttle, see gather_shape in hashgrid.hip); 0: none
   int tv_blocks = 0;             // > 0: workgroups (of 1024 threads) of the TV + squared-norm pass; 0: one per CU (A/B)
   int deterministic = 0;         // 1: every sum whose order depends on scheduling takes an ordered form -- compaction slots in sample order,
                                  // tiny-MLP weight gradients through partial tiles, hash bins never cut, d x from the hash grid level by level,
@@ -61,9 +61,20 @@ int ensure_dynamic_lds(const void* kernel, int bytes, const char* what);
 // Launches whose sample count is a DEVICE word (the compaction's active count; at most `capacity`, which sizes the grids), for
 // render_instant.hip's launch chain: no host ever reads the count.  hashgrid.hip: bf16 operand image [roundup(capacity, 128), 32] of
 // the first *count points; imlp.hip: the inference decoder chain on that image.  Nothing is touched when *count is 0.
+// LevelArgs: the level description of a hash grid as the extern "C" entries receive it (host arrays of n_levels elements each).
+struct LevelArgs {
+  int n_levels;
+  const float* scale;
+  const unsigned *res, *size, *offset, *dense;
+  float bound;
+  unsigned entries() const {            // of one table: max(offset + size)
+    unsigned e = 0;
+    for (int i = 0; i < n_levels; ++i) e = offset[i] + size[i] > e ? offset[i] + size[i] : e;
+    return e;
+  }
+};
 int hash_fwd_counted(const float* pts, const unsigned* count, int64_t capacity, const float* table_f32, const void* table_f16,
-                     int n_levels, const float* scale_host, const unsigned* res_host, const unsigned* size_host,
-                     const unsigned* offset_host, const unsigned* dense_host, float bound, void* out_nat, nerf_stream_t stream);
+                     const LevelArgs& levels, void* out_nat, nerf_stream_t stream);
 int imlp_fwd_counted(const void* packed, const void* hash_nat, const float* dirs, const unsigned* count, int64_t capacity, float* rgb,
                      float* sigma, nerf_stream_t stream);
 // The two launches of nerf_instant_grid_update (grid.hip) per slab of occupancy-grid cells.  hashgrid.hip: bf16 operand image
@@ -71,8 +82,7 @@ int imlp_fwd_counted(const void* packed, const void* hash_nat, const float* dirs
 // imlp.hip: the sigma-net alone on that image, folded into grid / binary_grid (already offset to the slab's first cell) with
 // nerf_grid_update's arithmetic, active cells added to *active_count (cleared by the caller).
 int hash_fwd_lattice(int64_t cell0, int64_t n_cells, int resolution, float grid_bound, const float* table_f32, const void* table_f16,
-                     int n_levels, const float* scale_host, const unsigned* res_host, const unsigned* size_host,
-                     const unsigned* offset_host, const unsigned* dense_host, float bound, void* out_nat, nerf_stream_t stream);
+                     const LevelArgs& levels, void* out_nat, nerf_stream_t stream);
 int imlp_sigma_grid(const void* packed, const void* hash_nat, int64_t n_cells, float* grid, uint8_t* binary_grid, float decay, int dynamic,
                     float threshold, unsigned long long* active_count, nerf_stream_t stream);
 // mlp_fwd.hip: the 8x256 inference chain in point mode (64 samples per wave) on the first *count rows of pts / dirs, for

@@ -103,8 +103,8 @@ extern "C" int nerf_instant_grid_update(const void* packed, const float* table_f
                                     hash_bound, workspace, 0, stream);
       if (rc != NERF_OK) return rc;
     } else {
-      rc = hash_fwd_lattice(c0, n, resolution, grid_bound, table_f32, table_f16, n_levels, scale_host, res_host, size_host, offset_host,
-                            dense_host, hash_bound, workspace, stream);
+      rc = hash_fwd_lattice(c0, n, resolution, grid_bound, table_f32, table_f16,
+                            LevelArgs{n_levels, scale_host, res_host, size_host, offset_host, dense_host, hash_bound}, workspace, stream);
       if (rc != NERF_OK) return rc;
     }
     rc = imlp_sigma_grid(packed, workspace, n, grid + c0, binary_grid + c0, decay, dynamic, threshold, active_count, stream);

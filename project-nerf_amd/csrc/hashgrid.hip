@@ -11,136 +11,22 @@
 // hash-map budget, xor-prime hash above), trilinear blend of F = 2 features.  Gather-bound:
 // 16 levels x 8 corners x 8 B (fp32 table) per point; the 52 MB table lives in the 256 MB
 // Infinity Cache.  Backward: 16 float atomics per (point, level).
+// The cell arithmetic itself (corners, gathers, blend, operand-image store, position gradient) is hash_cell.h.
 #include <stdlib.h>
+#include <type_traits>
 #include "common.h"
+#include "hash_cell.h"
 #include "lattice.h"
 
 namespace nerf {
 
-constexpr int kMaxLevels = 16;
-
-struct HashLevels {
-  float scale[kMaxLevels];
-  unsigned res[kMaxLevels];
-  unsigned size[kMaxLevels];
-  unsigned offset[kMaxLevels];
-  unsigned dense[kMaxLevels];
-  int n_levels;
-  float bound;
-};
-
-struct Corner {
-  unsigned idx[8];
-  float w[8];
-};
-
-__device__ __forceinline__ Corner corners_of(const HashLevels& L, int lvl, float px, float py, float pz) {
-  // HashRepresentation.forward: (x + bound) / (2 bound), clamp to [0, 1]  (embeddings.py:86-87)
-  const float two_b = 2.0f * L.bound;
-  float x01[3] = {add_rn(px, L.bound) / two_b, add_rn(py, L.bound) / two_b, add_rn(pz, L.bound) / two_b};
-  unsigned cell[3];
-  float frac[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float c = fminf(fmaxf(x01[a], 0.0f), 1.0f);
-    const float pos = add_rn(mul_rn(c, L.scale[lvl]), 0.5f);
-    const float fl = floorf(pos);
-    frac[a] = sub_rn(pos, fl);
-    cell[a] = (unsigned)fl;
-  }
-  Corner out;
-  const unsigned res = L.res[lvl], size = L.size[lvl];
-  const bool pow2 = (size & (size - 1)) == 0;
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const unsigned gx = cell[0] + (c & 1), gy = cell[1] + ((c >> 1) & 1), gz = cell[2] + ((c >> 2) & 1);
-    const float wx = (c & 1) ? frac[0] : sub_rn(1.0f, frac[0]);
-    const float wy = (c & 2) ? frac[1] : sub_rn(1.0f, frac[1]);
-    const float wz = (c & 4) ? frac[2] : sub_rn(1.0f, frac[2]);
-    out.w[c] = mul_rn(mul_rn(wx, wy), wz);
-    unsigned e;
-    if (L.dense[lvl]) {
-      // (gx + gy res + gz res^2) % size: every coordinate is at most res and size >= res^3, so the index is below 2 size --
-      // one conditional subtraction gives the remainder (a runtime udiv costs ~30 VALU ops per corner)
-      e = gx + gy * res + gz * res * res;
-      e = e >= size ? e - size : e;
-    }
-    else {
-      const unsigned h = (gx * 1u) ^ (gy * 2654435761u) ^ (gz * 805459861u);
-      e = pow2 ? (h & (size - 1)) : (h % size);     // same value; a runtime udiv costs ~30 VALU ops per corner
-    }
-    out.idx[c] = e + L.offset[lvl];
-  }
-  return out;
-}
-
-// out_f32 [n, 2L] row-major (optional), out_nat: bf16 natural-order operand blocks (optional):
-// [wave tile of 32 points][k-step ks = level/8][lane (c, h)][8] with feature 16ks + 8h + j
-// TableT = float2: the fp32 parameters themselves.  TableT = half2_t: an fp16 copy kept by the optimiser
-// (nerf_adamw_clip_step_shadow) -- half the bytes per gather and twice the entries per cache line; tinycudann
-// itself evaluates its grid from fp16 parameters next to an fp32 master copy.
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 // table slices of the binned backward (see below): the forward can already count the corners per (level, slice)
 constexpr unsigned kSliceLog2 = 12, kSlice = 1u << kSliceLog2;   // 4096 entries x 2 features x 8 B = 64 KiB of LDS
 struct LevelBins { unsigned bin0[kMaxLevels + 1]; };             // first bin of every level; bin0[n_levels] = number of bins
-__device__ __forceinline__ float2 table_entry(const float2* t, unsigned i) { return t[i]; }
-__device__ __forceinline__ float2 table_entry(const half2_t* t, unsigned i) {
-  const half2_t h = t[i];
-  return make_float2((float)h[0], (float)h[1]);
-}
-// Which (level, point chunk) a workgroup of the gather kernels works on.  n_chunks > 0 -- XCD-aware 1-D launch of
-// 8 * ceil(n_levels / 8) * n_chunks workgroups: the hardware deals consecutive workgroup ids to the eight XCDs in turn, so
-// workgroup b runs on XCD b % 8; it takes level (b % 8) + 8 * ((b / 8) / n_chunks), i.e. EVERY lookup into the tables of levels
-// x and x + 8 goes through the L2 of XCD x: one hashed level (2 MB of fp16 entries) and one coarse level per 4-MB L2, each
-// table fetched from HBM once per launch instead of once per XCD (level-major 2-D launch: 335 MB fetched for 105 MB of
-// gathers on 200 k points).  n_chunks == 0: the 2-D launch (blockIdx.y = level).
-struct LevelChunk { int lvl, chunk, chunks; };
-__device__ __forceinline__ LevelChunk level_chunk(int n_levels, int n_chunks) {
-  if (n_chunks <= 0) return {(int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x};
-  const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-  return {xcd + 8 * (j / n_chunks), j % n_chunks, n_chunks};
-}
-inline dim3 level_chunk_grid(int n_levels, int64_t blocks, bool xcd_aware) {
-  return xcd_aware ? dim3((unsigned)(8 * ((n_levels + 7) / 8) * blocks)) : dim3((unsigned)blocks, (unsigned)n_levels);
-}
-
-// The eight entries of a cell, gathered with as few cache-line requests as the addresses allow.  Corners 2j and 2j+1 differ in x
-// only: on a dense level their entries are neighbours (e, e + 1), on a hashed level with an even cell x they are e and e ^ 1
-// (the hash XORs x in unmultiplied) -- either way one 8-byte (fp16 table) / 16-byte (fp32) load at min(e0, e1) returns both.
-// Otherwise (hashed level, odd x: the carry changes higher bits) the second corner takes its own load.  The gather kernels are
-// bound by the texture path's line rate (one 64-byte line per lane and request on the hashed levels), not by bytes.
-struct half2x2 { half2_t a, b; };
-__device__ __forceinline__ void table_pair(const float2* t, unsigned lo, float2& v0, float2& v1) {
-  float4 q;
-  __builtin_memcpy(&q, reinterpret_cast<const char*>(t + lo), 16);      // 8-byte aligned: two dwordx2 or one dwordx4
-  v0 = make_float2(q.x, q.y);
-  v1 = make_float2(q.z, q.w);
-}
-__device__ __forceinline__ void table_pair(const half2_t* t, unsigned lo, float2& v0, float2& v1) {
-  half2x2 q;
-  __builtin_memcpy(&q, reinterpret_cast<const char*>(t + lo), 8);       // 4-byte aligned dwordx2
-  v0 = make_float2((float)q.a[0], (float)q.a[1]);
-  v1 = make_float2((float)q.b[0], (float)q.b[1]);
-}
-template <class TableT>
-__device__ __forceinline__ void gather_cell(const TableT* __restrict__ table, const Corner& c, float2 (&v)[8]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const unsigned e0 = c.idx[2 * j], e1 = c.idx[2 * j + 1], lo = e0 < e1 ? e0 : e1;
-    if ((e0 > e1 ? e0 - e1 : e1 - e0) == 1u) {
-      float2 p0, p1;
-      table_pair(table, lo, p0, p1);                       // entries lo and lo + 1 = the two corners
-      v[2 * j] = e0 == lo ? p0 : p1;
-      v[2 * j + 1] = e0 == lo ? p1 : p0;
-    } else {
-      v[2 * j] = table_entry(table, e0);
-      v[2 * j + 1] = table_entry(table, e1);
-    }
-  }
-}
 
 struct TableSet { int n; long long table_stride, out_stride; };     // n tables, entries between them, operand-image elements between their outputs
 
+// out_f32 [n, 2L] row-major (optional), out_nat: bf16 / fp16 natural-order operand blocks (optional, store_operand)
 template <class TableT>
 __global__ void __launch_bounds__(256)
 hash_fwd_kernel(const float* __restrict__ pts, int64_t n, int64_t n_pad, const TableT* __restrict__ table, HashLevels L,
@@ -150,8 +36,7 @@ hash_fwd_kernel(const float* __restrict__ pts, int64_t n, int64_t n_pad, const T
   // backward (hash_bin_count_*), done here where the corner indices already exist; LDS histogram per workgroup (the dynamic
   // LDS allocation, >= 4 bytes per slice of the level), one global add per non-empty bin and workgroup
   extern __shared__ unsigned hist_lds[];
-  // the operand image is padded to whole 128-point tiles: pad rows repeat the last point so that
-  // every stashed value is finite (their gradients are zero downstream)
+  // the operand image is padded to whole 128-point tiles (pad_row)
   // level-major: blockIdx.y = level, consecutive lanes = consecutive points = neighbouring samples of a
   // ray, so a wave's gathers at the coarse and middle levels fall into few cache lines (point-major,
   // 16 lanes of a wave hit 16 different level tables)
@@ -170,39 +55,22 @@ hash_fwd_kernel(const float* __restrict__ pts, int64_t n, int64_t n_pad, const T
   }
   for (int64_t p = lc.chunk * (int64_t)blockDim.x + threadIdx.x; p < rows; p += (int64_t)lc.chunks * blockDim.x) {
     const int64_t g = p * L.n_levels + lvl;
-    const int64_t ps = p < n ? p : n - 1;
+    const int64_t ps = pad_row(p, n);
     const Corner c = corners_of(L, lvl, pts[ps * 3 + 0], pts[ps * 3 + 1], pts[ps * 3 + 2]);
     if (hist_count != nullptr && p < n) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) atomicAdd(&hist_lds[(c.idx[k] - lvl_offset) >> kSliceLog2], 1u);
     }
-    float f0 = 0.0f, f1 = 0.0f;
-    float2 v[8];
-    gather_cell(table, c, v);
+    const float2 f = cell_features(table, c);
+    if (idx_out != nullptr && p < n) {
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {                           // the sums run over the corners in the reference's order
-      f0 += c.w[k] * v[k].x;
-      f1 += c.w[k] * v[k].y;
-      if (idx_out != nullptr && p < n) idx_out[g * 8 + k] = c.idx[k];
+      for (int k = 0; k < 8; ++k) idx_out[g * 8 + k] = c.idx[k];
     }
     if (out_f32 != nullptr && p < n) {
-      out_f32[p * (2 * L.n_levels) + 2 * lvl + 0] = f0;
-      out_f32[p * (2 * L.n_levels) + 2 * lvl + 1] = f1;
+      out_f32[p * (2 * L.n_levels) + 2 * lvl + 0] = f.x;
+      out_f32[p * (2 * L.n_levels) + 2 * lvl + 1] = f.y;
     }
-    if (out_nat != nullptr) {
-      const int f = 2 * lvl, ks = f >> 4, h = (f >> 3) & 1, j = f & 7;
-      const int64_t wt = p >> 5;
-      const int col = (int)(p & 31);
-      const int n_ks = (2 * L.n_levels + 15) / 16;
-      __bf16* dst = out_nat + ((wt * n_ks + ks) * 64 + 2 * col + h) * 8 + j;
-      if (nat_f16) {                       // fp16 operand image (the Part 4 forward chains contract fp16 operands)
-        reinterpret_cast<_Float16*>(dst)[0] = (_Float16)f0;
-        reinterpret_cast<_Float16*>(dst)[1] = (_Float16)f1;
-      } else {
-        dst[0] = (__bf16)f0;
-        dst[1] = (__bf16)f1;
-      }
-    }
+    if (out_nat != nullptr) store_operand(out_nat, p, lvl, L.n_levels, f.x, f.y, nat_f16 != 0);
   }
   if (hist_count != nullptr) {
     __syncthreads();
@@ -211,94 +79,52 @@ hash_fwd_kernel(const float* __restrict__ pts, int64_t n, int64_t n_pad, const T
   }
 }
 
-// hash_fwd_kernel's bf16 operand image with the point count read from DEVICE memory (nerf_instant_render_rays_fwd: the count is the
-// compaction's, which no host ever sees).  The launch is sized for `capacity` points; the loop bounds come from *count (clamped to the
-// capacity: a count the compaction cannot produce must not turn into a store outside the image).  Same corners, same gathers, same
-// eight-term sums in the same order, same rounding and operand address as hash_fwd_kernel; pad rows repeat point n - 1; no fp32
-// rows, corner indices, histogram or table set.  n == 0 leaves before n - 1 exists.
+// hash_fwd_kernel's bf16 operand image and nothing else (no fp32 rows, corner indices, histogram or table set) of n (> 0) points
+// that point_of(row, x, y, z) supplies; the rows up to the 128-row tile are pad rows.  The body of the two kernels below.
+template <class TableT, class PointOf>
+__device__ __forceinline__ void operand_image_of(int64_t n, const TableT* __restrict__ table, const HashLevels& L,
+                                                 __bf16* __restrict__ out_nat, int n_chunks, PointOf point_of) {
+  const int64_t n_pad = (n + 127) / 128 * 128;
+  const LevelChunk lc = level_chunk(L.n_levels, n_chunks);
+  if (lc.lvl >= L.n_levels) return;
+  for (int64_t p = lc.chunk * (int64_t)blockDim.x + threadIdx.x; p < n_pad; p += (int64_t)lc.chunks * blockDim.x) {
+    float x, y, z;
+    point_of(pad_row(p, n), x, y, z);
+    const float2 f = cell_features(table, corners_of(L, lc.lvl, x, y, z));
+    store_operand(out_nat, p, lc.lvl, L.n_levels, f.x, f.y, false);
+  }
+}
+
+// The point count is read from DEVICE memory (nerf_instant_render_rays_fwd: the count is the compaction's, which no host ever
+// sees).  The launch is sized for `capacity` points; the loop bounds come from *count (clamped to the capacity: a count the
+// compaction cannot produce must not turn into a store outside the image).  n == 0 leaves before n - 1 exists.
 template <class TableT>
 __global__ void __launch_bounds__(256)
 hash_fwd_counted_kernel(const float* __restrict__ pts, const unsigned* __restrict__ count, int64_t capacity,
                         const TableT* __restrict__ table, HashLevels L, __bf16* __restrict__ out_nat, int n_chunks) {
-  int64_t n = (int64_t)*count;
+  const int64_t n = (int64_t)*count;
   if (n == 0) return;
-  n = n < capacity ? n : capacity;
-  const int64_t n_pad = (n + 127) / 128 * 128;
-  const LevelChunk lc = level_chunk(L.n_levels, n_chunks);
-  if (lc.lvl >= L.n_levels) return;
-  const int lvl = lc.lvl;
-  for (int64_t p = lc.chunk * (int64_t)blockDim.x + threadIdx.x; p < n_pad; p += (int64_t)lc.chunks * blockDim.x) {
-    const int64_t ps = p < n ? p : n - 1;
-    const Corner c = corners_of(L, lvl, pts[ps * 3 + 0], pts[ps * 3 + 1], pts[ps * 3 + 2]);
-    float f0 = 0.0f, f1 = 0.0f;
-    float2 v[8];
-    gather_cell(table, c, v);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {                           // the sums run over the corners in the reference's order
-      f0 += c.w[k] * v[k].x;
-      f1 += c.w[k] * v[k].y;
-    }
-    const int f = 2 * lvl, ks = f >> 4, h = (f >> 3) & 1, j = f & 7;
-    const int64_t wt = p >> 5;
-    const int col = (int)(p & 31);
-    const int n_ks = (2 * L.n_levels + 15) / 16;
-    __bf16* dst = out_nat + ((wt * n_ks + ks) * 64 + 2 * col + h) * 8 + j;
-    dst[0] = (__bf16)f0;
-    dst[1] = (__bf16)f1;
-  }
+  operand_image_of(n < capacity ? n : capacity, table, L, out_nat, n_chunks, [pts](int64_t ps, float& x, float& y, float& z) {
+    x = pts[ps * 3 + 0]; y = pts[ps * 3 + 1]; z = pts[ps * 3 + 2];
+  });
 }
 
-// hash_fwd_counted_kernel's bf16 operand image for points that are never written out: point p of the slab is cell cell0 + p of the
-// occupancy grid's 'ij' lattice (nerf_instant_grid_update; lattice.h gives the node coordinates nerf_grid_lattice would store).
-// n (> 0) cells, known to the host; pad rows up to the 128-row tile repeat the slab's last cell.  Same corners, same gathers, same
-// eight-term sums in the same order, same rounding and operand address as hash_fwd_kernel.
+// Points that are never written out: point p of the slab is cell cell0 + p of the occupancy grid's 'ij' lattice
+// (nerf_instant_grid_update; lattice.h gives the node coordinates nerf_grid_lattice would store).  n (> 0) cells, known to the host.
 template <class TableT>
 __global__ void __launch_bounds__(256)
 hash_fwd_lattice_kernel(int64_t cell0, int64_t n, int res, float grid_bound, float step, const TableT* __restrict__ table,
                         HashLevels L, __bf16* __restrict__ out_nat, int n_chunks) {
-  const int64_t n_pad = (n + 127) / 128 * 128;
-  const LevelChunk lc = level_chunk(L.n_levels, n_chunks);
-  if (lc.lvl >= L.n_levels) return;
-  const int lvl = lc.lvl;
-  for (int64_t p = lc.chunk * (int64_t)blockDim.x + threadIdx.x; p < n_pad; p += (int64_t)lc.chunks * blockDim.x) {
-    const int64_t ps = p < n ? p : n - 1;
+  operand_image_of(n, table, L, out_nat, n_chunks, [=](int64_t ps, float& x, float& y, float& z) {
     int ix, iy, iz;
     lattice_cell(cell0 + ps, res, ix, iy, iz);
-    const Corner c = corners_of(L, lvl, lattice_node(ix, res, grid_bound, step), lattice_node(iy, res, grid_bound, step),
-                                lattice_node(iz, res, grid_bound, step));
-    float f0 = 0.0f, f1 = 0.0f;
-    float2 v[8];
-    gather_cell(table, c, v);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {                           // the sums run over the corners in the reference's order
-      f0 += c.w[k] * v[k].x;
-      f1 += c.w[k] * v[k].y;
-    }
-    const int f = 2 * lvl, ks = f >> 4, h = (f >> 3) & 1, j = f & 7;
-    const int64_t wt = p >> 5;
-    const int col = (int)(p & 31);
-    const int n_ks = (2 * L.n_levels + 15) / 16;
-    __bf16* dst = out_nat + ((wt * n_ks + ks) * 64 + 2 * col + h) * 8 + j;
-    dst[0] = (__bf16)f0;
-    dst[1] = (__bf16)f1;
-  }
+    x = lattice_node(ix, res, grid_bound, step); y = lattice_node(iy, res, grid_bound, step); z = lattice_node(iz, res, grid_bound, step);
+  });
 }
 
-// d_feat [n, 2L] fp32 -> scatter into d_table [E, 2].  Level-major work split (blockIdx.y = level,
-// consecutive lanes = consecutive points, i.e. neighbouring samples of a ray): a wave's 64 x 16
-// float atomics then fall into ONE level's table, mostly into neighbouring cells, instead of 16
-// unrelated regions.  Levels whose whole table fits in LDS (<= kLdsEntries entries: the dense
-// 16^3 and 24^3 levels, where thousands of samples hit each cell) are reduced in LDS first and
-// flushed with one well-shaped (contiguous) global atomic per entry per workgroup.
-// The larger levels use global float atomics, coalesced four lanes per (point, level) (see the
-// kernel body).  Built, measured on 200 k points and dropped: entries sliced per XCD by
-// HW_REG_XCC_ID so that every 128-byte line stays in one L2 -- no change; owner-computes (a
-// workgroup per 16384-entry slice scans the whole batch into LDS) -- slower, the 32-fold
-// recomputation of the corner hashes costs more than the atomics it removes; a packed-fp16
-// gradient table (one atomic per corner) -- 1.29 ms against 0.72 ms for the coalesced fp32 form.
 // Gradient with respect to the ENCODED POSITION (dynamic fields: x_canonical = x + delta_x is encoded, so the
 // loss reaches the deformation through d features / d x; reference src/core.py:268-271, 341-344):
-//   d f / d x01_a = scale_l * sum_corners table[corner] * (+1 | -1 along a) * prod_{b != a} w_b,
+//   d f / d x01_a = scale_l * sum_corners table[corner] * (+1 | -1 along a) * prod_{b != a} w_b   (cell_position_gradient),
 //   d x01 / d x = 1 / (2 bound) inside the box, 0 where HashRepresentation's clamp is active.
 // One thread per (point, level), level-major like the forward; the 16 levels of a point meet in d_pts through
 // float atomics (three per thread; d_pts is zeroed by the launcher).
@@ -319,30 +145,13 @@ hash_bwd_input_kernel(const float* __restrict__ pts, int64_t n, const TableT* __
     if (g0 == 0.0f && g1 == 0.0f) continue;
     const float px = pts[p * 3 + 0], py = pts[p * 3 + 1], pz = pts[p * 3 + 2];
     const Corner c = corners_of(L, lvl, px, py, pz);
-    // per-axis weights recovered from the same arithmetic as corners_of
-    float frac[3], x01[3] = {add_rn(px, L.bound) / two_b, add_rn(py, L.bound) / two_b, add_rn(pz, L.bound) / two_b};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float cl = fminf(fmaxf(x01[a], 0.0f), 1.0f);
-      const float pos = add_rn(mul_rn(cl, L.scale[lvl]), 0.5f);
-      frac[a] = sub_rn(pos, floorf(pos));
-    }
-    float d[3] = {0.0f, 0.0f, 0.0f};
-    float2 tv[8];
-    gather_cell(table, c, tv);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float2 v = tv[k];
-      const float gv = g0 * v.x + g1 * v.y;
-      const float wx = (k & 1) ? frac[0] : 1.0f - frac[0], wy = (k & 2) ? frac[1] : 1.0f - frac[1], wz = (k & 4) ? frac[2] : 1.0f - frac[2];
-      d[0] += gv * ((k & 1) ? 1.0f : -1.0f) * wy * wz;
-      d[1] += gv * ((k & 2) ? 1.0f : -1.0f) * wx * wz;
-      d[2] += gv * ((k & 4) ? 1.0f : -1.0f) * wx * wy;
-    }
+    const CellAxes ax = cell_axes(L, lvl, px, py, pz);
+    float d[3];
+    cell_position_gradient(table, c, ax.frac, g0, g1, d);
     const float s = L.scale[lvl] / two_b;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      const bool inside = x01[a] >= 0.0f && x01[a] <= 1.0f;          // torch.clamp passes the gradient on its closed interval
+      const bool inside = ax.x01[a] >= 0.0f && ax.x01[a] <= 1.0f;    // torch.clamp passes the gradient on its closed interval
       if (inside && d[a] != 0.0f) atomicAdd(d_pts + p * 3 + a, d[a] * s);
     }
   }
@@ -357,19 +166,16 @@ hash_bwd_input_ordered_kernel(const float* __restrict__ pts, int64_t n, const Ta
   const float two_b = 2.0f * L.bound;
   for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
     const float px = pts[p * 3 + 0], py = pts[p * 3 + 1], pz = pts[p * 3 + 2];
-    const float x01[3] = {add_rn(px, L.bound) / two_b, add_rn(py, L.bound) / two_b, add_rn(pz, L.bound) / two_b};
+    const float x01[3] = {box_coordinate(L, px), box_coordinate(L, py), box_coordinate(L, pz)};
     float sum[3] = {0.0f, 0.0f, 0.0f};
     for (int lvl = 0; lvl < L.n_levels; ++lvl) {
       const float g0 = d_feat[p * (2 * L.n_levels) + 2 * lvl + 0], g1 = d_feat[p * (2 * L.n_levels) + 2 * lvl + 1];
       if (g0 == 0.0f && g1 == 0.0f) continue;
       const Corner c = corners_of(L, lvl, px, py, pz);
-      float frac[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const float cl = fminf(fmaxf(x01[a], 0.0f), 1.0f);
-        const float pos = add_rn(mul_rn(cl, L.scale[lvl]), 0.5f);
-        frac[a] = sub_rn(pos, floorf(pos));
-      }
+      const CellAxes ax = cell_axes(L, lvl, px, py, pz);
+      const float (&frac)[3] = ax.frac;
+      // cell_position_gradient's loop, written out: inlined from there, the compiler rounds the other product of g . v in this
+      // kernel, and every result changes in the last bit
       float d[3] = {0.0f, 0.0f, 0.0f};
       float2 tv[8];
       gather_cell(table, c, tv);
@@ -395,6 +201,19 @@ hash_bwd_input_ordered_kernel(const float* __restrict__ pts, int64_t n, const Ta
   }
 }
 
+
+// d_feat [n, 2L] fp32 -> scatter into d_table [E, 2].  Level-major work split (blockIdx.y = level,
+// consecutive lanes = consecutive points, i.e. neighbouring samples of a ray): a wave's 64 x 16
+// float atomics then fall into ONE level's table, mostly into neighbouring cells, instead of 16
+// unrelated regions.  Levels whose whole table fits in LDS (<= kLdsEntries entries: the dense
+// 16^3 and 24^3 levels, where thousands of samples hit each cell) are reduced in LDS first and
+// flushed with one well-shaped (contiguous) global atomic per entry per workgroup.
+// The larger levels use global float atomics, coalesced four lanes per (point, level) (see the
+// kernel body).  Built, measured on 200 k points and dropped: entries sliced per XCD by
+// HW_REG_XCC_ID so that every 128-byte line stays in one L2 -- no change; owner-computes (a
+// workgroup per 16384-entry slice scans the whole batch into LDS) -- slower, the 32-fold
+// recomputation of the corner hashes costs more than the atomics it removes; a packed-fp16
+// gradient table (one atomic per corner) -- 1.29 ms against 0.72 ms for the coalesced fp32 form.
 constexpr int kLdsEntries = 16384;      // 128 KiB of float2
 template <bool in_lds>
 __global__ void __launch_bounds__(512)
@@ -1120,19 +939,8 @@ hash_bin_overflow_kernel(BinHeader* __restrict__ header, const BinRecord* __rest
   atomicExch(&h[threadIdx.x], 0u);
 }
 
-// The level description every extern "C" entry receives as seven arguments of these names (host arrays of n_levels elements each).
+// The level description (LevelArgs, common.h) every extern "C" entry of this file receives as seven arguments of these names.
 #define LEVEL_ARGS LevelArgs{n_levels, scale_host, res_host, size_host, offset_host, dense_host, bound}
-struct LevelArgs {
-  int n_levels;
-  const float* scale;
-  const unsigned *res, *size, *offset, *dense;
-  float bound;
-  unsigned entries() const {            // of one table: max(offset + size)
-    unsigned e = 0;
-    for (int i = 0; i < n_levels; ++i) e = offset[i] + size[i] > e ? offset[i] + size[i] : e;
-    return e;
-  }
-};
 
 static int fill_levels(HashLevels& L, const LevelArgs& lv) {
   if (lv.n_levels < 1 || lv.n_levels > kMaxLevels) return fail(NERF_EINVAL, "hash grid: n_levels=%d (1..16)", lv.n_levels);
@@ -1252,6 +1060,38 @@ static int run_binned(const BinnedCall& c, const float* pts, int64_t n, float* d
 
 using namespace nerf;
 
+// The launch shape of the gather kernels for `rows` rows on `levels` (virtual) levels: one thread per (row, level), at most 2048
+// workgroups of 256 per level, XCD-aware placement unless option hash_xcd is 0 (level_chunk), and for the forwards the
+// occupancy throttle: they use no LDS (but for the histogram); asking for 36 KiB per workgroup leaves 4 workgroups (1024 threads)
+// per CU, i.e. about 1.3 level tables in flight on the chip instead of 2.6 -- the 2 MB tables of the hashed levels then stay in
+// the 4 MB L2 of each XCD (91 -> 85 us on 200 k points; 3 or 2 workgroups per CU: 98 us).  The input gradient asks for none.
+struct GatherShape {
+  int64_t blocks;
+  int lds;                              // bytes, option hash_fwd_lds_kb
+  dim3 grid;
+  int n_chunks;
+};
+static GatherShape gather_shape(int64_t rows, int levels) {
+  GatherShape s;
+  s.blocks = (rows + 255) / 256;
+  if (s.blocks > 2048) s.blocks = 2048;
+  const int lds_kb = options().hash_fwd_lds_kb;
+  s.lds = (lds_kb < 0 ? 0 : (lds_kb > 64 ? 64 : lds_kb)) * 1024;
+  const bool xcd = options().hash_xcd != 0;
+  s.grid = level_chunk_grid(levels, s.blocks, xcd);
+  s.n_chunks = xcd ? (int)s.blocks : 0;
+  return s;
+}
+static int64_t tile_rows(int64_t n) { return (n + 127) / 128 * 128; }      // rows of the operand image of n points
+
+// launch(table) with the table as the type it has: the fp16 copy where there is one, else the fp32 parameters
+template <class Launch>
+static void with_table(const float* table_f32, const void* table_f16, Launch launch) {
+  if (table_f16 != nullptr) launch(static_cast<const half2_t*>(table_f16));
+  else launch(reinterpret_cast<const float2*>(table_f32));
+}
+template <class TablePtr> using table_t = std::remove_const_t<std::remove_pointer_t<TablePtr>>;      // a kernel's TableT
+
 struct FwdExtras {                      // what only some forward entries ask for
   int nat_f16 = 0;                      // the operand image in fp16 instead of bf16
   void* bwd_workspace = nullptr;        // also count the corners per (level, slice) into the binned backward's workspace
@@ -1268,14 +1108,8 @@ static int hash_fwd_impl(const float* pts, int64_t n, const float* table, const 
   const int n_levels = lv.n_levels;
   HashLevels L;
   if (int rc = fill_levels(L, lv); rc != NERF_OK) return rc;
-  const int64_t n_pad = (n + 127) / 128 * 128;
-  int64_t blocks = (n_pad + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  // occupancy throttle: the kernel uses no LDS; asking for 36 KiB per workgroup leaves 4 workgroups (1024 threads) per CU,
-  // i.e. about 1.3 level tables in flight on the chip instead of 2.6 -- the 2 MB tables of the hashed levels then stay in
-  // the 4 MB L2 of each XCD (91 -> 85 us on 200 k points; 3 or 2 workgroups per CU: 98 us)
-  const int lds_kb = options().hash_fwd_lds_kb;
-  int lds = (lds_kb < 0 ? 0 : (lds_kb > 64 ? 64 : lds_kb)) * 1024;
+  const int64_t n_pad = tile_rows(n);
+  int lds_floor = 0;                    // the histogram's LDS, where it is larger than the throttle's
   // bwd_workspace: this forward also counts the corners per (level, slice) into the binned backward's workspace (header and
   // counts are zeroed here), so that nerf_hash_encode_bwd_ws_store_precounted can skip its count pass
   unsigned* hist_count = nullptr;
@@ -1295,74 +1129,49 @@ static int hash_fwd_impl(const float* pts, int64_t n, const float* table, const 
     if (hipMemsetAsync(w.header, 0, 256 + sizeof(unsigned) * lb.bin0[n_levels], as_stream(stream)) != hipSuccess)
       return fail(NERF_ELAUNCH, "nerf_hash_encode_fwd_hist: memset failed");
     hist_count = w.count;
-    if (lds < (int)(max_slices * sizeof(unsigned))) lds = (int)(max_slices * sizeof(unsigned));
+    lds_floor = (int)(max_slices * sizeof(unsigned));
   }
-  const bool xcd = options().hash_xcd != 0;
   NERF_REQUIRE(x.ts.n >= 1 && (x.ts.n == 1 || (out_f32 == nullptr && idx_out == nullptr && x.bwd_workspace == nullptr && out_nat_bf16 != nullptr)),
                "nerf_hash_encode_fwd_nat_tables: several tables write operand images only");
-  const dim3 grid = level_chunk_grid(n_levels * x.ts.n, blocks, xcd);
-  const int n_chunks = xcd ? (int)blocks : 0;
-  if (table_f16 != nullptr)
-    hipLaunchKernelGGL(hash_fwd_kernel<half2_t>, grid, dim3(256), lds, as_stream(stream), pts, n, n_pad,
-                       static_cast<const half2_t*>(table_f16), L, out_f32, static_cast<__bf16*>(out_nat_bf16), idx_out, x.nat_f16,
-                       hist_count, lb, n_chunks, x.ts);
-  else
-    hipLaunchKernelGGL(hash_fwd_kernel<float2>, grid, dim3(256), lds, as_stream(stream), pts, n, n_pad,
-                       reinterpret_cast<const float2*>(table), L, out_f32, static_cast<__bf16*>(out_nat_bf16), idx_out, x.nat_f16,
-                       hist_count, lb, n_chunks, x.ts);
+  const GatherShape s = gather_shape(n_pad, n_levels * x.ts.n);
+  with_table(table, table_f16, [&](auto t) {
+    hipLaunchKernelGGL(hash_fwd_kernel<table_t<decltype(t)>>, s.grid, dim3(256), s.lds > lds_floor ? s.lds : lds_floor, as_stream(stream),
+                       pts, n, n_pad, t, L, out_f32, static_cast<__bf16*>(out_nat_bf16), idx_out, x.nat_f16, hist_count, lb, s.n_chunks,
+                       x.ts);
+  });
   return check_launch("nerf_hash_encode_fwd");
 }
 
 // The operand-image forward for a point count that lives on the device (common.h; called by render_instant.hip, which has checked
-// its arguments): hash_fwd_impl's launch shape -- 2048-workgroup cap, XCD-aware placement, LDS throttle -- sized by the capacity.
+// its arguments): the forward's launch shape (gather_shape), sized by the capacity.
 int nerf::hash_fwd_counted(const float* pts, const unsigned* count, int64_t capacity, const float* table_f32, const void* table_f16,
-                           int n_levels, const float* scale_host, const unsigned* res_host, const unsigned* size_host,
-                           const unsigned* offset_host, const unsigned* dense_host, float bound, void* out_nat, nerf_stream_t stream) {
-  NERF_REQUIRE(capacity > 0 && pts && count && out_nat && (table_f32 == nullptr) != (table_f16 == nullptr) && scale_host && res_host &&
-               size_host && offset_host && dense_host, "hash_fwd_counted: bad arguments");
+                           const LevelArgs& lv, void* out_nat, nerf_stream_t stream) {
+  NERF_REQUIRE(capacity > 0 && pts && count && out_nat && (table_f32 == nullptr) != (table_f16 == nullptr) && lv.scale && lv.res &&
+               lv.size && lv.offset && lv.dense, "hash_fwd_counted: bad arguments");
   HashLevels L;
-  if (int rc = fill_levels(L, LEVEL_ARGS); rc != NERF_OK) return rc;
-  const int64_t cap_pad = (capacity + 127) / 128 * 128;
-  int64_t blocks = (cap_pad + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  const int lds_kb = options().hash_fwd_lds_kb;                      // occupancy throttle, see hash_fwd_impl
-  const int lds = (lds_kb < 0 ? 0 : (lds_kb > 64 ? 64 : lds_kb)) * 1024;
-  const bool xcd = options().hash_xcd != 0;
-  const dim3 grid = level_chunk_grid(n_levels, blocks, xcd);
-  const int n_chunks = xcd ? (int)blocks : 0;
-  if (table_f16 != nullptr)
-    hipLaunchKernelGGL(hash_fwd_counted_kernel<half2_t>, grid, dim3(256), lds, as_stream(stream), pts, count, capacity,
-                       static_cast<const half2_t*>(table_f16), L, static_cast<__bf16*>(out_nat), n_chunks);
-  else
-    hipLaunchKernelGGL(hash_fwd_counted_kernel<float2>, grid, dim3(256), lds, as_stream(stream), pts, count, capacity,
-                       reinterpret_cast<const float2*>(table_f32), L, static_cast<__bf16*>(out_nat), n_chunks);
+  if (int rc = fill_levels(L, lv); rc != NERF_OK) return rc;
+  const GatherShape s = gather_shape(tile_rows(capacity), lv.n_levels);
+  with_table(table_f32, table_f16, [&](auto t) {
+    hipLaunchKernelGGL(hash_fwd_counted_kernel<table_t<decltype(t)>>, s.grid, dim3(256), s.lds, as_stream(stream), pts, count, capacity, t, L,
+                       static_cast<__bf16*>(out_nat), s.n_chunks);
+  });
   return check_launch("nerf_instant_render_rays_fwd (hash)");
 }
 
 // The operand-image forward of a slab of occupancy-grid cells (common.h; called by grid.hip's nerf_instant_grid_update, which has
-// checked its arguments): hash_fwd_impl's launch shape, sized by the slab.
+// checked its arguments): the forward's launch shape, sized by the slab.
 int nerf::hash_fwd_lattice(int64_t cell0, int64_t n_cells, int resolution, float grid_bound, const float* table_f32, const void* table_f16,
-                           int n_levels, const float* scale_host, const unsigned* res_host, const unsigned* size_host,
-                           const unsigned* offset_host, const unsigned* dense_host, float bound, void* out_nat, nerf_stream_t stream) {
-  NERF_REQUIRE(cell0 >= 0 && n_cells > 0 && resolution >= 2 && out_nat && (table_f32 == nullptr) != (table_f16 == nullptr) && scale_host &&
-               res_host && size_host && offset_host && dense_host, "hash_fwd_lattice: bad arguments");
+                           const LevelArgs& lv, void* out_nat, nerf_stream_t stream) {
+  NERF_REQUIRE(cell0 >= 0 && n_cells > 0 && resolution >= 2 && out_nat && (table_f32 == nullptr) != (table_f16 == nullptr) && lv.scale &&
+               lv.res && lv.size && lv.offset && lv.dense, "hash_fwd_lattice: bad arguments");
   HashLevels L;
-  if (int rc = fill_levels(L, LEVEL_ARGS); rc != NERF_OK) return rc;
-  const int64_t n_pad = (n_cells + 127) / 128 * 128;
-  int64_t blocks = (n_pad + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  const int lds_kb = options().hash_fwd_lds_kb;                      // occupancy throttle, see hash_fwd_impl
-  const int lds = (lds_kb < 0 ? 0 : (lds_kb > 64 ? 64 : lds_kb)) * 1024;
-  const bool xcd = options().hash_xcd != 0;
-  const dim3 grid = level_chunk_grid(n_levels, blocks, xcd);
-  const int n_chunks = xcd ? (int)blocks : 0;
+  if (int rc = fill_levels(L, lv); rc != NERF_OK) return rc;
+  const GatherShape s = gather_shape(tile_rows(n_cells), lv.n_levels);
   const float step = lattice_step(grid_bound, resolution);
-  if (table_f16 != nullptr)
-    hipLaunchKernelGGL(hash_fwd_lattice_kernel<half2_t>, grid, dim3(256), lds, as_stream(stream), cell0, n_cells, resolution, grid_bound, step,
-                       static_cast<const half2_t*>(table_f16), L, static_cast<__bf16*>(out_nat), n_chunks);
-  else
-    hipLaunchKernelGGL(hash_fwd_lattice_kernel<float2>, grid, dim3(256), lds, as_stream(stream), cell0, n_cells, resolution, grid_bound, step,
-                       reinterpret_cast<const float2*>(table_f32), L, static_cast<__bf16*>(out_nat), n_chunks);
+  with_table(table_f32, table_f16, [&](auto t) {
+    hipLaunchKernelGGL(hash_fwd_lattice_kernel<table_t<decltype(t)>>, s.grid, dim3(256), s.lds, as_stream(stream), cell0, n_cells, resolution,
+                       grid_bound, step, t, L, static_cast<__bf16*>(out_nat), s.n_chunks);
+  });
   return check_launch("nerf_instant_grid_update (hash)");
 }
 
@@ -1675,28 +1484,21 @@ static int hash_bwd_input_impl(const float* pts, int64_t n, const float* table, 
   NERF_REQUIRE(pts && (table || table_f16) && (d_feat || grad_lm) && d_pts && lv.scale && lv.res && lv.size && lv.offset && lv.dense, "nerf_hash_encode_bwd_input: NULL pointer");
   HashLevels L;
   if (int rc = fill_levels(L, lv); rc != NERF_OK) return rc;
-  int64_t blocks = (n + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
+  const GatherShape s = gather_shape(n, lv.n_levels);        // its LDS throttle is the forwards': these launches ask for no LDS
   NERF_REQUIRE(!(options().deterministic && grad_lm != nullptr), "nerf_hash_encode_bwd_input_lm: not with option \"deterministic\"");
   if (options().deterministic) {          // levels summed in order per point: no float atomics
-    if (table_f16 != nullptr)
-      hipLaunchKernelGGL(hash_bwd_input_ordered_kernel<half2_t>, dim3((int)blocks), dim3(256), 0, as_stream(stream), pts, n,
-                         static_cast<const half2_t*>(table_f16), L, d_feat, d_pts, accumulate);
-    else
-      hipLaunchKernelGGL(hash_bwd_input_ordered_kernel<float2>, dim3((int)blocks), dim3(256), 0, as_stream(stream), pts, n,
-                         reinterpret_cast<const float2*>(table), L, d_feat, d_pts, accumulate);
+    with_table(table, table_f16, [&](auto t) {
+      hipLaunchKernelGGL(hash_bwd_input_ordered_kernel<table_t<decltype(t)>>, dim3((int)s.blocks), dim3(256), 0, as_stream(stream), pts, n, t,
+                         L, d_feat, d_pts, accumulate);
+    });
     return check_launch("nerf_hash_encode_bwd_input (ordered)");
   }
   if (!accumulate && hipMemsetAsync(d_pts, 0, sizeof(float) * 3 * (size_t)n, as_stream(stream)) != hipSuccess)
     return fail(NERF_ELAUNCH, "nerf_hash_encode_bwd_input: memset failed");
-  const bool xcd = options().hash_xcd != 0;
-  const dim3 grid = level_chunk_grid(lv.n_levels, blocks, xcd);
-  if (table_f16 != nullptr)
-    hipLaunchKernelGGL(hash_bwd_input_kernel<half2_t>, grid, dim3(256), 0, as_stream(stream), pts, n,
-                       static_cast<const half2_t*>(table_f16), L, d_feat, d_pts, xcd ? (int)blocks : 0, grad_lm);
-  else
-    hipLaunchKernelGGL(hash_bwd_input_kernel<float2>, grid, dim3(256), 0, as_stream(stream), pts, n,
-                       reinterpret_cast<const float2*>(table), L, d_feat, d_pts, xcd ? (int)blocks : 0, grad_lm);
+  with_table(table, table_f16, [&](auto t) {
+    hipLaunchKernelGGL(hash_bwd_input_kernel<table_t<decltype(t)>>, s.grid, dim3(256), 0, as_stream(stream), pts, n, t, L, d_feat, d_pts,
+                       s.n_chunks, grad_lm);
+  });
   return check_launch("nerf_hash_encode_bwd_input");
 }
 

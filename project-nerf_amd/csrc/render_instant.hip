@@ -23,12 +23,12 @@ extern "C" int nerf_instant_render_rays_fwd(const void* imlp_packed, const float
   NERF_REQUIRE((table_f32 == nullptr) != (table_f16 == nullptr), "%s: exactly one of table_f32 / table_f16", kWhat);
   NERF_REQUIRE(hash_bound > 0.0f, "%s: hash_bound must be positive", kWhat);
   NERF_REQUIRE(imlp_packed && scale_host && res_host && size_host && offset_host && dense_host, "%s: NULL pointer", kWhat);
+  const nerf::LevelArgs levels{n_levels, scale_host, res_host, size_host, offset_host, dense_host, hash_bound};
   return nerf::counted_render(
       kWhat, kImageRowBytes, binary_grid, grid_resolution, grid_bound, rays_o, rays_d, n_rays, n_samples, near_plane, far_plane, bg, bg_rows,
       chunk_rays, workspace, out_rgb, out_depth, out_acc, stream,
       [=](const float* pts, const float* dirs, const unsigned* count, int64_t capacity, void* image, float* rgb, float* sigma) {
-        const int rc = nerf::hash_fwd_counted(pts, count, capacity, table_f32, table_f16, n_levels, scale_host, res_host, size_host, offset_host,
-                                              dense_host, hash_bound, image, stream);
+        const int rc = nerf::hash_fwd_counted(pts, count, capacity, table_f32, table_f16, levels, image, stream);
         if (rc != NERF_OK) return rc;
         return nerf::imlp_fwd_counted(imlp_packed, image, dirs, count, capacity, rgb, sigma, stream);
       });
