@@ -49,7 +49,8 @@ extern "C" {
 /* 10: the vanilla field's evaluation through an occupancy grid as one launch chain, nerf_render_rays_grid_*, is new. */
 /* 11: the data side of a training step through the occupancy grid in one launch, nerf_train_batch_compact*, is new. */
 /* 12: the Instant-NGP occupancy-grid refresh as one density-only launch chain, nerf_instant_grid_update*, is new. */
-#define NERF_ABI_VERSION 12
+/* 13: the Part 4 occupancy-grid refresh as one density-only launch chain, nerf_p4_grid_update*, is new. */
+#define NERF_ABI_VERSION 13
 
 typedef void* nerf_stream_t;
 
@@ -272,6 +273,47 @@ int nerf_instant_grid_update(const void* packed, const float* table_f32, const v
                              float* grid, uint8_t* binary_grid, float decay, int dynamic, float threshold,
                              unsigned long long* active_count, int64_t slab_cells, void* workspace,
                              nerf_stream_t stream);
+
+/* ---- a12 + f3: refresh of the Part 4 dual-hash field's occupancy grid as one density-only launch chain ----
+ * replaces DensityGrid.update in its dynamic form (src/renderer.py:62-86, 118-132: density at the time anchors
+ * 0, 0.5, 1, their maximum, the running maximum against the decayed history, threshold and count) around
+ * NeuralField('part4').forward (src/core.py:282-352).  On the caller's stream: clear *active_count, then per slab of
+ * `slab_cells` cells and per anchor k: hash gather of deformation grid k ALONE at the lattice nodes (points from the
+ * cell index; at an anchor the tri-grid weights are a unit vector) into an fp16 operand image -> deformation chain at
+ * the scalar t (time modulation once per wave, x_c alone is stored) -> nerf_hash_encode_fwd_nat of the canonical
+ * grid at x_c -> canonical sigma-net (S1, S2 of nerf_p4_canon_fwd only) whose epilogue folds sigma into grid /
+ * binary_grid.  The first anchor of a slab folds with `decay`, the other two with decay 1; only the last anchor's pass
+ * counts.  12 * ceil(n_cells / slab_cells) + 1 enqueues, no lattice tensor, no time vector, no rgb, no view
+ * directions, no allocation, no host read: the call can be captured in a hipGraph as a linear chain.
+ * After the call grid, binary_grid and *active_count hold the same BITS as nerf_grid_lattice -> [the three
+ * deformation gathers -> nerf_p4_deform_fwd -> nerf_hash_encode_fwd_nat -> nerf_p4_canon_fwd](train = 0, zero
+ * directions) at t = 0, 0.5, 1 -> element-wise maximum -> nerf_grid_update(dynamic = 1) leave, for either table
+ * type and any slab size, PROVIDED every table entry is finite (the chain reads one deformation grid where the loop
+ * multiplies the other two by a weight of exactly 0).
+ *   packed: nerf_p4_pack's image; params_f32: the flat parameters (displacement_scale is read from them).
+ *   tables_f32 / tables_f16 (exactly one): HOST array of four device pointers [start, mid, end, canonical], all fp32
+ *   [entries,2] or all fp16 copies.  deform_levels (12) and canon_levels (16) with their host level arrays, hash_bound:
+ *   as nerf_hash_encode_fwd_nat, for the three deformation grids and the canonical grid.
+ *   Cell c is node (c / res^2, (c / res) % res, c % res) of nerf_grid_lattice's lattice for `resolution` (2..32768)
+ *   and grid_bound; n_cells must equal resolution^3.  There is no point-buffer source.
+ *   grid [n_cells] in/out: max(max(max(grid * decay, s0), s1), s2); binary_grid [n_cells] bytes = grid > threshold;
+ *   *active_count (device u64) = number of set cells.
+ *   slab_cells: a positive multiple of 128 with slab_cells * 32 < 2^31.
+ *   workspace: nerf_p4_grid_update_workspace_bytes(slab_cells) bytes, 256-byte aligned, contents irrelevant.  With
+ *   rows = roundup(slab_cells, 128): [deformation operand image rows x 32 fp16 | x_c rows x 3 fp32 | canonical operand
+ *   image rows x 32 fp16] = (64 + 12 + 64) bytes per row, each piece rounded up to 256 bytes (140 * rows in all:
+ *   36 700 160 bytes for 2^18 cells), reused by every (slab, anchor) pass (stream order serialises them).  The query
+ *   returns 0 for slab_cells <= 0. */
+size_t nerf_p4_grid_update_workspace_bytes(int64_t slab_cells);
+int nerf_p4_grid_update(const void* packed, const float* params_f32, const float* const* tables_f32,
+                        const void* const* tables_f16, int deform_levels, const float* d_scale_host,
+                        const unsigned* d_res_host, const unsigned* d_size_host, const unsigned* d_offset_host,
+                        const unsigned* d_dense_host, int canon_levels, const float* c_scale_host,
+                        const unsigned* c_res_host, const unsigned* c_size_host, const unsigned* c_offset_host,
+                        const unsigned* c_dense_host, float hash_bound, int64_t n_cells, int resolution,
+                        float grid_bound, float* grid, uint8_t* binary_grid, float decay, float threshold,
+                        unsigned long long* active_count, int64_t slab_cells, void* workspace,
+                        nerf_stream_t stream);
 
 /* ---- a5: Fourier features ---------------------------------------------------
  * replaces FourierRepresentation.forward (src/embeddings.py:22-32).

@@ -82,9 +82,19 @@ int imlp_fwd_counted(const void* packed, const void* hash_nat, const float* dirs
 // imlp.hip: the sigma-net alone on that image, folded into grid / binary_grid (already offset to the slab's first cell) with
 // nerf_grid_update's arithmetic, active cells added to *active_count (cleared by the caller).
 int hash_fwd_lattice(int64_t cell0, int64_t n_cells, int resolution, float grid_bound, const float* table_f32, const void* table_f16,
-                     const LevelArgs& levels, void* out_nat, nerf_stream_t stream);
+                     const LevelArgs& levels, void* out_nat, int nat_f16, nerf_stream_t stream);      // nat_f16: fp16 image instead of bf16
 int imlp_sigma_grid(const void* packed, const void* hash_nat, int64_t n_cells, float* grid, uint8_t* binary_grid, float decay, int dynamic,
                     float threshold, unsigned long long* active_count, nerf_stream_t stream);
+// The two chain launches of nerf_p4_grid_update (grid.hip) per (slab of occupancy-grid cells, time anchor t); p4mlp.hip.
+// p4_deform_lattice: the deformation chain at time t on ONE deformation grid's fp16 operand image [roundup(n_cells, 128), 32] of cells
+// cell0 .. cell0 + n_cells - 1 (hash_fwd_lattice, nat_f16 = 1), the points formed from the cell index: x_c [n_cells,3] fp32 and
+// nothing else.  p4_canon_sigma_grid: the canonical sigma-net alone on [hash image of x_c | time code of t], folded into grid /
+// binary_grid (already offset to the slab's first cell) with nerf_grid_update's running maximum; active cells are added to
+// *active_count where it is non-NULL (the caller clears it and passes it with the last anchor only).
+int p4_deform_lattice(const void* packed, const float* params_f32, const void* feat_nat, float t, int64_t cell0, int64_t n_cells, int resolution,
+                      float grid_bound, float* x_canonical, nerf_stream_t stream);
+int p4_canon_sigma_grid(const void* packed, const void* hash_nat, float t, int64_t n_cells, float* grid, uint8_t* binary_grid, float decay,
+                        float threshold, unsigned long long* active_count, nerf_stream_t stream);
 // mlp_fwd.hip: the 8x256 inference chain in point mode (64 samples per wave) on the first *count rows of pts / dirs, for
 // render_grid.hip's launch chain
 int mlp_fwd_counted(const void* packed, const float* pts, const float* dirs, const unsigned* count, int64_t capacity, float* rgb,

@@ -104,11 +104,89 @@ extern "C" int nerf_instant_grid_update(const void* packed, const float* table_f
       if (rc != NERF_OK) return rc;
     } else {
       rc = hash_fwd_lattice(c0, n, resolution, grid_bound, table_f32, table_f16,
-                            LevelArgs{n_levels, scale_host, res_host, size_host, offset_host, dense_host, hash_bound}, workspace, stream);
+                            LevelArgs{n_levels, scale_host, res_host, size_host, offset_host, dense_host, hash_bound}, workspace, 0, stream);
       if (rc != NERF_OK) return rc;
     }
     rc = imlp_sigma_grid(packed, workspace, n, grid + c0, binary_grid + c0, decay, dynamic, threshold, active_count, stream);
     if (rc != NERF_OK) return rc;
+  }
+  return NERF_OK;
+}
+
+// ---- the Part 4 dual-hash field's refresh as one launch chain (reference DensityGrid.update in its dynamic form around
+// NeuralField('part4'), src/renderer.py:62-86, 118-132, src/core.py:282-352) ----
+// clear the count -> per slab of `slab_cells` cells, per time anchor k (t = 0, 0.5, 1): gather of deformation grid k ALONE at the
+// lattice nodes (the triangle weights of an anchor are a unit vector) -> density-only deformation chain (x_c) -> canonical gather at
+// x_c -> canonical sigma-net chain with the running maximum in its epilogue.  The first anchor of a slab folds against the decayed
+// history, max(grid * decay, s0); the other two run with decay 1, so the cell ends as max(max(max(g d, s0), s1), s2) -- the
+// reference's max(g d, max(s0, s1, s2)) (a maximum of non-NaN values does not depend on its grouping).  Only the last anchor's
+// pass is given the count pointer (instant_sigma skips a NULL one): binary_grid and the count are those of the finished cell.
+// The (slab, anchor) passes share ONE workspace; stream order serialises them.  12 * ceil(n_cells / slab_cells) + 1 enqueues.
+namespace nerf {
+struct P4GridWorkspace { size_t deform_nat, xc, canon_nat, total; };
+static P4GridWorkspace p4_grid_workspace(int64_t slab_cells) {
+  const size_t rows = ((size_t)slab_cells + 127) / 128 * 128;
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  P4GridWorkspace w{};
+  w.deform_nat = 0;
+  w.xc = w.deform_nat + up(rows * 32 * 2);
+  w.canon_nat = w.xc + up(rows * 3 * 4);
+  w.total = w.canon_nat + up(rows * 32 * 2);
+  return w;
+}
+}  // namespace nerf
+
+extern "C" size_t nerf_p4_grid_update_workspace_bytes(int64_t slab_cells) {
+  return slab_cells > 0 ? p4_grid_workspace(slab_cells).total : 0;
+}
+
+extern "C" int nerf_p4_grid_update(const void* packed, const float* params_f32, const float* const* tables_f32, const void* const* tables_f16,
+                                   int deform_levels, const float* d_scale_host, const unsigned* d_res_host, const unsigned* d_size_host,
+                                   const unsigned* d_offset_host, const unsigned* d_dense_host, int canon_levels, const float* c_scale_host,
+                                   const unsigned* c_res_host, const unsigned* c_size_host, const unsigned* c_offset_host,
+                                   const unsigned* c_dense_host, float hash_bound, int64_t n_cells, int resolution, float grid_bound,
+                                   float* grid, uint8_t* binary_grid, float decay, float threshold, unsigned long long* active_count,
+                                   int64_t slab_cells, void* workspace, nerf_stream_t stream) {
+  NERF_REQUIRE((tables_f32 == nullptr) != (tables_f16 == nullptr),
+               "nerf_p4_grid_update: exactly one of tables_f32 / tables_f16 (the four tables are all fp32 or all fp16)");
+  for (int k = 0; k < 4; ++k)
+    NERF_REQUIRE((tables_f32 != nullptr ? (const void*)tables_f32[k] : tables_f16[k]) != nullptr, "nerf_p4_grid_update: table %d is NULL", k);
+  NERF_REQUIRE(deform_levels == 12 && canon_levels == 16,
+               "nerf_p4_grid_update: deform_levels=%d, canon_levels=%d (the default-shape chains read 12 and 16 levels x 2 features)",
+               deform_levels, canon_levels);
+  NERF_REQUIRE(resolution >= 2 && resolution <= 32768, "nerf_p4_grid_update: resolution=%d (2..32768)", resolution);
+  NERF_REQUIRE(n_cells == (int64_t)resolution * resolution * resolution, "nerf_p4_grid_update: n_cells=%lld is not resolution^3 (%d)",
+               (long long)n_cells, resolution);
+  NERF_REQUIRE(slab_cells > 0 && slab_cells % 128 == 0, "nerf_p4_grid_update: slab_cells=%lld (a positive multiple of 128)", (long long)slab_cells);
+  NERF_REQUIRE(slab_cells * 32 < ((int64_t)1 << 31), "nerf_p4_grid_update: slab too large (slab_cells * 32 must stay below 2^31)");
+  NERF_REQUIRE(workspace != nullptr, "nerf_p4_grid_update: workspace is NULL");
+  NERF_REQUIRE(((uintptr_t)workspace & 255) == 0, "nerf_p4_grid_update: workspace must be 256-byte aligned");
+  NERF_REQUIRE(hash_bound > 0.0f && grid_bound > 0.0f, "nerf_p4_grid_update: hash_bound and grid_bound must be positive");
+  NERF_REQUIRE(packed && params_f32 && grid && binary_grid && active_count, "nerf_p4_grid_update: NULL pointer");
+  NERF_REQUIRE(d_scale_host && d_res_host && d_size_host && d_offset_host && d_dense_host && c_scale_host && c_res_host && c_size_host &&
+               c_offset_host && c_dense_host, "nerf_p4_grid_update: NULL level table");
+  const LevelArgs lv_d{deform_levels, d_scale_host, d_res_host, d_size_host, d_offset_host, d_dense_host, hash_bound};
+  const P4GridWorkspace w = p4_grid_workspace(slab_cells);
+  char* ws = static_cast<char*>(workspace);
+  float* xc = reinterpret_cast<float*>(ws + w.xc);
+  if (hipMemsetAsync(active_count, 0, sizeof(unsigned long long), as_stream(stream)) != hipSuccess)
+    return fail(NERF_ELAUNCH, "nerf_p4_grid_update: memset failed");
+  const float anchors[3] = {0.0f, 0.5f, 1.0f};
+  for (int64_t c0 = 0; c0 < n_cells; c0 += slab_cells) {
+    const int64_t n = n_cells - c0 < slab_cells ? n_cells - c0 : slab_cells;
+    for (int k = 0; k < 3; ++k) {
+      int rc = hash_fwd_lattice(c0, n, resolution, grid_bound, tables_f32 ? tables_f32[k] : nullptr, tables_f16 ? tables_f16[k] : nullptr, lv_d,
+                                ws + w.deform_nat, 1, stream);
+      if (rc != NERF_OK) return rc;
+      rc = p4_deform_lattice(packed, params_f32, ws + w.deform_nat, anchors[k], c0, n, resolution, grid_bound, xc, stream);
+      if (rc != NERF_OK) return rc;
+      rc = nerf_hash_encode_fwd_nat(xc, n, tables_f32 ? tables_f32[3] : nullptr, tables_f16 ? tables_f16[3] : nullptr, canon_levels, c_scale_host,
+                                    c_res_host, c_size_host, c_offset_host, c_dense_host, hash_bound, ws + w.canon_nat, 1, stream);
+      if (rc != NERF_OK) return rc;
+      rc = p4_canon_sigma_grid(packed, ws + w.canon_nat, anchors[k], n, grid + c0, binary_grid + c0, k == 0 ? decay : 1.0f, threshold,
+                               k == 2 ? active_count : nullptr, stream);
+      if (rc != NERF_OK) return rc;
+    }
   }
   return NERF_OK;
 }

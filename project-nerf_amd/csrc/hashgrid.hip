@@ -79,11 +79,12 @@ hash_fwd_kernel(const float* __restrict__ pts, int64_t n, int64_t n_pad, const T
   }
 }
 
-// hash_fwd_kernel's bf16 operand image and nothing else (no fp32 rows, corner indices, histogram or table set) of n (> 0) points
-// that point_of(row, x, y, z) supplies; the rows up to the 128-row tile are pad rows.  The body of the two kernels below.
+// hash_fwd_kernel's operand image (bf16, or fp16 where nat_f16) and nothing else (no fp32 rows, corner indices, histogram or table
+// set) of n (> 0) points that point_of(row, x, y, z) supplies; the rows up to the 128-row tile are pad rows.  The body of the two
+// kernels below.
 template <class TableT, class PointOf>
 __device__ __forceinline__ void operand_image_of(int64_t n, const TableT* __restrict__ table, const HashLevels& L,
-                                                 __bf16* __restrict__ out_nat, int n_chunks, PointOf point_of) {
+                                                 __bf16* __restrict__ out_nat, int n_chunks, bool nat_f16, PointOf point_of) {
   const int64_t n_pad = (n + 127) / 128 * 128;
   const LevelChunk lc = level_chunk(L.n_levels, n_chunks);
   if (lc.lvl >= L.n_levels) return;
@@ -91,7 +92,7 @@ __device__ __forceinline__ void operand_image_of(int64_t n, const TableT* __rest
     float x, y, z;
     point_of(pad_row(p, n), x, y, z);
     const float2 f = cell_features(table, corners_of(L, lc.lvl, x, y, z));
-    store_operand(out_nat, p, lc.lvl, L.n_levels, f.x, f.y, false);
+    store_operand(out_nat, p, lc.lvl, L.n_levels, f.x, f.y, nat_f16);
   }
 }
 
@@ -104,18 +105,19 @@ hash_fwd_counted_kernel(const float* __restrict__ pts, const unsigned* __restric
                         const TableT* __restrict__ table, HashLevels L, __bf16* __restrict__ out_nat, int n_chunks) {
   const int64_t n = (int64_t)*count;
   if (n == 0) return;
-  operand_image_of(n < capacity ? n : capacity, table, L, out_nat, n_chunks, [pts](int64_t ps, float& x, float& y, float& z) {
+  operand_image_of(n < capacity ? n : capacity, table, L, out_nat, n_chunks, false, [pts](int64_t ps, float& x, float& y, float& z) {
     x = pts[ps * 3 + 0]; y = pts[ps * 3 + 1]; z = pts[ps * 3 + 2];
   });
 }
 
 // Points that are never written out: point p of the slab is cell cell0 + p of the occupancy grid's 'ij' lattice
-// (nerf_instant_grid_update; lattice.h gives the node coordinates nerf_grid_lattice would store).  n (> 0) cells, known to the host.
+// (nerf_instant_grid_update, nerf_p4_grid_update; lattice.h gives the node coordinates nerf_grid_lattice would store).  n (> 0)
+// cells, known to the host.  nat_f16: the image in fp16 (the Part 4 forward chains' operands) instead of bf16.
 template <class TableT>
 __global__ void __launch_bounds__(256)
 hash_fwd_lattice_kernel(int64_t cell0, int64_t n, int res, float grid_bound, float step, const TableT* __restrict__ table,
-                        HashLevels L, __bf16* __restrict__ out_nat, int n_chunks) {
-  operand_image_of(n, table, L, out_nat, n_chunks, [=](int64_t ps, float& x, float& y, float& z) {
+                        HashLevels L, __bf16* __restrict__ out_nat, int n_chunks, int nat_f16) {
+  operand_image_of(n, table, L, out_nat, n_chunks, nat_f16 != 0, [=](int64_t ps, float& x, float& y, float& z) {
     int ix, iy, iz;
     lattice_cell(cell0 + ps, res, ix, iy, iz);
     x = lattice_node(ix, res, grid_bound, step); y = lattice_node(iy, res, grid_bound, step); z = lattice_node(iz, res, grid_bound, step);
@@ -1158,10 +1160,10 @@ int nerf::hash_fwd_counted(const float* pts, const unsigned* count, int64_t capa
   return check_launch("nerf_instant_render_rays_fwd (hash)");
 }
 
-// The operand-image forward of a slab of occupancy-grid cells (common.h; called by grid.hip's nerf_instant_grid_update, which has
-// checked its arguments): the forward's launch shape, sized by the slab.
+// The operand-image forward of a slab of occupancy-grid cells (common.h; called by grid.hip's nerf_instant_grid_update and
+// nerf_p4_grid_update, which have checked their arguments): the forward's launch shape, sized by the slab.
 int nerf::hash_fwd_lattice(int64_t cell0, int64_t n_cells, int resolution, float grid_bound, const float* table_f32, const void* table_f16,
-                           const LevelArgs& lv, void* out_nat, nerf_stream_t stream) {
+                           const LevelArgs& lv, void* out_nat, int nat_f16, nerf_stream_t stream) {
   NERF_REQUIRE(cell0 >= 0 && n_cells > 0 && resolution >= 2 && out_nat && (table_f32 == nullptr) != (table_f16 == nullptr) && lv.scale &&
                lv.res && lv.size && lv.offset && lv.dense, "hash_fwd_lattice: bad arguments");
   HashLevels L;
@@ -1170,9 +1172,9 @@ int nerf::hash_fwd_lattice(int64_t cell0, int64_t n_cells, int resolution, float
   const float step = lattice_step(grid_bound, resolution);
   with_table(table_f32, table_f16, [&](auto t) {
     hipLaunchKernelGGL(hash_fwd_lattice_kernel<table_t<decltype(t)>>, s.grid, dim3(256), s.lds, as_stream(stream), cell0, n_cells, resolution,
-                       grid_bound, step, t, L, static_cast<__bf16*>(out_nat), s.n_chunks);
+                       grid_bound, step, t, L, static_cast<__bf16*>(out_nat), s.n_chunks, nat_f16);
   });
-  return check_launch("nerf_instant_grid_update (hash)");
+  return check_launch("nerf_instant_grid_update / nerf_p4_grid_update (lattice hash)");
 }
 
 extern "C" int nerf_hash_encode_fwd(const float* pts, int64_t n, const float* table, int n_levels,

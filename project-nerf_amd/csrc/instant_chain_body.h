@@ -64,7 +64,7 @@ __device__ __forceinline__ void instant_forward(const A a, char* smem, int tid, 
 // (grid.hip; reference src/renderer.py:118-132) on the lane that owns acc[0] of a live row; every thread counts its active cells
 // over its whole tile loop: one reduction and one 64-bit atomic per workgroup at the kernel's end, none per tile.
 // P adds: P::sigma_operands(a, wt, col, half, sin) forms the sigma-net's input alone.
-// A: packed, n, n_pad, grid, binary, decay, dynamic, threshold, count (+ what P::sigma_operands reads).
+// A: packed, n, n_pad, grid, binary, decay, dynamic, threshold, count (NULL: nothing is counted) (+ what P::sigma_operands reads).
 template <class P, class A>
 __device__ __forceinline__ void instant_sigma(const A a, char* smem, int tid, int lane, int wave, int col, int half) {
   using V = typename P::V;
@@ -106,7 +106,7 @@ __device__ __forceinline__ void instant_sigma(const A a, char* smem, int tid, in
     unsigned long long total = 0;
 #pragma unroll
     for (int w = 0; w < kInstantThreads / 64; ++w) total += wave_active[w];
-    if (total) atomicAdd(a.count, total);
+    if (total && a.count != nullptr) atomicAdd(a.count, total);      // NULL: a pass whose cells a later pass counts (nerf_p4_grid_update)
   }
 }
 

@@ -27,6 +27,7 @@
 //   C1 [64,48] C2 [64,64] C3 [16,64]                        decoder.color_net.params
 //   scale [1]                                               deform_decoder.displacement_scale
 #include "instant_chain_body.h"
+#include "lattice.h"
 #include "mlp_wgrad.h"
 
 namespace nerf {
@@ -260,6 +261,88 @@ __global__ void __launch_bounds__(kThreads) deform_fwd_kernel(const DeformArgs a
   }
 }
 
+// The deformation chain of the occupancy-grid refresh (nerf_p4_grid_update): deform_fwd_kernel<false> for the cells of a lattice slab
+// at ONE time stamp t, which is a time anchor (0, 0.5 or 1), storing x_c alone.  What that fixes, and why the bits stay the loop's:
+//   * t is uniform, so the time code and the whole T1 -> T2 block are the same in every MFMA column of every tile (a column's
+//     output depends on its own column's inputs only): computed ONCE per wave, before the tile loop, with the A fragments and the
+//     T2 bias read from the packed image in global memory.  Only D1, D2, D3 (24 of the forward's 36 fragments) are resident in LDS.
+//   * at an anchor triangle_weights gives exactly (1,0,0), (0,1,0) or (0,0,1) (the normaliser 1e-8f + 1 is 1.0f), so the blend
+//     w0 f0 + w1 f1 + w2 f2 of FINITE features is the anchor grid's feature in value: the kernel reads that ONE image.  The loop's
+//     sum may carry the other sign on an exact zero (0 * f of either sign is added); a zero of either sign in a B operand adds a
+//     zero product to D1's accumulators, which start at +0 and therefore never hold -0 (a sum of zeros is -0 only if every term is),
+//     so hd1 and everything behind it are unchanged.  Non-finite table entries would break this (0 * inf); they are not supported.
+//   * x is lattice_node of the cell index (the value nerf_grid_lattice stores), x_c = fma(dx_raw, scale, x): the contraction the
+//     compiler applies to deform_fwd_kernel's `x + acc * scale`, written out so that it does not depend on what else is stored.
+struct DeformLatticeArgs {
+  const char* packed;
+  const __bf16* feat;      // nat image [n_pad,32] of the anchor's deformation grid at the slab's cells, FP16 (features 0..23 valid)
+  const float* params;     // flat fp32 parameters (displacement_scale is read from here)
+  float t;                 // the anchor
+  int64_t cell0, n, n_pad; // first cell of the slab, its cells, rounded up to whole tiles
+  int res;
+  float bound, step;       // the lattice (lattice.h)
+  float* xc;               // [n,3]
+};
+constexpr int kDeformLattice0 = step_of(D1).frag0, kDeformLatticeN = kDeformFwd0 + kDeformFwdN - kDeformLattice0;
+static_assert(step_of(T1).frag0 == kDeformFwd0 && kDeformLattice0 == 12 && kDeformLatticeN == 24, "T1, T2 lead the forward fragment stream");
+
+__global__ void __launch_bounds__(kThreads) deform_lattice_kernel(const DeformLatticeArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
+  const char* wbase = resident_weights<kThreads>(smem, a.packed, kDeformLattice0, kDeformLatticeN, tid, lane);
+  // ---- time modulation (decoders.py:368-371), once per wave: fragments and bias straight from the packed image ----
+  f16x8 tm[4];
+  {
+    const char* gbase = a.packed + lane * 16;
+    const float* bias = reinterpret_cast<const float*>(a.packed + kPackBiasOff);
+    f16x8 tc[2], ht1[4];
+    bf16x8 tc_b[2];
+    float v[2][8];
+    time_values<2, true>(a.t, half, v);
+    cast_values<2>(v, tc, tc_b);
+    uint32_t mw = 0;
+    run_step<step_of, T1, 2>(gbase, tc, nullptr, Mfma16{}, relu_epilogue<false>(ht1, (__bf16*)nullptr, mw, 0, col, half));
+    run_step<step_of, T2, 4>(gbase, ht1, nullptr, Mfma16{}, [&](auto mc, f32x16 acc) {
+      constexpr int m = decltype(mc)::value;
+      const f32x16 b = bias_tile(bias, 32 * m, half);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = 1.0f / (1.0f + __expf(-(acc[r] + b[r])));
+      acc_to_operand16(acc, tm[2 * m], tm[2 * m + 1]);
+    });
+  }
+  __syncthreads();
+  const float scale = a.params[kScale];
+  const int64_t n_tiles = a.n_pad / kTile;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const int64_t wt = tile * 4 + wave, n = wt * 32 + col;
+    const bool live = n < a.n;
+    // ---- the anchor grid's features (core.py:313-336 with unit weights) ----
+    f16x8 df[2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const f16x8 f = load_nat<f16x8>(a.feat, wt, 2, ks, col, half);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) df[ks][j] = 16 * ks + 8 * half + j < kHashDeform ? f[j] : (_Float16)0.0f;   // features 24..31 are unwritten
+    }
+    // ---- displacement decoder (decoders.py:313-316) ----
+    uint32_t mw[2] = {0, 0};
+    f16x8 hd1[4], hd2[4];
+    {
+      f16x8 cat[6] = {tm[0], tm[1], tm[2], tm[3], df[0], df[1]};
+      run_step<step_of, D1, 6>(wbase, cat, nullptr, Mfma16{}, relu_epilogue<false>(hd1, (__bf16*)nullptr, mw[0], wt, col, half));
+    }
+    run_step<step_of, D2, 4>(wbase, hd1, nullptr, Mfma16{}, relu_epilogue<false>(hd2, (__bf16*)nullptr, mw[1], wt, col, half));
+    run_step<step_of, D3, 4>(wbase, hd2, nullptr, Mfma16{}, [&](auto, f32x16 acc) {
+      if (live && half == 0) {
+        int i[3];
+        lattice_cell(a.cell0 + n, a.res, i[0], i[1], i[2]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a.xc[n * 3 + c] = __builtin_fmaf(acc[c], scale, lattice_node(i[c], a.res, a.bound, a.step));
+      }
+    });
+  }
+}
+
 __global__ void __launch_bounds__(kThreads) deform_bwd_kernel(const DeformArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
@@ -373,6 +456,19 @@ struct CanonPolicy {
   static constexpr bool kZeroGrads = false, kFence = false;
   using V = f16x8;
   using Mfma = Mfma16;
+  // the sigma-net's input alone at ONE time stamp (instant_sigma): the two k-steps of the hash operand image and the time code of
+  // the scalar a.t -- what operands<false> forms for sin[0..3]
+  template <class A>
+  static __device__ __forceinline__ void sigma_operands(const A& a, int64_t wt, int col, int half, f16x8 (&sin)[4]) {
+    sin[0] = load_nat<f16x8>(a.hash_nat, wt, 2, 0, col, half);
+    sin[1] = load_nat<f16x8>(a.hash_nat, wt, 2, 1, col, half);
+    float v[2][8];
+    f16x8 tc[2];
+    bf16x8 tc_b[2];
+    time_values<2, false>(a.t, half, v);
+    cast_values<2>(v, tc, tc_b);
+    sin[2] = tc[0]; sin[3] = tc[1];
+  }
   template <bool TRAIN>
   static __device__ __forceinline__ void operands(const CanonArgs& a, int64_t wt, int64_t nc, int col, int half, f16x8 (&sin)[4], f16x8 (&denc)[2]) {
     bf16x8 sin_b[4], denc_b[2];
@@ -413,6 +509,26 @@ __global__ void __launch_bounds__(kThreads) canon_bwd_kernel(const CanonArgs a) 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
   instant_dgrad<CanonPolicy>(a, smem, tid, lane, wave, col, half);
+}
+
+// The canonical chain of the occupancy-grid refresh (nerf_p4_grid_update): the sigma-net alone (S1, S2: 12 of the forward's 30
+// fragments) on a slab's hash image at x_c and the time code of one anchor, folded into the grid as a running maximum
+struct CanonSigmaArgs {
+  const char* packed;
+  const __bf16* hash_nat;   // nat [n_pad,32] FP16 of the slab's x_c
+  float t;                  // the anchor
+  int64_t n, n_pad;
+  float* grid;              // [n] in/out, the slab's cells
+  uint8_t* binary;          // [n]
+  float decay; int dynamic; float threshold;
+  unsigned long long* count;   // NULL: this pass does not count
+};
+constexpr int kCanonSigmaFrags = step_of(C1).frag0 - kCanonFwd0;
+
+__global__ void __launch_bounds__(kThreads) canon_sigma_grid_kernel(const CanonSigmaArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
+  instant_sigma<CanonPolicy>(a, smem, tid, lane, wave, col, half);
 }
 
 // ------------------------------------------------------------------------------------------------ per-sample inputs
@@ -648,4 +764,36 @@ extern "C" int nerf_p4_deform_bwd(const void* packed, const float* params_f32, v
   wa.n_jobs = 5;
   if (det) return wgrad_launch(wa, n, grads_f32, as_stream(stream), reinterpret_cast<float*>(static_cast<char*>(workspace) + l.slab), kSmallSlabBytes);
   return wgrad_launch(wa, n, grads_f32, as_stream(stream));
+}
+
+// The chain launches of nerf_p4_grid_update per (slab, anchor) (common.h; grid.hip has checked the entry's arguments)
+int nerf::p4_deform_lattice(const void* packed, const float* params_f32, const void* feat_nat, float t, int64_t cell0, int64_t n_cells,
+                            int resolution, float grid_bound, float* x_canonical, nerf_stream_t stream) {
+  NERF_REQUIRE(cell0 >= 0 && n_cells > 0 && resolution >= 2 && packed && params_f32 && feat_nat && x_canonical, "p4_deform_lattice: bad arguments");
+  DeformLatticeArgs a{};
+  a.packed = static_cast<const char*>(packed);
+  a.feat = static_cast<const __bf16*>(feat_nat);
+  a.params = params_f32; a.t = t;
+  a.cell0 = cell0; a.n = n_cells; a.n_pad = (n_cells + kTile - 1) / kTile * kTile;
+  a.res = resolution; a.bound = grid_bound; a.step = lattice_step(grid_bound, resolution);
+  a.xc = x_canonical;
+  const int grid = grid_for(a.n_pad / kTile, 4);
+  if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_p4_grid_update: cannot query device");
+  hipLaunchKernelGGL(p4::deform_lattice_kernel, dim3(grid), dim3(kThreads), kDeformLatticeN * 1024, as_stream(stream), a);
+  return check_launch("nerf_p4_grid_update (deformation chain)");
+}
+
+int nerf::p4_canon_sigma_grid(const void* packed, const void* hash_nat, float t, int64_t n_cells, float* grid, uint8_t* binary_grid, float decay,
+                              float threshold, unsigned long long* active_count, nerf_stream_t stream) {
+  NERF_REQUIRE(n_cells > 0 && packed && hash_nat && grid && binary_grid, "p4_canon_sigma_grid: bad arguments");
+  CanonSigmaArgs a{};
+  a.packed = static_cast<const char*>(packed);
+  a.hash_nat = static_cast<const __bf16*>(hash_nat);
+  a.t = t; a.n = n_cells; a.n_pad = (n_cells + kTile - 1) / kTile * kTile;
+  a.grid = grid; a.binary = binary_grid; a.decay = decay; a.dynamic = 1; a.threshold = threshold; a.count = active_count;
+  // two workgroups per CU, one atomic per workgroup: imlp_sigma_grid's launch shape (DESIGN 4.22 measured both)
+  const int wgs = grid_for(a.n_pad / kTile, 2);
+  if (wgs <= 0) return fail(NERF_ELAUNCH, "nerf_p4_grid_update: cannot query device");
+  hipLaunchKernelGGL(p4::canon_sigma_grid_kernel, dim3(wgs), dim3(kThreads), kCanonSigmaFrags * 1024, as_stream(stream), a);
+  return check_launch("nerf_p4_grid_update (sigma-net)");
 }

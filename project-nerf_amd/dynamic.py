@@ -270,6 +270,12 @@ def run_dynamic(cfg, args):
         use_engine3n = why is None
         if why is not None:
             say(f">>> Part 3 engine not compiled for {why}: module path")
+    # grid_update_chain: true (mode part4) -- occupancy-grid refreshes through DualHashEngine.update_grid(chain=True), one density-only
+    # launch chain
+    grid_chain = bool(cfg.get("grid_update_chain", False))
+    if grid_chain and not args.eval_only and not use_engine:
+        raise ValueError("grid_update_chain: true needs mode part4 on the fused engine (engine: true, use_density_grid and the compiled "
+                         "shapes): the refresh chain is the flat-parameter engine's; Part 3 refreshes keep their loop")
     if world > 1 and not args.eval_only:
         say(f">>> data parallel: {world} ranks x {local} rays (global batch {local * world}); clip after the all-reduce")
     sync_async = parallel.allreduce_sum_async if world > 1 else None
@@ -362,7 +368,7 @@ def run_dynamic(cfg, args):
             if step < iters * stop:
                 interval = 32 if step < iters * 0.1 else (128 if step < iters * 0.5 else 512)
                 if step >= warm and step % interval == 0:
-                    active = eng.update_grid(decay=decay)   # three time anchors, running maximum (replicated)
+                    active = eng.update_grid(decay=decay, chain=grid_chain)   # three time anchors, running maximum (replicated)
                     ahead.clear()                           # the waiting batch was compacted against the previous grid
             log(step, loss_rgb, active)
             validate(step)

@@ -1158,6 +1158,49 @@ def instant_grid_update(packed: Tensor, table: Tensor, levels: HashLevelTable, h
     return grid, binary, count
 
 
+def p4_grid_update_workspace_bytes(slab_cells: int) -> int:
+    return _lib.load().nerf_p4_grid_update_workspace_bytes(slab_cells)
+
+
+def p4_grid_update(packed: Tensor, params: Tensor, tables, levels_d: HashLevelTable, levels_c: HashLevelTable, hash_bound: float,
+                   resolution: int, grid_bound: float, threshold: float, prev: Tensor, decay: float, slab_cells: int = 2 ** 18,
+                   workspace: Optional[Tensor] = None):
+    """Occupancy-grid refresh of the Part 4 dual-hash field as one density-only launch chain (nerf_p4_grid_update): per slab of
+    ``slab_cells`` cells and per time anchor (0, 0.5, 1) the anchor's deformation gather, the deformation chain (x_c only), the
+    canonical gather and the canonical sigma-net, whose epilogue keeps the running maximum, thresholds and counts -- no lattice
+    tensor, no time vector, no rgb, no allocation or host read between the launches.  ``tables``: [start, mid, end, canonical], all
+    fp32 [entries, 2] or all fp16 copies (finite entries).  ``prev`` [res, res, res]: the running density, updated IN PLACE to
+    max(prev * decay, sigma at the three anchors), as grid_threshold does.  ``workspace``: uint8, at least
+    p4_grid_update_workspace_bytes(slab_cells) bytes (allocated here otherwise).
+    Returns (grid = prev, binary_grid bool, count int64 [1] on the device: no host sync here)."""
+    lib = _lib.load()
+    packed, params = _dev(packed, "packed", torch.uint8), _dev(params, "params")
+    if len(tables) != 4 or len({t.dtype for t in tables}) != 1:
+        raise TypeError("p4_grid_update: tables must be four tensors [start, mid, end, canonical] of one dtype (fp32 or fp16)")
+    held = [_table_arg("p4_grid_update", t, levels_c if k == 3 else levels_d)[0] for k, t in enumerate(tables)]   # kept until the launches are queued
+    ptrs = (_ct.c_void_p * 4)(*[t.data_ptr() for t in held])
+    half = held[0].dtype == torch.float16
+    res = int(resolution)
+    if res < 2:
+        raise ValueError(f"p4_grid_update: resolution {res} (at least 2)")
+    grid = _dev(prev, "prev")
+    if grid is not prev or grid.numel() != res ** 3:
+        raise ValueError("p4_grid_update: prev must be a contiguous tensor of one value per cell (it is updated in place)")
+    slab_cells = int(slab_cells)
+    need = lib.nerf_p4_grid_update_workspace_bytes(slab_cells)
+    if workspace is None:
+        workspace = torch.empty(max(need, 256), device=packed.device, dtype=torch.uint8)
+    elif _dev(workspace, "workspace", torch.uint8).numel() < need:
+        raise ValueError(f"p4_grid_update: workspace of {workspace.numel()} bytes, {need} needed for slabs of {slab_cells} cells")
+    binary = torch.empty((res, res, res), device=packed.device, dtype=torch.bool)
+    count = torch.empty(1, device=packed.device, dtype=torch.int64)      # cleared by the call
+    _lib.check(lib.nerf_p4_grid_update(_p(packed), _p(params), None if half else ptrs, ptrs if half else None, levels_d.n_levels,
+                                       *levels_d.host_args(), levels_c.n_levels, *levels_c.host_args(), float(hash_bound), res ** 3, res,
+                                       float(grid_bound), _p(grid), _p(binary), float(decay), float(threshold), _p(count), slab_cells,
+                                       _p(workspace), _stream()), "nerf_p4_grid_update")
+    return grid, binary, count
+
+
 def instant_field(table: Tensor, net_params: Tensor, packed: Tensor, pts: Tensor, dirs: Tensor,
                   levels: HashLevelTable, bound: float):
     """rgb [n,3], sigma [n] for world-space points and unit view directions."""

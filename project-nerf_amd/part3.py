@@ -323,9 +323,12 @@ class Part3InstantEngine(GridEngine):
 
     # -- occupancy grid --------------------------------------------------------------------------------------
     @torch.no_grad()
-    def update_grid(self, times) -> float:
+    def update_grid(self, times, chain: bool = False) -> float:
         """Part 3's DensityGrid refresh (reference run.py:1191-1222, renderer.py:87-101): density on the lattice at each of
         ``times``, running maximum with decay 1.0 -- the union over the times."""
+        if chain:
+            raise NotImplementedError("update_grid(chain=True): the density-only refresh chain (nerf_p4_grid_update) is wired for the Part 4 "
+                                      "dual-hash field; Part 3's MLP deformation at 8-16 times keeps the loop")
         res = self.grid.shape[0]
         lattice = self._lattice()
         ratio = 0.0

@@ -307,6 +307,7 @@ class DualHashEngine(GridEngine):
         from .specbwd import SpeculativeScatter
         on = bool(cfg.get("speculative_hash_backward", True)) and not os.environ.get("NERF_NO_SPECULATIVE_BWD")      # env: A/B aid
         self.spec_c, self.spec_d = SpeculativeScatter(on), SpeculativeScatter(on)
+        self._grid_ws = None           # update_grid(chain=True): one slab's two operand images and x_c
         self.repack()
 
     # -- parameters ------------------------------------------------------------------------------------------
@@ -541,9 +542,13 @@ class DualHashEngine(GridEngine):
         return rgb, sigma, dx
 
     @torch.no_grad()
-    def update_grid(self, decay: float = 0.95) -> float:
+    def update_grid(self, decay: float = 0.95, chain: bool = False) -> float:
         """DensityGrid.update of mode part4 (reference src/renderer.py:65-86, 122-125): density on the lattice at the time
-        anchors 0, 0.5, 1, element-wise maximum, running maximum against the decayed history."""
+        anchors 0, 0.5, 1, element-wise maximum, running maximum against the decayed history.  ``chain=True``: the refresh as ONE
+        density-only launch chain (nerf_p4_grid_update) -- no lattice tensor, one deformation gather per anchor instead of three,
+        no colour-net, one workspace kept on the engine; the same bits as the loop."""
+        if chain:
+            return self._update_grid_chain(decay)
         res = self.grid.shape[0]
         lattice = self._lattice()
         sig = torch.zeros(res ** 3, device=self.device)
@@ -552,3 +557,17 @@ class DualHashEngine(GridEngine):
                 torch.maximum(sig[i:i + s.shape[0]], s, out=sig[i:i + s.shape[0]])
         self.binary_grid, ratio = ops.grid_threshold(sig.view(res, res, res), self.grid_threshold, prev=self.grid, decay=decay)
         return ratio
+
+    _GRID_SLAB = 2 ** 18       # cells per slab of the chain refresh: the loop form's batch
+
+    def _update_grid_chain(self, decay: float) -> float:
+        res = self.grid.shape[0]
+        if self._grid_ws is None:
+            self._grid_ws = torch.empty(ops.p4_grid_update_workspace_bytes(self._GRID_SLAB), dtype=torch.uint8, device=self.device)
+        # NEW grid tensors, allocated while the old ones are alive: the speculative hash backward recognises a refresh by
+        # (data_ptr, _version) of binary_grid, and a raw kernel store into the old tensor would change neither
+        grid, binary, count = ops.p4_grid_update(self.packed, self.net, self._tables_for_forward(), self.levels_d, self.levels_c, self.bound,
+                                                 res, self.grid_bound, self.grid_threshold, self.grid.clone(), decay,
+                                                 slab_cells=self._GRID_SLAB, workspace=self._grid_ws)
+        self.grid, self.binary_grid = grid, binary
+        return float(count.item()) / binary.numel()      # the one host sync the loop form also has
