@@ -211,8 +211,8 @@ def load():
     return lib
 
 
-NORMSQ_WS_FLOATS = 4136
-COMPACT_CHAIN_WORDS = 40     # NERF_COMPACT_CHAIN_WORDS     # NERF_NORMSQ_WS_FLOATS
+NORMSQ_WS_FLOATS = 4136     # NERF_NORMSQ_WS_FLOATS
+COMPACT_CHAIN_WORDS = 40    # NERF_COMPACT_CHAIN_WORDS
 SUM_WS_FLOATS = 12288       # NERF_SUM_WS_FLOATS
 
 

@@ -49,18 +49,15 @@ def composite_mse_reg_bwd(rgb: Tensor, sigma: Tensor, slots: Tensor, z: Tensor, 
 def normsq_flat(params: Tensor, grads: Tensor, n: int, scale: float, normsq: Tensor, first: bool) -> None:
     """squared norm of ``scale`` * grads (no TV term) into the workspace ``normsq``: the step's ``first`` call STORES it (no
     zeroing launch), later calls add"""
-    _lib.check(_lib.load().nerf_tv_normsq_codes(P(params), P(grads), n, 1, 0.0, scale, P(normsq), 0 if first else 1, None, ops._stream()),
-               "nerf_tv_normsq_codes")
+    ops.tv_normsq_codes(params, grads, n, normsq, grad_scale=scale, accumulate=not first)
 
 
 def clip_adamw_flat(params: Tensor, grads: Tensor, state, n: int, step: int, lr: float, wd: float, normsq: Tensor, max_norm: float,
                     scale: float, solo: int = 0, solo_lr: float = 0.0) -> None:
     """global-norm clip (the finished squared norm in ``normsq``) + AdamW of a flat network buffer with no TV term and no fp16
     copy; ``state`` = (exp_avg, exp_avg_sq).  ``solo_lr`` != 0: element ``solo`` steps at its own rate."""
-    m, v = state
-    _lib.check(_lib.load().nerf_adamw_clip_step_tv(P(params), P(grads), P(m), P(v), n, step, lr, 0.9, 0.999, 1e-8, wd, P(normsq), max_norm,
-                                                   scale, None, 0, 0.0, 0, 0.0, 0, solo, solo_lr, None, ops._stream()),
-               "nerf_adamw_clip_step_tv")
+    ops.adamw_clip_step_tv(params, grads, *state, n, step, lr, normsq, weight_decay=wd, max_norm=max_norm, grad_scale=scale,
+                           lr_split=(solo, solo_lr))
 
 
 def wait_all(handles) -> None:

@@ -1227,6 +1227,46 @@ def adam_step(params: Tensor, grads: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor
 SMALL_GROUP = 65536        # nerf_clip_adamw_small's limit
 
 
+# The two passes of the step's tail over a flat buffer (include/nerf_hip.h), by keyword.  Tensors or views of them go in as they are
+# (their data pointers): no checks, no allocation, one launch each.
+def tv_normsq_codes(params: Tensor, grads: Tensor, n: int, normsq: Tensor, *, n_tables: int = 1, tv_weight: float = 0.0,
+                    grad_scale: float = 1.0, accumulate: bool = False, codes: Optional[Tensor] = None) -> None:
+    """pass 1: the squared norm of grads * grad_scale + TV term over ``n_tables`` equal tables into the workspace ``normsq``
+    (STORED -- no zeroing launch -- unless ``accumulate``); the TV term's signs go to ``codes`` (needed when tv_weight != 0)"""
+    _lib.check(_lib.load().nerf_tv_normsq_codes(_p(params), _p(grads), n, n_tables, tv_weight, grad_scale, _p(normsq), int(accumulate),
+                                                _p(codes), _stream()), "nerf_tv_normsq_codes")
+
+
+def tv_normsq_codes_piece(params: Tensor, grads: Tensor, n: int, normsq: Tensor, *, table_elems: int, halo: int, tv_weight: float = 0.0,
+                          grad_scale: float = 1.0, accumulate: bool = False, codes: Optional[Tensor] = None) -> None:
+    """pass 1 on a piece of ONE table of ``table_elems`` elements; ``halo`` bit 0 / 1: the element before / behind the piece belongs
+    to the table; ``codes`` starts at the piece's first byte and has at least one byte before it"""
+    _lib.check(_lib.load().nerf_tv_normsq_codes_piece(_p(params), _p(grads), n, table_elems, halo, tv_weight, grad_scale, _p(normsq),
+                                                      int(accumulate), _p(codes), _stream()), "nerf_tv_normsq_codes_piece")
+
+
+def adamw_clip_step_tv(params: Tensor, grads: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, n: int, step: int, lr: float, normsq: Tensor, *,
+                       weight_decay: float, max_norm: float, grad_scale: float, codes: Optional[Tensor] = None, tv=None, lr_split=None,
+                       shadow_f16: Optional[Tensor] = None, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+    """pass 2: global-norm clip by the finished ``normsq`` + AdamW, the TV term rebuilt from ``codes``.
+    ``tv``: (weight, elements per table) of one TV weight for the whole buffer, or (split, weight_lo, seg_lo, weight_hi, seg_hi) of two
+    ranges [0, split) and [split, n); ``lr_split``: (element, rate_hi) -- from that element on the step's rate is rate_hi;
+    ``shadow_f16``: receives the updated parameters in fp16."""
+    tv = (0, 0.0, 0, 0.0, 0) if tv is None else tv if len(tv) == 5 else (n, tv[0], tv[1], 0.0, 0)
+    _lib.check(_lib.load().nerf_adamw_clip_step_tv(_p(params), _p(grads), _p(exp_avg), _p(exp_avg_sq), n, step, lr, *betas, eps, weight_decay,
+                                                   _p(normsq), max_norm, grad_scale, _p(codes), *tv, *(lr_split or (0, 0.0)), _p(shadow_f16),
+                                                   _stream()), "nerf_adamw_clip_step_tv")
+
+
+def adamw_clip_step_tv_piece(params: Tensor, grads: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, n: int, step: int, lr: float, normsq: Tensor, *,
+                             weight_decay: float, max_norm: float, grad_scale: float, table_elems: int, halo_lo: int, tv_weight: float = 0.0,
+                             codes: Optional[Tensor] = None, shadow_f16: Optional[Tensor] = None, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+    """pass 2 on a piece of ONE table (see tv_normsq_codes_piece); ``halo_lo``: codes[-1] holds the sign in front of the piece"""
+    _lib.check(_lib.load().nerf_adamw_clip_step_tv_piece(_p(params), _p(grads), _p(exp_avg), _p(exp_avg_sq), n, step, lr, *betas, eps,
+                                                         weight_decay, _p(normsq), max_norm, grad_scale, _p(codes), tv_weight, table_elems,
+                                                         halo_lo, _p(shadow_f16), _stream()), "nerf_adamw_clip_step_tv_piece")
+
+
 def tv_clip_adamw_step(params: Tensor, grads: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, step: int, lr: float,
                        tv_weight: float = 0.0, max_norm: float = 0.0, weight_decay: float = 0.0,
                        beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, grad_scale: float = 1.0,
@@ -1258,8 +1298,6 @@ def tv_clip_adamw_step(params: Tensor, grads: Tensor, exp_avg: Tensor, exp_avg_s
                                              max_norm, grad_scale, _p(normsq), 0, _stream()), "nerf_clip_adamw_small")
         return
     # the call STORES the squared norm (accumulate 0): no zeroing launch
-    _lib.check(lib.nerf_tv_normsq_codes(_p(params), _p(grads), n, 1, tv_weight, grad_scale, _p(normsq), 0, _p(tv_codes), _stream()),
-               "nerf_tv_normsq_codes")
-    _lib.check(lib.nerf_adamw_clip_step_tv(_p(params), _p(grads), _p(exp_avg), _p(exp_avg_sq), n, step, lr, beta1, beta2, eps, weight_decay,
-                                           _p(normsq), max_norm, grad_scale, _p(tv_codes), n, tv_weight, n, 0.0, 0, 0, 0.0, _p(shadow_f16),
-                                           _stream()), "nerf_adamw_clip_step_tv")
+    tv_normsq_codes(params, grads, n, normsq, tv_weight=tv_weight, grad_scale=grad_scale, codes=tv_codes)
+    adamw_clip_step_tv(params, grads, exp_avg, exp_avg_sq, n, step, lr, normsq, weight_decay=weight_decay, max_norm=max_norm,
+                       grad_scale=grad_scale, codes=tv_codes, tv=(tv_weight, n), shadow_f16=shadow_f16, betas=(beta1, beta2), eps=eps)

@@ -301,23 +301,18 @@ class Part3InstantEngine(GridEngine):
         """TV-L1 on the canonical table, ONE global-norm clip over every parameter (clip_grad_norm_(model.parameters()),
         run.py:1174) and AdamW as one group with the cosine schedule; after a summing all-reduce the data gradient is
         averaged (1/world), the TV term is added unscaled."""
-        lib = _lib.load()
-        st = ops._stream()
         scale = 1.0 / self.world_size
         normsq = self._normsq_ws
         n_tab = self.table.numel()
         codes = self._tv_codes if self.tv != 0.0 else None
         # pass 1: the table STORES the squared norm (no zeroing launch), the networks add to it
-        _lib.check(lib.nerf_tv_normsq_codes(P(self.table), P(self.g_table), n_tab, 1, self.tv, scale, P(normsq), 0, P(codes), st),
-                   "nerf_tv_normsq_codes")
+        ops.tv_normsq_codes(self.table, self.g_table, n_tab, normsq, tv_weight=self.tv, grad_scale=scale, codes=codes)
         normsq_flat(self.net, self.g_net, N_PARAMS, scale, normsq, first=False)
         lr = self.lr()                             # the rate of THIS step: scheduler.step() follows optimizer.step()
         self.step_count += 1
         # pass 2: the whole table is the "lo" range of ONE table (tv_split = n): the seam path of two ranges is never reached
-        m, v = self.state["table"]
-        _lib.check(lib.nerf_adamw_clip_step_tv(P(self.table), P(self.g_table), P(m), P(v), n_tab, self.step_count, lr, 0.9, 0.999, 1e-8, self.wd,
-                                               P(normsq), self.max_norm, scale, P(codes), n_tab, self.tv, n_tab, 0.0, 0, 0, 0.0,
-                                               P(self.table_h), st), "nerf_adamw_clip_step_tv")
+        ops.adamw_clip_step_tv(self.table, self.g_table, *self.state["table"], n_tab, self.step_count, lr, normsq, weight_decay=self.wd,
+                               max_norm=self.max_norm, grad_scale=scale, codes=codes, tv=(self.tv, n_tab), shadow_f16=self.table_h)
         clip_adamw_flat(self.net, self.g_net, self.state["net"], N_PARAMS, self.step_count, lr, self.wd, normsq, self.max_norm, scale)
         self._pack_nets()
 

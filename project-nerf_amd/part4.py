@@ -503,8 +503,6 @@ class DualHashEngine(GridEngine):
         gradient is averaged (1/world), the TV terms are added unscaled."""
         if self.shard is not None:
             return self._apply_gradients_sharded()
-        lib = _lib.load()
-        st = ops._stream()
         scale = 1.0 / self.world_size
         normsq = self._normsq_ws                 # [0] the squared norm of ALL groups, [1] ticket, [2:] partials (include/nerf_hip.h)
         # pass 1 (three launches): ONE squared norm over all groups; the TV terms' signs go to a two-bit code per table entry instead
@@ -512,19 +510,18 @@ class DualHashEngine(GridEngine):
         # the flat buffer) in one launch, each with its own total variation
         n_def, n_can, total = self.table_sizes[0], self.table_sizes[3], self.tables.numel()
         codes = self._tv_codes
-        _lib.check(lib.nerf_tv_normsq_codes(P(self.table(0)), P(self.g_table(0)), 3 * n_def, 3, self.tv_disp, scale, P(normsq), 0, P(codes), st),
-                   "nerf_tv_normsq_codes")          # the first group STORES the norm (no zeroing launch), the others add
-        _lib.check(lib.nerf_tv_normsq_codes(P(self.table(3)), P(self.g_table(3)), n_can, 1, self.tv_canon, scale, P(normsq), 1,
-                                            P(codes[3 * n_def // 4:]), st), "nerf_tv_normsq_codes")
+        # the first group STORES the norm (no zeroing launch), the others add
+        ops.tv_normsq_codes(self.table(0), self.g_table(0), 3 * n_def, normsq, n_tables=3, tv_weight=self.tv_disp, grad_scale=scale, codes=codes)
+        ops.tv_normsq_codes(self.table(3), self.g_table(3), n_can, normsq, tv_weight=self.tv_canon, grad_scale=scale, accumulate=True,
+                            codes=codes[3 * n_def // 4:])
         normsq_flat(self.net, self.g_net, N_PARAMS, scale, normsq, first=False)
         lr_t, lr_n, lr_s = self.lr(2.0), self.lr(1.0), self.lr(5.0)      # the rates of THIS step: scheduler.step() follows optimizer.step()
         self.step_count += 1
         step = self.step_count
         # pass 2 (two launches): the four grids (TV weights per range, fp16 copy written), the networks + displacement_scale (its own rate)
-        m, v = self.state["tables"]
-        _lib.check(lib.nerf_adamw_clip_step_tv(P(self.tables), P(self.g_tables), P(m), P(v), total, step, lr_t, 0.9, 0.999, 1e-8, self.wd,
-                                               P(normsq), self.max_norm, scale, P(codes), 3 * n_def, self.tv_disp, n_def, self.tv_canon, n_can,
-                                               0, 0.0, P(self.tables_h), st), "nerf_adamw_clip_step_tv")
+        ops.adamw_clip_step_tv(self.tables, self.g_tables, *self.state["tables"], total, step, lr_t, normsq, weight_decay=self.wd,
+                               max_norm=self.max_norm, grad_scale=scale, codes=codes, tv=(3 * n_def, self.tv_disp, n_def, self.tv_canon, n_can),
+                               shadow_f16=self.tables_h)
         clip_adamw_flat(self.net, self.g_net, self.state["net"], N_PARAMS, step, lr_n, self.wd, normsq, self.max_norm, scale, SCALE, lr_s)
         pack(self.net, self.packed)
 

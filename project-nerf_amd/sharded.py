@@ -24,10 +24,9 @@ from typing import List, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
-from . import _lib, ops
+from . import ops
 
 Tensor = torch.Tensor
-P = lambda t: None if t is None else t.data_ptr()
 ALIGN = 1024
 
 
@@ -72,22 +71,19 @@ class ShardedTableOptimizer:
     def accumulate_normsq(self, normsq_ws: Tensor, grad_scale: float, first: bool = False) -> None:
         """adds this rank's part of the squared norm of (grads * grad_scale + TV terms) to normsq_ws[0] (``first``: the first piece
         STORES it, a rank without pieces stores zero -- no zeroing launch); leaves the TV sign codes"""
-        lib, st = _lib.load(), ops._stream()
         if first and not self.pieces:
             normsq_ws[:1].zero_()
         for i, (a, cnt, table_elems, tv_w, halo) in enumerate(self.pieces):
-            _lib.check(lib.nerf_tv_normsq_codes_piece(P(self.params[a:]), P(self.grads[a:]), cnt, table_elems, halo, tv_w, grad_scale,
-                                                      P(normsq_ws), 0 if (first and i == 0) else 1, P(self.codes[16 + (a - self.lo) // 4:]), st),
-                       "nerf_tv_normsq_codes_piece")
+            ops.tv_normsq_codes_piece(self.params[a:], self.grads[a:], cnt, normsq_ws, table_elems=table_elems, halo=halo, tv_weight=tv_w,
+                                      grad_scale=grad_scale, accumulate=not (first and i == 0), codes=self.codes[16 + (a - self.lo) // 4:])
 
     def adamw(self, normsq_ws: Tensor, step: int, lr: float, weight_decay: float, max_norm: float, grad_scale: float,
               beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8) -> None:
-        lib, st = _lib.load(), ops._stream()
         for a, cnt, table_elems, tv_w, halo in self.pieces:
-            _lib.check(lib.nerf_adamw_clip_step_tv_piece(P(self.params[a:]), P(self.grads[a:]), P(self.m[a:]), P(self.v[a:]), cnt, step, lr,
-                                                         beta1, beta2, eps, weight_decay, P(normsq_ws), max_norm, grad_scale,
-                                                         P(self.codes[16 + (a - self.lo) // 4:]) if tv_w != 0.0 else None, tv_w, table_elems,
-                                                         halo & 1, P(self.shadow[a:]), st), "nerf_adamw_clip_step_tv_piece")
+            ops.adamw_clip_step_tv_piece(self.params[a:], self.grads[a:], self.m[a:], self.v[a:], cnt, step, lr, normsq_ws,
+                                         weight_decay=weight_decay, max_norm=max_norm, grad_scale=grad_scale, table_elems=table_elems,
+                                         halo_lo=halo & 1, tv_weight=tv_w, codes=self.codes[16 + (a - self.lo) // 4:] if tv_w != 0.0 else None,
+                                         shadow_f16=self.shadow[a:], betas=(beta1, beta2), eps=eps)
 
     def exchange(self) -> None:
         """after the step: the neighbours' edge elements of the fp32 master (next step's TV terms) and the fp16 copy of every slice"""
