@@ -50,7 +50,8 @@ extern "C" {
 /* 11: the data side of a training step through the occupancy grid in one launch, nerf_train_batch_compact*, is new. */
 /* 12: the Instant-NGP occupancy-grid refresh as one density-only launch chain, nerf_instant_grid_update*, is new. */
 /* 13: the Part 4 occupancy-grid refresh as one density-only launch chain, nerf_p4_grid_update*, is new. */
-#define NERF_ABI_VERSION 13
+/* 14: the Part 3 (MLP deformation) occupancy-grid refresh as one density-only launch chain, nerf_p3_grid_update*, is new. */
+#define NERF_ABI_VERSION 14
 
 typedef void* nerf_stream_t;
 
@@ -314,6 +315,43 @@ int nerf_p4_grid_update(const void* packed, const float* params_f32, const float
                         float grid_bound, float* grid, uint8_t* binary_grid, float decay, float threshold,
                         unsigned long long* active_count, int64_t slab_cells, void* workspace,
                         nerf_stream_t stream);
+
+/* ---- a12 + f2: refresh of the Part 3 field's occupancy grid (MLP deformation, hash-grid canonical field) as one launch chain ----
+ * replaces the refresh loop of run_part3 (run.py:1191-1222: the union over 8-16 times across the sequence) with its
+ * DensityGrid.update(..., decay=1.0) calls (src/renderer.py:87-101, 118-132) around NeuralField('part3').forward
+ * (src/core.py:233-281) and its deformation MLP (src/decoders.py:165-195).  On the caller's stream: clear *active_count, then per
+ * slab of `slab_cells` cells and per time j: the deformation MLP chain at the scalar times_host[j] on the lattice nodes (points
+ * from the cell index, the time columns of the code formed once per wave, x_c alone is stored) -> nerf_hash_encode_fwd_nat of
+ * the canonical grid at x_c into an fp16 operand image -> canonical sigma-net (S1, S2 of nerf_p4_canon_fwd only) at the scalar
+ * time, whose epilogue folds sigma into grid / binary_grid.  The first time of a slab folds with `decay`, the others with decay
+ * 1; only the last time's pass counts.  3 * n_times * ceil(n_cells / slab_cells) + 1 enqueues, no lattice tensor, no time
+ * vector, no delta_x, no rgb, no view directions, no allocation, no host read: the call can be captured in a hipGraph as a
+ * linear chain.
+ * After the call grid, binary_grid and *active_count hold the same BITS as nerf_grid_lattice -> per time in order
+ * [nerf_p3_deform_fwd(train = 0) -> nerf_hash_encode_fwd_nat (fp16 image) -> nerf_p4_canon_fwd(train = 0, zero directions) ->
+ * nerf_grid_update(dynamic = 1; `decay` at the first time, 1 afterwards)] leave, for either table type and any slab size: the
+ * same arithmetic on the same values in the same order.
+ *   packed_deform: nerf_p3_deform_pack's image; packed_canon: nerf_p4_pack's image (the canonical decoder is Part 4's).
+ *   table_f32 / table_f16 (exactly one): the canonical table, fp32 [entries,2] or its fp16 copy.  canon_levels (16) with its
+ *   host level arrays, hash_bound: as nerf_hash_encode_fwd_nat.
+ *   times_host: HOST array of n_times (1..256) finite time stamps, read before the call returns.
+ *   Cell c is node (c / res^2, (c / res) % res, c % res) of nerf_grid_lattice's lattice for `resolution` (2..32768)
+ *   and grid_bound; n_cells must equal resolution^3.  There is no point-buffer source.
+ *   grid [n_cells] in/out: max(... max(max(grid * decay, s_0), s_1) ..., s_{T-1}); binary_grid [n_cells] bytes = grid > threshold;
+ *   *active_count (device u64) = number of set cells.
+ *   slab_cells: a positive multiple of 128 with slab_cells * 32 < 2^31.
+ *   workspace: nerf_p3_grid_update_workspace_bytes(slab_cells) bytes, 256-byte aligned, contents irrelevant.  With
+ *   rows = roundup(slab_cells, 128): [x_c rows x 3 fp32 | canonical operand image rows x 32 fp16] = (12 + 64) bytes per row,
+ *   each piece rounded up to 256 bytes (76 * rows in all: 19 922 944 bytes for 2^18 cells), reused by every (slab, time) pass
+ *   (stream order serialises them).  The query returns 0 for slab_cells <= 0. */
+size_t nerf_p3_grid_update_workspace_bytes(int64_t slab_cells);
+int nerf_p3_grid_update(const void* packed_deform, const void* packed_canon, const float* table_f32,
+                        const void* table_f16, int canon_levels, const float* c_scale_host,
+                        const unsigned* c_res_host, const unsigned* c_size_host, const unsigned* c_offset_host,
+                        const unsigned* c_dense_host, float hash_bound, const float* times_host, int n_times,
+                        int64_t n_cells, int resolution, float grid_bound, float* grid, uint8_t* binary_grid,
+                        float decay, float threshold, unsigned long long* active_count, int64_t slab_cells,
+                        void* workspace, nerf_stream_t stream);
 
 /* ---- a5: Fourier features ---------------------------------------------------
  * replaces FourierRepresentation.forward (src/embeddings.py:22-32).

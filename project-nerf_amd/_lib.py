@@ -55,6 +55,9 @@ PROTOTYPES = {
     "nerf_p4_grid_update_workspace_bytes": (size_t, [i64]),
     "nerf_p4_grid_update": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, f32,
                                   i64, i32, f32, c_ptr, c_ptr, f32, f32, c_ptr, i64, c_ptr, c_ptr]),
+    "nerf_p3_grid_update_workspace_bytes": (size_t, [i64]),
+    "nerf_p3_grid_update": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, f32, c_ptr, i32, i64, i32, f32, c_ptr, c_ptr,
+                                  f32, f32, c_ptr, i64, c_ptr, c_ptr]),
     "nerf_fourier_encode": (i32, [c_ptr, i64, i32, i32, c_ptr, c_ptr]),
     "nerf_composite_fwd": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, i64, c_ptr, i64, i32,
                                  c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
@@ -180,7 +183,7 @@ PROTOTYPES = {
     "nerf_adamw_clip_step_shadow": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, i64, i32, f32, f32, f32, f32, f32, c_ptr, f32, f32, c_ptr, c_ptr]),
 }
 
-ABI_VERSION = 13    # the NERF_ABI_VERSION of include/nerf_hip.h this table was written against
+ABI_VERSION = 14    # the NERF_ABI_VERSION of include/nerf_hip.h this table was written against
 
 _lib = None
 

@@ -95,6 +95,12 @@ int p4_deform_lattice(const void* packed, const float* params_f32, const void* f
                       float grid_bound, float* x_canonical, nerf_stream_t stream);
 int p4_canon_sigma_grid(const void* packed, const void* hash_nat, float t, int64_t n_cells, float* grid, uint8_t* binary_grid, float decay,
                         float threshold, unsigned long long* active_count, nerf_stream_t stream);
+// The deformation launch of nerf_p3_grid_update (grid.hip) per (slab of occupancy-grid cells, time t); p3deform.hip.  The Part 3
+// deformation MLP (nerf_p3_deform_pack's image) at the scalar time t on cells cell0 .. cell0 + n_cells - 1 of the res^3 lattice, the
+// points formed from the cell index: x_c [n_cells,3] fp32 and nothing else.  The canonical gather (nerf_hash_encode_fwd_nat) and
+// p4_canon_sigma_grid follow it.
+int p3_deform_lattice(const void* packed, float t, int64_t cell0, int64_t n_cells, int resolution, float grid_bound, float* x_canonical,
+                      nerf_stream_t stream);
 // mlp_fwd.hip: the 8x256 inference chain in point mode (64 samples per wave) on the first *count rows of pts / dirs, for
 // render_grid.hip's launch chain
 int mlp_fwd_counted(const void* packed, const float* pts, const float* dirs, const unsigned* count, int64_t capacity, float* rgb,

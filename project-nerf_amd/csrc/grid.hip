@@ -190,3 +190,72 @@ extern "C" int nerf_p4_grid_update(const void* packed, const float* params_f32, 
   }
   return NERF_OK;
 }
+
+// ---- the Part 3 field's refresh (MLP deformation, hash-grid canonical field) as one launch chain (reference run.py:1191-1222: the
+// union over 8-16 times through DensityGrid.update(..., decay=1.0), src/renderer.py:87-101, 118-132, around NeuralField('part3'),
+// src/core.py:233-281, with the deformation MLP of src/decoders.py:165-195) ----
+// clear the count -> per slab of `slab_cells` cells, per time j: deformation chain on the lattice nodes at the scalar time (x_c
+// alone) -> canonical gather at x_c -> canonical sigma-net chain with the running maximum in its epilogue.  The first time of a slab
+// folds against the decayed history, max(grid * decay, s_0); the others run with decay 1, so the cell ends as
+// max(... max(max(g d, s_0), s_1) ..., s_{T-1}) -- with decay 1 the reference's sequence of updates.  Only the last time's pass is
+// given the count pointer (instant_sigma skips a NULL one): binary_grid and the count are those of the finished cell.
+// The (slab, time) passes share ONE workspace; stream order serialises them.  3 * n_times * ceil(n_cells / slab_cells) + 1 enqueues.
+namespace nerf {
+struct P3GridWorkspace { size_t xc, canon_nat, total; };
+static P3GridWorkspace p3_grid_workspace(int64_t slab_cells) {
+  const size_t rows = ((size_t)slab_cells + 127) / 128 * 128;
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  P3GridWorkspace w{};
+  w.xc = 0;
+  w.canon_nat = w.xc + up(rows * 3 * 4);
+  w.total = w.canon_nat + up(rows * 32 * 2);
+  return w;
+}
+}  // namespace nerf
+
+extern "C" size_t nerf_p3_grid_update_workspace_bytes(int64_t slab_cells) {
+  return slab_cells > 0 ? p3_grid_workspace(slab_cells).total : 0;
+}
+
+extern "C" int nerf_p3_grid_update(const void* packed_deform, const void* packed_canon, const float* table_f32, const void* table_f16,
+                                   int canon_levels, const float* c_scale_host, const unsigned* c_res_host, const unsigned* c_size_host,
+                                   const unsigned* c_offset_host, const unsigned* c_dense_host, float hash_bound, const float* times_host,
+                                   int n_times, int64_t n_cells, int resolution, float grid_bound, float* grid, uint8_t* binary_grid,
+                                   float decay, float threshold, unsigned long long* active_count, int64_t slab_cells, void* workspace,
+                                   nerf_stream_t stream) {
+  NERF_REQUIRE((table_f32 == nullptr) != (table_f16 == nullptr), "nerf_p3_grid_update: exactly one of table_f32 / table_f16");
+  NERF_REQUIRE(canon_levels == 16, "nerf_p3_grid_update: canon_levels=%d (the default-shape sigma-net reads 16 levels x 2 features)", canon_levels);
+  NERF_REQUIRE(n_times >= 1 && n_times <= 256, "nerf_p3_grid_update: n_times=%d (1..256)", n_times);
+  NERF_REQUIRE(times_host != nullptr, "nerf_p3_grid_update: times_host is NULL");
+  for (int j = 0; j < n_times; ++j)
+    NERF_REQUIRE(__builtin_isfinite(times_host[j]), "nerf_p3_grid_update: times_host[%d] is not finite", j);
+  NERF_REQUIRE(resolution >= 2 && resolution <= 32768, "nerf_p3_grid_update: resolution=%d (2..32768)", resolution);
+  NERF_REQUIRE(n_cells == (int64_t)resolution * resolution * resolution, "nerf_p3_grid_update: n_cells=%lld is not resolution^3 (%d)",
+               (long long)n_cells, resolution);
+  NERF_REQUIRE(slab_cells > 0 && slab_cells % 128 == 0, "nerf_p3_grid_update: slab_cells=%lld (a positive multiple of 128)", (long long)slab_cells);
+  NERF_REQUIRE(slab_cells * 32 < ((int64_t)1 << 31), "nerf_p3_grid_update: slab too large (slab_cells * 32 must stay below 2^31)");
+  NERF_REQUIRE(workspace != nullptr, "nerf_p3_grid_update: workspace is NULL");
+  NERF_REQUIRE(((uintptr_t)workspace & 255) == 0, "nerf_p3_grid_update: workspace must be 256-byte aligned");
+  NERF_REQUIRE(hash_bound > 0.0f && grid_bound > 0.0f, "nerf_p3_grid_update: hash_bound and grid_bound must be positive");
+  NERF_REQUIRE(packed_deform && packed_canon && grid && binary_grid && active_count, "nerf_p3_grid_update: NULL pointer");
+  NERF_REQUIRE(c_scale_host && c_res_host && c_size_host && c_offset_host && c_dense_host, "nerf_p3_grid_update: NULL level table");
+  const P3GridWorkspace w = p3_grid_workspace(slab_cells);
+  char* ws = static_cast<char*>(workspace);
+  float* xc = reinterpret_cast<float*>(ws + w.xc);
+  if (hipMemsetAsync(active_count, 0, sizeof(unsigned long long), as_stream(stream)) != hipSuccess)
+    return fail(NERF_ELAUNCH, "nerf_p3_grid_update: memset failed");
+  for (int64_t c0 = 0; c0 < n_cells; c0 += slab_cells) {
+    const int64_t n = n_cells - c0 < slab_cells ? n_cells - c0 : slab_cells;
+    for (int j = 0; j < n_times; ++j) {
+      int rc = p3_deform_lattice(packed_deform, times_host[j], c0, n, resolution, grid_bound, xc, stream);
+      if (rc != NERF_OK) return rc;
+      rc = nerf_hash_encode_fwd_nat(xc, n, table_f32, table_f16, canon_levels, c_scale_host, c_res_host, c_size_host, c_offset_host,
+                                    c_dense_host, hash_bound, ws + w.canon_nat, 1, stream);
+      if (rc != NERF_OK) return rc;
+      rc = p4_canon_sigma_grid(packed_canon, ws + w.canon_nat, times_host[j], n, grid + c0, binary_grid + c0, j == 0 ? decay : 1.0f, threshold,
+                               j == n_times - 1 ? active_count : nullptr, stream);
+      if (rc != NERF_OK) return rc;
+    }
+  }
+  return NERF_OK;
+}

@@ -24,6 +24,7 @@
 //   W1 [128,84] b1 [128] W2 [128,128] b2 [128] W3 [128,128] b3 [128] W4 [3,128] b4 [3]   deform_net.net.{0,2,4,6}
 #include "resident_chain.h"
 #include "sample_chain.h"
+#include "lattice.h"
 
 namespace nerf {
 namespace p3 {
@@ -86,12 +87,73 @@ struct Args {
   __bf16* code; __bf16* h[3]; __bf16* dz[3];   // training images [n_pad][96] / [n_pad][128]
 };
 
+// Column f >= kPosDim of the layer-1 operand at time t: [t | sin(2^0 pi t) | cos(2^0 pi t) | ... (21) | 1 | 0 ...]
+__device__ __forceinline__ float time_column(int f, float t) {
+  if (f < kIn) {
+    const int c = f - kPosDim;
+    if (c == 0) return t;
+    return sincos_rev(t, (float)(1u << ((c - 1) >> 1)), ((c - 1) & 1) ? 0.25f : 0.0f);
+  }
+  return f == kIn ? 1.0f : 0.0f;
+}
+// One wave tile of the forward chain, shared by fwd_kernel and deform_lattice_kernel: the layer-1 operand of the point (x0, x1, x2)
+// -- its 63 position columns are formed here; time_of(f) is the value of column f >= kPosDim (time_column's), asked for the two
+// columns 16 ks + j and 16 ks + 8 + j of which the lane keeps its half's -- then F1..F3 with the ReLU epilogue and F4, whose
+// accumulator tile goes to out(mc, acc).  n: the lane's row (the training images' row; unused otherwise).  FENCE: run_step's, one
+// m-tile at a time.
+template <bool TRAIN, bool FENCE, class TimeOf, class Out>
+__device__ __forceinline__ void chain_tile(const char* wbase, const float* bias, float x0, float x1, float x2, TimeOf&& time_of, int64_t n,
+                                           int half, __bf16* code_img, __bf16* const (&h_img)[3], Out&& out) {
+  // layer-1 operand, natural order: column f = 16 ks + 8 half + j of [xcode (63) | tcode (21) | 1 | 0 ...]
+  f16x8 code[6];
+#pragma unroll
+  for (int ks = 0; ks < 6; ++ks) {
+    bf16x8 cb;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int f0 = 16 * ks + j, f1 = f0 + 8;       // this lane's column is f0 (half 0) or f1 (half 1)
+      auto value = [&](int f) -> float {
+        if (f < kPosDim) return feat_eval<kPosDim>(feat_spec<kPosDim>(f), x0, x1, x2);
+        return time_of(f);
+      };
+      const float v = half ? value(f1) : value(f0);
+      code[ks][j] = (_Float16)v;
+      cb[j] = (__bf16)v;
+    }
+    if constexpr (TRAIN) *reinterpret_cast<bf16x8*>(code_img + n * kCodeLd + 16 * ks + 8 * half) = cb;
+  }
+  auto relu_epi = [&](f16x8* o, __bf16* img) {
+    return [=](auto mc, f32x16 acc) {
+      constexpr int m = decltype(mc)::value;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.0f);
+      acc_to_operand16(acc, o[2 * m], o[2 * m + 1]);
+      if constexpr (TRAIN) {
+        bf16x8 lo, hi;
+        acc_to_operand(acc, lo, hi);
+        sample_chain::store_rows(img, kHid, n, m, half, lo, hi);
+      }
+    };
+  };
+  f16x8 h1[8], h2[8];
+  run_step<step_of, F1, 6, FENCE>(wbase, code, nullptr, Mfma16{}, relu_epi(h1, h_img[0]));
+  run_step<step_of, F2, 8, FENCE>(wbase, h1, bias, Mfma16{}, relu_epi(h2, h_img[1]));
+  run_step<step_of, F3, 8, FENCE>(wbase, h2, bias + 128, Mfma16{}, relu_epi(h1, h_img[2]));
+  run_step<step_of, F4, 8, FENCE>(wbase, h1, nullptr, Mfma16{}, out);
+}
+
+// forward fragments and the bias block -> LDS (the caller's barrier follows); returns the lane's A base
+__device__ __forceinline__ const char* fwd_resident(char* smem, const char* packed, int tid, int lane) {
+  const char* wbase = resident_weights<kThreads>(smem, packed, kFwd0, kFwdN, tid, lane);
+  if (tid < 128) reinterpret_cast<uint4*>(smem + kFwdN * 1024)[tid] = reinterpret_cast<const uint4*>(packed + kBiasOff)[tid];
+  return wbase;
+}
+
 template <bool TRAIN>
 __global__ void __launch_bounds__(kThreads) fwd_kernel(const Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
-  const char* wbase = resident_weights<kThreads>(smem, a.packed, kFwd0, kFwdN, tid, lane);
-  if (tid < 128) reinterpret_cast<uint4*>(smem + kFwdN * 1024)[tid] = reinterpret_cast<const uint4*>(a.packed + kBiasOff)[tid];
+  const char* wbase = fwd_resident(smem, a.packed, tid, lane);
   __syncthreads();
   const float* bias = reinterpret_cast<const float*>(smem + kFwdN * 1024);
   const int64_t n_tiles = a.n_pad / kTile;
@@ -100,47 +162,8 @@ __global__ void __launch_bounds__(kThreads) fwd_kernel(const Args a) {
     const bool live = n < a.n;
     const int64_t nc = live ? n : a.n - 1;
     const float x0 = a.x_code[nc * 3 + 0], x1 = a.x_code[nc * 3 + 1], x2 = a.x_code[nc * 3 + 2], t = a.t[nc];
-    // layer-1 operand, natural order: column f = 16 ks + 8 half + j of [xcode (63) | tcode (21) | 1 | 0 ...]
-    f16x8 code[6];
-#pragma unroll
-    for (int ks = 0; ks < 6; ++ks) {
-      bf16x8 cb;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int f0 = 16 * ks + j, f1 = f0 + 8;       // this lane's column is f0 (half 0) or f1 (half 1)
-        auto value = [&](int f) -> float {
-          if (f < kPosDim) return feat_eval<kPosDim>(feat_spec<kPosDim>(f), x0, x1, x2);
-          if (f < kIn) {
-            const int c = f - kPosDim;
-            if (c == 0) return t;
-            return sincos_rev(t, (float)(1u << ((c - 1) >> 1)), ((c - 1) & 1) ? 0.25f : 0.0f);
-          }
-          return f == kIn ? 1.0f : 0.0f;
-        };
-        const float v = half ? value(f1) : value(f0);
-        code[ks][j] = (_Float16)v;
-        cb[j] = (__bf16)v;
-      }
-      if constexpr (TRAIN) *reinterpret_cast<bf16x8*>(a.code + n * kCodeLd + 16 * ks + 8 * half) = cb;
-    }
-    auto relu_epi = [&](f16x8* out, __bf16* img) {
-      return [=](auto mc, f32x16 acc) {
-        constexpr int m = decltype(mc)::value;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.0f);
-        acc_to_operand16(acc, out[2 * m], out[2 * m + 1]);
-        if constexpr (TRAIN) {
-          bf16x8 lo, hi;
-          acc_to_operand(acc, lo, hi);
-          sample_chain::store_rows(img, kHid, n, m, half, lo, hi);
-        }
-      };
-    };
-    f16x8 h1[8], h2[8];
-    run_step<step_of, F1, 6>(wbase, code, nullptr, Mfma16{}, relu_epi(h1, a.h[0]));
-    run_step<step_of, F2, 8>(wbase, h1, bias, Mfma16{}, relu_epi(h2, a.h[1]));
-    run_step<step_of, F3, 8>(wbase, h2, bias + 128, Mfma16{}, relu_epi(h1, a.h[2]));
-    run_step<step_of, F4, 8>(wbase, h1, nullptr, Mfma16{}, [&](auto, f32x16 acc) {
+    chain_tile<TRAIN, false>(wbase, bias, x0, x1, x2, [&](int f) { return time_column(f, t); }, n, half, a.code, a.h,
+                      [&](auto, f32x16 acc) {
       if (live && half == 0) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -148,6 +171,64 @@ __global__ void __launch_bounds__(kThreads) fwd_kernel(const Args a) {
           a.dx[n * 3 + c] = d;
           a.xc[n * 3 + c] = a.x[n * 3 + c] + d;
         }
+      }
+    });
+  }
+}
+
+// The deformation chain of the occupancy-grid refresh (nerf_p3_grid_update): fwd_kernel<false> for the cells of a lattice slab at
+// ONE time stamp t, storing x_c alone.  Why the bits stay fwd_kernel's:
+//   * x is lattice_node of the cell index, the value nerf_grid_lattice stores; the code's input x' is x (evaluation adds no noise).
+//   * t is uniform, so columns 63..95 of the layer-1 operand (t, its 20 sin / cos columns, the constant 1, the zero pad) are the same
+//     in every MFMA column of every tile: formed ONCE per wave, before the tile loop, by time_column on the same value -- the
+//     lane's part of k-step 3 and all of k-steps 4 and 5, as fp16.  F1 contracts them in its own k-step order, as fwd_kernel does
+//     (they are NOT moved into an accumulator initialiser, which would change the fp32 summation order).
+//   * x_c = x + (acc + b4), fwd_kernel's association.
+struct LatticeArgs {
+  const char* packed;
+  float t;
+  int64_t cell0, n, n_pad;   // first cell of the slab, its cells, rounded up to whole tiles
+  int res;
+  float bound, step;         // the lattice (lattice.h)
+  float* xc;                 // [n,3]
+};
+
+__global__ void __launch_bounds__(kThreads) deform_lattice_kernel(const LatticeArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
+  const char* wbase = fwd_resident(smem, a.packed, tid, lane);
+  // tcode[ks - 3][j]: THIS LANE's column 16 ks + 8 half + j of k-steps 3..5, where it is a time column.  Lane-half 0 of k-step 3
+  // holds columns 48..55, all position columns: its slots stay 0 and are never asked for.
+  f16x8 tcode[3];
+#pragma unroll
+  for (int ks = 3; ks < 6; ++ks) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int f0 = 16 * ks + j, f1 = f0 + 8;
+      const float v = half ? time_column(f1, a.t) : (f0 >= kPosDim ? time_column(f0, a.t) : 0.0f);
+      tcode[ks - 3][j] = (_Float16)v;
+    }
+  }
+  __syncthreads();
+  const float* bias = reinterpret_cast<const float*>(smem + kFwdN * 1024);
+  __bf16* const no_img[3] = {nullptr, nullptr, nullptr};
+  const int64_t n_tiles = a.n_pad / kTile;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const int64_t n = (tile * kWaves + wave) * 32 + col;
+    const bool live = n < a.n;
+    int i[3];
+    lattice_cell(a.cell0 + (live ? n : a.n - 1), a.res, i[0], i[1], i[2]);
+    float x[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) x[c] = lattice_node(i[c], a.res, a.bound, a.step);
+    // chain_tile asks for columns 16 ks + j and 16 ks + 8 + j and keeps the one of the lane's half: both map to slot [ks - 3][j], which
+    // holds that half's value (fp16 -> fp32 -> fp16 is exact)
+    auto time_of = [&](int f) { return (float)tcode[f / 16 - 3][f % 8]; };
+    chain_tile<false, true>(wbase, bias, x[0], x[1], x[2], time_of, n, half, nullptr, no_img,
+                      [&](auto, f32x16 acc) {
+      if (live && half == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a.xc[n * 3 + c] = x[c] + (acc[c] + bias[256 + c]);
       }
     });
   }
@@ -367,4 +448,21 @@ extern "C" int nerf_p3_deform_bwd(const void* packed, void* workspace, const flo
   if (int rc = check_launch("nerf_p3_deform_bwd (wgrad)"); rc != NERF_OK) return rc;
   hipLaunchKernelGGL(p3::wgrad_reduce_kernel, dim3((p3::kParams + 255) / 256), dim3(256), 0, as_stream(stream), w.slab, (int)chunks, grads_f32);
   return check_launch("nerf_p3_deform_bwd (reduce)");
+}
+
+// The deformation launch of nerf_p3_grid_update per (slab, time) (common.h; grid.hip has checked the entry's arguments)
+int nerf::p3_deform_lattice(const void* packed, float t, int64_t cell0, int64_t n_cells, int resolution, float grid_bound, float* x_canonical,
+                            nerf_stream_t stream) {
+  NERF_REQUIRE(cell0 >= 0 && n_cells > 0 && resolution >= 2 && packed && x_canonical, "nerf_p3_grid_update (deformation chain): bad arguments");
+  p3::LatticeArgs a{};
+  a.packed = static_cast<const char*>(packed);
+  a.t = t;
+  a.cell0 = cell0; a.n = n_cells; a.n_pad = (n_cells + p3::kTile - 1) / p3::kTile * p3::kTile;
+  a.res = resolution; a.bound = grid_bound; a.step = lattice_step(grid_bound, resolution);
+  a.xc = x_canonical;
+  const int grid = grid_for(a.n_pad / p3::kTile, 1);   // one workgroup per CU (LDS)
+  if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_p3_grid_update: cannot query device");
+  if (int rc = ensure_dynamic_lds((const void*)p3::deform_lattice_kernel, p3::kFwdLds, "nerf_p3_grid_update"); rc != NERF_OK) return rc;
+  hipLaunchKernelGGL(p3::deform_lattice_kernel, dim3(grid), dim3(p3::kThreads), p3::kFwdLds, as_stream(stream), a);
+  return check_launch("nerf_p3_grid_update (deformation chain)");
 }

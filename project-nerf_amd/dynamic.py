@@ -270,12 +270,13 @@ def run_dynamic(cfg, args):
         use_engine3n = why is None
         if why is not None:
             say(f">>> Part 3 engine not compiled for {why}: module path")
-    # grid_update_chain: true (mode part4) -- occupancy-grid refreshes through DualHashEngine.update_grid(chain=True), one density-only
-    # launch chain
+    # grid_update_chain: true -- occupancy-grid refreshes as one density-only launch chain: DualHashEngine.update_grid(chain=True)
+    # (mode part4) or Part3InstantEngine.update_grid_chain(times) (mode part3 with the hash-grid canonical field)
     grid_chain = bool(cfg.get("grid_update_chain", False))
-    if grid_chain and not args.eval_only and not use_engine:
-        raise ValueError("grid_update_chain: true needs mode part4 on the fused engine (engine: true, use_density_grid and the compiled "
-                         "shapes): the refresh chain is the flat-parameter engine's; Part 3 refreshes keep their loop")
+    if grid_chain and not args.eval_only and not (use_engine or use_engine3):
+        raise ValueError("grid_update_chain: true needs a fused grid engine (engine: true, use_density_grid and the compiled shapes; mode "
+                         "part4, or mode part3 with canonical_type instant): the refresh chain is the flat-parameter engine's -- the "
+                         "module path and Part3NerfEngine, which has no occupancy grid, have none")
     if world > 1 and not args.eval_only:
         say(f">>> data parallel: {world} ranks x {local} rays (global batch {local * world}); clip after the all-reduce")
     sync_async = parallel.allreduce_sum_async if world > 1 else None
@@ -335,7 +336,8 @@ def run_dynamic(cfg, args):
                 # run.py:1191-1222: every 16 / 64 / 256 steps the union over 16 (later 8) times across the sequence, no decay
                 interval = 16 if step < iters * 0.1 else (64 if step < iters * 0.5 else 256)
                 if grid.should_update(step, interval, warm):
-                    active = eng.update_grid(torch.linspace(t_lo, t_hi, 16 if step < 1000 else 8).tolist())
+                    times = torch.linspace(t_lo, t_hi, 16 if step < 1000 else 8).tolist()
+                    active = eng.update_grid_chain(times) if grid_chain else eng.update_grid(times)
             log(step, loss_rgb, active)
             validate(step)
         sync()

@@ -1201,6 +1201,50 @@ def p4_grid_update(packed: Tensor, params: Tensor, tables, levels_d: HashLevelTa
     return grid, binary, count
 
 
+def p3_grid_update_workspace_bytes(slab_cells: int) -> int:
+    return _lib.load().nerf_p3_grid_update_workspace_bytes(slab_cells)
+
+
+def p3_grid_update(packed_d: Tensor, packed_c: Tensor, table: Tensor, levels: HashLevelTable, hash_bound: float, times, resolution: int,
+                   grid_bound: float, threshold: float, prev: Tensor, decay: float = 1.0, slab_cells: int = 2 ** 18,
+                   workspace: Optional[Tensor] = None):
+    """Occupancy-grid refresh of the Part 3 field (MLP deformation, hash-grid canonical field) as one density-only launch chain
+    (nerf_p3_grid_update): per slab of ``slab_cells`` cells and per time of ``times`` the deformation chain on the lattice nodes
+    (x_c only), the canonical gather and the canonical sigma-net, whose epilogue keeps the running maximum, thresholds and counts --
+    no lattice tensor, no time vector, no delta_x, no rgb, no allocation or host read between the launches.  ``packed_d``:
+    part3.deform_pack's image, ``packed_c``: part4.pack's.  ``table``: the canonical table, fp32 [entries, 2] or its fp16 copy.
+    ``times``: 1..256 finite floats.  ``prev`` [res, res, res]: the running density, updated IN PLACE to the maximum of
+    prev * decay and sigma at every time, as grid_threshold does time by time.  ``workspace``: uint8, at least
+    p3_grid_update_workspace_bytes(slab_cells) bytes (allocated here otherwise).
+    Returns (grid = prev, binary_grid bool, count int64 [1] on the device: no host sync here)."""
+    lib = _lib.load()
+    packed_d, packed_c = _dev(packed_d, "packed_d", torch.uint8), _dev(packed_c, "packed_c", torch.uint8)
+    table, table_f32, table_f16 = _table_arg("p3_grid_update", table, levels)
+    times = [float(t) for t in times]
+    if not 1 <= len(times) <= 256:
+        raise ValueError(f"p3_grid_update: {len(times)} times (1..256)")
+    times_host = (_ct.c_float * len(times))(*times)
+    res = int(resolution)
+    if res < 2:
+        raise ValueError(f"p3_grid_update: resolution {res} (at least 2)")
+    grid = _dev(prev, "prev")
+    if grid is not prev or grid.numel() != res ** 3:
+        raise ValueError("p3_grid_update: prev must be a contiguous tensor of one value per cell (it is updated in place)")
+    slab_cells = int(slab_cells)
+    need = lib.nerf_p3_grid_update_workspace_bytes(slab_cells)
+    if workspace is None:
+        workspace = torch.empty(max(need, 256), device=packed_d.device, dtype=torch.uint8)
+    elif _dev(workspace, "workspace", torch.uint8).numel() < need:
+        raise ValueError(f"p3_grid_update: workspace of {workspace.numel()} bytes, {need} needed for slabs of {slab_cells} cells")
+    binary = torch.empty((res, res, res), device=packed_d.device, dtype=torch.bool)
+    count = torch.empty(1, device=packed_d.device, dtype=torch.int64)      # cleared by the call
+    _lib.check(lib.nerf_p3_grid_update(_p(packed_d), _p(packed_c), table_f32, table_f16, levels.n_levels, *levels.host_args(),
+                                       float(hash_bound), times_host, len(times), res ** 3, res, float(grid_bound), _p(grid), _p(binary),
+                                       float(decay), float(threshold), _p(count), slab_cells, _p(workspace), _stream()),
+               "nerf_p3_grid_update")
+    return grid, binary, count
+
+
 def instant_field(table: Tensor, net_params: Tensor, packed: Tensor, pts: Tensor, dirs: Tensor,
                   levels: HashLevelTable, bound: float):
     """rgb [n,3], sigma [n] for world-space points and unit view directions."""

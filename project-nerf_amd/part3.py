@@ -322,8 +322,8 @@ class Part3InstantEngine(GridEngine):
         """Part 3's DensityGrid refresh (reference run.py:1191-1222, renderer.py:87-101): density on the lattice at each of
         ``times``, running maximum with decay 1.0 -- the union over the times."""
         if chain:
-            raise NotImplementedError("update_grid(chain=True): the density-only refresh chain (nerf_p4_grid_update) is wired for the Part 4 "
-                                      "dual-hash field; Part 3's MLP deformation at 8-16 times keeps the loop")
+            raise NotImplementedError("update_grid(chain=True): this keyword names the Part 4 dual-hash field's refresh chain "
+                                      "(nerf_p4_grid_update); Part 3's density-only chain is update_grid_chain(times)")
         res = self.grid.shape[0]
         lattice = self._lattice()
         ratio = 0.0
@@ -333,3 +333,19 @@ class Part3InstantEngine(GridEngine):
                 sig[i:i + s.shape[0]] = s
             self.binary_grid, ratio = ops.grid_threshold(sig.view(res, res, res), self.grid_threshold, prev=self.grid, decay=1.0)
         return ratio
+
+    _GRID_SLAB = 2 ** 18       # cells per slab of the chain refresh: the loop form's batch
+    _grid_ws = None            # update_grid_chain: one slab's x_c and canonical operand image
+
+    @torch.no_grad()
+    def update_grid_chain(self, times) -> float:
+        """update_grid(times) as ONE density-only launch chain (nerf_p3_grid_update): no lattice tensor, no time vectors, no
+        delta_x, no colour-net, one sync instead of one per time, one workspace kept on the engine; the same bits as the loop.
+        ``self.grid`` is updated in place and ``binary_grid`` is a new tensor, as the loop leaves them."""
+        if self._grid_ws is None:
+            self._grid_ws = torch.empty(ops.p3_grid_update_workspace_bytes(self._GRID_SLAB), dtype=torch.uint8, device=self.device)
+        _, binary, count = ops.p3_grid_update(self.packed_d, self.packed_c, self.table_h.view(-1, 2), self.levels, self.bound, times,
+                                              self.grid.shape[0], self.grid_bound, self.grid_threshold, self.grid, decay=1.0,
+                                              slab_cells=self._GRID_SLAB, workspace=self._grid_ws)
+        self.binary_grid = binary
+        return float(count.item()) / binary.numel()      # the one host sync
