@@ -51,7 +51,8 @@ extern "C" {
 /* 12: the Instant-NGP occupancy-grid refresh as one density-only launch chain, nerf_instant_grid_update*, is new. */
 /* 13: the Part 4 occupancy-grid refresh as one density-only launch chain, nerf_p4_grid_update*, is new. */
 /* 14: the Part 3 (MLP deformation) occupancy-grid refresh as one density-only launch chain, nerf_p3_grid_update*, is new. */
-#define NERF_ABI_VERSION 14
+/* 15: the Part 3 (hash-grid canonical field) evaluation launch chain, nerf_p3_render_*, is new. */
+#define NERF_ABI_VERSION 15
 
 typedef void* nerf_stream_t;
 
@@ -737,6 +738,44 @@ int nerf_render_rays_grid_fwd(const void* packed, const uint8_t* binary_grid, in
                               float near_plane, float far_plane, const float* bg, int64_t bg_rows,
                               int64_t chunk_rays, void* workspace, float* out_rgb, float* out_depth, float* out_acc,
                               nerf_stream_t stream);
+
+/* ---- a1-a4 + a7 + a8 + a10 + a11 + f2: evaluation of Part 3 with a hash-grid canonical field as one launch chain ----
+ * replaces render_rays(perturb=False) with a density_grid and render_image's chunk loop
+ * (src/renderer.py:240-384, 387-418) for mode part3 with canonical_type instant, the field query being the Part 3
+ * forward of NeuralField (src/core.py:233-281: deformation MLP src/decoders.py:165-195 applied at 262-270, hash
+ * encoding of x_c, InstantNeRFDecoder on [hash | time code]).  A frame is rendered at ONE time; per chunk of
+ * `chunk_rays` rays, on the caller's stream: clear the count word -> nerf_sample_compact (plain depths) ->
+ * deformation chain at the scalar time on the compact points -> x_c -> fp16 gather of the canonical table at x_c
+ * -> canonical chain -> nerf_composite_fwd_indexed.  The three field launches read the compaction's active
+ * count AND the time from DEVICE memory, so the host never reads anything: no allocation, no host read, no
+ * event, no synchronisation; the whole frame can be captured in a hipGraph and replayed at another time after
+ * the time word (like the rays, the table, the packed images and the grid) was overwritten in place.  Results
+ * are bit-identical to the same steps called one by one with the count read back and a time vector that
+ * repeats the time (nerf_sample_compact, nerf_p3_deform_fwd, nerf_hash_encode_fwd_nat with nat_dtype 1,
+ * nerf_p4_canon_fwd, nerf_composite_fwd_indexed), a non-finite time included.
+ *   packed_deform: nerf_p3_deform_pack's image; packed_canon: nerf_p4_pack's image of the canonical decoder.
+ *   table_f32 / table_f16 (exactly one), canon_levels (16) ... dense_host, hash_bound (> 0): the canonical grid,
+ *   as nerf_hash_encode_fwd_nat.  binary_grid [res,res,res] bytes, grid_resolution <= 32768, grid_bound (> 0):
+ *   as nerf_sample_compact.  rays_o / rays_d [n_rays,3]; 2 <= n_samples <= 1024; time_dev: ONE fp32 on the
+ *   device; bg / bg_rows as nerf_composite_fwd (bg_rows in {1, n_rays}); chunk_rays * n_samples < 2^31.
+ *   workspace: nerf_p3_render_workspace_bytes(chunk_rays, n_samples) bytes, 256-byte aligned, contents
+ *   irrelevant.  With n = chunk_rays * n_samples, every piece rounded up to 256 bytes: 256 (the count word),
+ *   z n*4, slots n*4, pts n*12, dirs n*12, operands roundup(n,128)*76 (x_c roundup(n,128)*12, then the fp16
+ *   canonical image roundup(n,128)*64), rgb n*12, sigma n*4 -- 124 bytes per sample (the training layouts of
+ *   nerf_p3_deform_workspace_bytes and nerf_p4_workspace_bytes are not used).  The query returns 0 for
+ *   non-positive arguments.  After the call the count word holds the LAST chunk's active count.
+ * Semantics: those of nerf_instant_render_rays_fwd -- a skipped sample contributes sigma = 0 and rgb = 0, a chunk
+ * without an active sample renders the background, depth 0 and acc 0, and the reference's forced query of
+ * sample 0 of the first ray (src/renderer.py:309-311) is not reproduced.  n_rays == 0 is a successful no-op. */
+size_t nerf_p3_render_workspace_bytes(int64_t chunk_rays, int n_samples);
+int nerf_p3_render_rays_fwd(const void* packed_deform, const void* packed_canon, const float* table_f32,
+                            const void* table_f16, int canon_levels, const float* scale_host,
+                            const unsigned* res_host, const unsigned* size_host, const unsigned* offset_host,
+                            const unsigned* dense_host, float hash_bound, const uint8_t* binary_grid,
+                            int grid_resolution, float grid_bound, const float* rays_o, const float* rays_d,
+                            int64_t n_rays, int n_samples, float near_plane, float far_plane, const float* time_dev,
+                            const float* bg, int64_t bg_rows, int64_t chunk_rays, void* workspace, float* out_rgb,
+                            float* out_depth, float* out_acc, nerf_stream_t stream);
 
 /* ---- a9 + a14: compositing fused with the MSE loss and its backward --------------------------
  * replaces, for one training step, volume_render (src/renderer.py:204-237), nn.MSELoss

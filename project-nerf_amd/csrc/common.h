@@ -101,6 +101,17 @@ int p4_canon_sigma_grid(const void* packed, const void* hash_nat, float t, int64
 // p4_canon_sigma_grid follow it.
 int p3_deform_lattice(const void* packed, float t, int64_t cell0, int64_t n_cells, int resolution, float grid_bound, float* x_canonical,
                       nerf_stream_t stream);
+// The three field launches of nerf_p3_render_rays_fwd (render_p3.hip) per chunk, on the first *count rows of the compaction's pts / dirs
+// (at most `capacity`, which sizes the grids) at the time *time_dev, count and time both DEVICE words.  p3deform.hip: the deformation
+// MLP at the scalar time, x_c [capacity,3] fp32 and nothing else; hashgrid.hip: hash_fwd_counted with an fp16 operand image
+// [roundup(capacity, 128), 32] (the canonical chain's operand format); p4mlp.hip: the canonical inference chain on [that image | time
+// code of the scalar] and dirs.  Nothing is touched when *count is 0.
+int p3_deform_counted(const void* packed, const float* pts, const unsigned* count, int64_t capacity, const float* time_dev, float* x_canonical,
+                      nerf_stream_t stream);
+int hash_fwd_counted_f16(const float* pts, const unsigned* count, int64_t capacity, const float* table_f32, const void* table_f16,
+                         const LevelArgs& levels, void* out_nat, nerf_stream_t stream);
+int p4_canon_fwd_counted(const void* packed, const void* hash_nat, const float* dirs, const unsigned* count, int64_t capacity,
+                         const float* time_dev, float* rgb, float* sigma, nerf_stream_t stream);
 // mlp_fwd.hip: the 8x256 inference chain in point mode (64 samples per wave) on the first *count rows of pts / dirs, for
 // render_grid.hip's launch chain
 int mlp_fwd_counted(const void* packed, const float* pts, const float* dirs, const unsigned* count, int64_t capacity, float* rgb,

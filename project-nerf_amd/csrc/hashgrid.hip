@@ -110,6 +110,19 @@ hash_fwd_counted_kernel(const float* __restrict__ pts, const unsigned* __restric
   });
 }
 
+// hash_fwd_counted_kernel for a chain whose operands are fp16 (nerf_p3_render_rays_fwd: the canonical chain of p4mlp.hip): the same
+// count handling, the image in fp16.  A kernel of its own, so that hash_fwd_counted_kernel keeps its signature and its code.
+template <class TableT>
+__global__ void __launch_bounds__(256)
+hash_fwd_counted_f16_kernel(const float* __restrict__ pts, const unsigned* __restrict__ count, int64_t capacity,
+                            const TableT* __restrict__ table, HashLevels L, __bf16* __restrict__ out_nat, int n_chunks) {
+  const int64_t n = (int64_t)*count;
+  if (n == 0) return;
+  operand_image_of(n < capacity ? n : capacity, table, L, out_nat, n_chunks, true, [pts](int64_t ps, float& x, float& y, float& z) {
+    x = pts[ps * 3 + 0]; y = pts[ps * 3 + 1]; z = pts[ps * 3 + 2];
+  });
+}
+
 // Points that are never written out: point p of the slab is cell cell0 + p of the occupancy grid's 'ij' lattice
 // (nerf_instant_grid_update, nerf_p4_grid_update; lattice.h gives the node coordinates nerf_grid_lattice would store).  n (> 0)
 // cells, known to the host.  nat_f16: the image in fp16 (the Part 4 forward chains' operands) instead of bf16.
@@ -1158,6 +1171,21 @@ int nerf::hash_fwd_counted(const float* pts, const unsigned* count, int64_t capa
                        static_cast<__bf16*>(out_nat), s.n_chunks);
   });
   return check_launch("nerf_instant_render_rays_fwd (hash)");
+}
+
+// hash_fwd_counted with the image in fp16 (common.h; called by render_p3.hip, which has checked its arguments)
+int nerf::hash_fwd_counted_f16(const float* pts, const unsigned* count, int64_t capacity, const float* table_f32, const void* table_f16,
+                               const LevelArgs& lv, void* out_nat, nerf_stream_t stream) {
+  NERF_REQUIRE(capacity > 0 && pts && count && out_nat && (table_f32 == nullptr) != (table_f16 == nullptr) && lv.scale && lv.res &&
+               lv.size && lv.offset && lv.dense, "hash_fwd_counted_f16: bad arguments");
+  HashLevels L;
+  if (int rc = fill_levels(L, lv); rc != NERF_OK) return rc;
+  const GatherShape s = gather_shape(tile_rows(capacity), lv.n_levels);
+  with_table(table_f32, table_f16, [&](auto t) {
+    hipLaunchKernelGGL(hash_fwd_counted_f16_kernel<table_t<decltype(t)>>, s.grid, dim3(256), s.lds, as_stream(stream), pts, count, capacity, t,
+                       L, static_cast<__bf16*>(out_nat), s.n_chunks);
+  });
+  return check_launch("nerf_p3_render_rays_fwd (hash)");
 }
 
 // The operand-image forward of a slab of occupancy-grid cells (common.h; called by grid.hip's nerf_instant_grid_update and

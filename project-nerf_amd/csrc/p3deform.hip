@@ -96,7 +96,7 @@ __device__ __forceinline__ float time_column(int f, float t) {
   }
   return f == kIn ? 1.0f : 0.0f;
 }
-// One wave tile of the forward chain, shared by fwd_kernel and deform_lattice_kernel: the layer-1 operand of the point (x0, x1, x2)
+// One wave tile of the forward chain, shared by fwd_kernel and the scalar-time kernels (deform_scalar_time): the layer-1 operand of the point (x0, x1, x2)
 // -- its 63 position columns are formed here; time_of(f) is the value of column f >= kPosDim (time_column's), asked for the two
 // columns 16 ks + j and 16 ks + 8 + j of which the lane keeps its half's -- then F1..F3 with the ReLU epilogue and F4, whose
 // accumulator tile goes to out(mc, acc).  n: the lane's row (the training images' row; unused otherwise).  FENCE: run_step's, one
@@ -193,10 +193,12 @@ struct LatticeArgs {
   float* xc;                 // [n,3]
 };
 
-__global__ void __launch_bounds__(kThreads) deform_lattice_kernel(const LatticeArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
-  const char* wbase = fwd_resident(smem, a.packed, tid, lane);
+// The body of the two scalar-time kernels below: rows [0, n_rows) (> 0; n_pad: rounded up to whole tiles) at the time t, the point of a
+// row supplied by point_of(row, x) -- pad rows ask for row n_rows - 1 -- and x_c stored for the live rows alone.
+template <class PointOf>
+__device__ __forceinline__ void deform_scalar_time(char* smem, const char* packed, float t, int64_t n_rows, int64_t n_pad, float* xc,
+                                                   int tid, int lane, int wave, int col, int half, PointOf point_of) {
+  const char* wbase = fwd_resident(smem, packed, tid, lane);
   // tcode[ks - 3][j]: THIS LANE's column 16 ks + 8 half + j of k-steps 3..5, where it is a time column.  Lane-half 0 of k-step 3
   // holds columns 48..55, all position columns: its slots stay 0 and are never asked for.
   f16x8 tcode[3];
@@ -205,22 +207,19 @@ __global__ void __launch_bounds__(kThreads) deform_lattice_kernel(const LatticeA
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int f0 = 16 * ks + j, f1 = f0 + 8;
-      const float v = half ? time_column(f1, a.t) : (f0 >= kPosDim ? time_column(f0, a.t) : 0.0f);
+      const float v = half ? time_column(f1, t) : (f0 >= kPosDim ? time_column(f0, t) : 0.0f);
       tcode[ks - 3][j] = (_Float16)v;
     }
   }
   __syncthreads();
   const float* bias = reinterpret_cast<const float*>(smem + kFwdN * 1024);
   __bf16* const no_img[3] = {nullptr, nullptr, nullptr};
-  const int64_t n_tiles = a.n_pad / kTile;
+  const int64_t n_tiles = n_pad / kTile;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const int64_t n = (tile * kWaves + wave) * 32 + col;
-    const bool live = n < a.n;
-    int i[3];
-    lattice_cell(a.cell0 + (live ? n : a.n - 1), a.res, i[0], i[1], i[2]);
+    const bool live = n < n_rows;
     float x[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) x[c] = lattice_node(i[c], a.res, a.bound, a.step);
+    point_of(live ? n : n_rows - 1, x);
     // chain_tile asks for columns 16 ks + j and 16 ks + 8 + j and keeps the one of the lane's half: both map to slot [ks - 3][j], which
     // holds that half's value (fp16 -> fp32 -> fp16 is exact)
     auto time_of = [&](int f) { return (float)tcode[f / 16 - 3][f % 8]; };
@@ -228,10 +227,40 @@ __global__ void __launch_bounds__(kThreads) deform_lattice_kernel(const LatticeA
                       [&](auto, f32x16 acc) {
       if (live && half == 0) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) a.xc[n * 3 + c] = x[c] + (acc[c] + bias[256 + c]);
+        for (int c = 0; c < 3; ++c) xc[n * 3 + c] = x[c] + (acc[c] + bias[256 + c]);
       }
     });
   }
+}
+
+__global__ void __launch_bounds__(kThreads) deform_lattice_kernel(const LatticeArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
+  deform_scalar_time(smem, a.packed, a.t, a.n, a.n_pad, a.xc, tid, lane, wave, col, half, [&](int64_t row, float (&x)[3]) {
+    int i[3];
+    lattice_cell(a.cell0 + row, a.res, i[0], i[1], i[2]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) x[c] = lattice_node(i[c], a.res, a.bound, a.step);
+  });
+}
+
+// The deformation chain of the Part 3 evaluation launch chain (nerf_p3_render_rays_fwd): the same body on the first *count rows of the
+// compaction's pts at the time *time_dev, both read from DEVICE memory.  The launch is sized for `capacity` rows; the count is clamped
+// to it (a count the compaction cannot produce must not become an access outside pts / xc), n == 0 leaves before n - 1 exists, and the
+// padded row count is formed here.  The early return is uniform over the launch: no barrier is skipped by part of a workgroup.
+__global__ void __launch_bounds__(kThreads) deform_counted_kernel(const char* packed, const float* __restrict__ pts,
+                                                                  const unsigned* __restrict__ count, int64_t capacity,
+                                                                  const float* __restrict__ time_dev, float* __restrict__ xc) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  int64_t n = (int64_t)*count;
+  if (n == 0) return;
+  n = n < capacity ? n : capacity;
+  const float t = *time_dev;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
+  deform_scalar_time(smem, packed, t, n, (n + kTile - 1) / kTile * kTile, xc, tid, lane, wave, col, half, [&](int64_t row, float (&x)[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) x[c] = pts[row * 3 + c];
+  });
 }
 
 __global__ void __launch_bounds__(kThreads) dgrad_kernel(const Args a) {
@@ -465,4 +494,17 @@ int nerf::p3_deform_lattice(const void* packed, float t, int64_t cell0, int64_t 
   if (int rc = ensure_dynamic_lds((const void*)p3::deform_lattice_kernel, p3::kFwdLds, "nerf_p3_grid_update"); rc != NERF_OK) return rc;
   hipLaunchKernelGGL(p3::deform_lattice_kernel, dim3(grid), dim3(p3::kThreads), p3::kFwdLds, as_stream(stream), a);
   return check_launch("nerf_p3_grid_update (deformation chain)");
+}
+
+// The deformation launch of nerf_p3_render_rays_fwd per chunk (common.h; render_p3.hip has checked the entry's arguments): sized for the
+// chunk's capacity, surplus workgroups fall out of the striding tile loop.
+int nerf::p3_deform_counted(const void* packed, const float* pts, const unsigned* count, int64_t capacity, const float* time_dev,
+                            float* x_canonical, nerf_stream_t stream) {
+  NERF_REQUIRE(capacity > 0 && packed && pts && count && time_dev && x_canonical, "nerf_p3_render_rays_fwd (deformation chain): bad arguments");
+  const int grid = grid_for((capacity + p3::kTile - 1) / p3::kTile, 1);   // one workgroup per CU (LDS)
+  if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_p3_render_rays_fwd: cannot query device");
+  if (int rc = ensure_dynamic_lds((const void*)p3::deform_counted_kernel, p3::kFwdLds, "nerf_p3_render_rays_fwd"); rc != NERF_OK) return rc;
+  hipLaunchKernelGGL(p3::deform_counted_kernel, dim3(grid), dim3(p3::kThreads), p3::kFwdLds, as_stream(stream),
+                     static_cast<const char*>(packed), pts, count, capacity, time_dev, x_canonical);
+  return check_launch("nerf_p3_render_rays_fwd (deformation chain)");
 }

@@ -505,6 +505,51 @@ __global__ void __launch_bounds__(kThreads) canon_fwd_kernel(const CanonArgs a) 
   instant_forward<CanonPolicy, TRAIN>(a, smem, tid, lane, wave, col, half);
 }
 
+// The canonical chain of the Part 3 evaluation launch chain (nerf_p3_render_rays_fwd): instant_forward<., false> on the first *count
+// rows at ONE time stamp, count and time both read from DEVICE memory.  The policy is CanonPolicy with the time code formed from the
+// scalar, by sigma_operands' calls; inference stores no image, so the struct carries the image names as NULLs only.
+struct CanonScalarArgs {
+  const char* packed;
+  const __bf16* hash_nat;  // nat [roundup(capacity, 128),32] FP16 at x_c (hash_fwd_counted_f16)
+  float t;                 // set by the kernel from its time word
+  const float* dirs;       // [capacity,3] unit view directions
+  int64_t n, n_pad;        // set by the kernel from its count word
+  float* rgb; float* sigma;
+  __bf16* hs1; __bf16* hc1; __bf16* hc2;   // never dereferenced (TRAIN = false)
+};
+struct CanonScalarPolicy : CanonPolicy {
+  template <bool TRAIN>
+  static __device__ __forceinline__ void operands(const CanonScalarArgs& a, int64_t wt, int64_t nc, int col, int half, f16x8 (&sin)[4], f16x8 (&denc)[2]) {
+    static_assert(!TRAIN, "the scalar-time canonical chain is inference only");
+    sin[0] = load_nat<f16x8>(a.hash_nat, wt, 2, 0, col, half);
+    sin[1] = load_nat<f16x8>(a.hash_nat, wt, 2, 1, col, half);
+    float v[2][8];
+    f16x8 tc[2];
+    bf16x8 tc_b[2], denc_b[2];
+    time_values<2, false>(a.t, half, v);
+    cast_values<2>(v, tc, tc_b);
+    sin[2] = tc[0]; sin[3] = tc[1];
+    dir_values<2>(a.dirs[nc * 3 + 0], a.dirs[nc * 3 + 1], a.dirs[nc * 3 + 2], half, v);
+    cast_values<2>(v, denc, denc_b);
+  }
+};
+
+// The launch is sized for `capacity` rows; the count is clamped to it (a count the compaction cannot produce must not become an access
+// outside the chunk's pieces), n == 0 leaves before n - 1 exists, n_pad is formed here.
+__global__ void __launch_bounds__(kThreads) canon_fwd_counted_kernel(const CanonScalarArgs a0, const unsigned* __restrict__ count,
+                                                                     int64_t capacity, const float* __restrict__ time_dev) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  int64_t n = (int64_t)*count;
+  if (n == 0) return;
+  n = n < capacity ? n : capacity;
+  CanonScalarArgs a = a0;
+  a.t = *time_dev;
+  a.n = n;
+  a.n_pad = (n + kTile - 1) / kTile * kTile;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
+  instant_forward<CanonScalarPolicy, false>(a, smem, tid, lane, wave, col, half);
+}
+
 __global__ void __launch_bounds__(kThreads) canon_bwd_kernel(const CanonArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
@@ -796,4 +841,19 @@ int nerf::p4_canon_sigma_grid(const void* packed, const void* hash_nat, float t,
   if (wgs <= 0) return fail(NERF_ELAUNCH, "nerf_p4_grid_update: cannot query device");
   hipLaunchKernelGGL(p4::canon_sigma_grid_kernel, dim3(wgs), dim3(kThreads), kCanonSigmaFrags * 1024, as_stream(stream), a);
   return check_launch("nerf_p4_grid_update (sigma-net)");
+}
+
+// The canonical launch of nerf_p3_render_rays_fwd per chunk (common.h; render_p3.hip has checked the entry's arguments):
+// nerf_p4_canon_fwd's launch shape sized for the chunk's capacity, surplus workgroups fall out of the striding tile loop.
+int nerf::p4_canon_fwd_counted(const void* packed, const void* hash_nat, const float* dirs, const unsigned* count, int64_t capacity,
+                               const float* time_dev, float* rgb, float* sigma, nerf_stream_t stream) {
+  NERF_REQUIRE(capacity > 0 && packed && hash_nat && dirs && count && time_dev && rgb && sigma, "p4_canon_fwd_counted: bad arguments");
+  CanonScalarArgs a{};
+  a.packed = static_cast<const char*>(packed);
+  a.hash_nat = static_cast<const __bf16*>(hash_nat);
+  a.dirs = dirs; a.rgb = rgb; a.sigma = sigma;
+  const int grid = grid_for((capacity + kTile - 1) / kTile, 4);
+  if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_p3_render_rays_fwd: cannot query device");
+  hipLaunchKernelGGL(p4::canon_fwd_counted_kernel, dim3(grid), dim3(kThreads), kCanonFwdN * 1024, as_stream(stream), a, count, capacity, time_dev);
+  return check_launch("nerf_p3_render_rays_fwd (canonical chain)");
 }

@@ -144,11 +144,18 @@ class DynamicEngine:
     # -- rendering -----------------------------------------------------------------------------------------------
     @torch.no_grad()
     def render_image(self, rays_o: Tensor, rays_d: Tensor, time: Tensor, n_samples: int, chunk: Optional[int] = None,
-                     bg: Optional[Tensor] = None) -> Tensor:
-        """one view at one time, ``chunk`` (default RENDER_CHUNK) rays per render_rays call"""
+                     bg: Optional[Tensor] = None, chain: bool = False) -> Tensor:
+        """one view at one time, ``chunk`` (default RENDER_CHUNK) rays per render_rays call.  ``chain=True``: the frame as ONE launch
+        chain, for the engines that have one (_render_image_chain)"""
         chunk = chunk or self.RENDER_CHUNK
+        if chain:
+            return self._render_image_chain(rays_o, rays_d, time, n_samples, chunk, bg)
         return render_chunks(lambda o, d: self.render_rays(o, d, time.reshape(1, 1).to(self.device), n_samples, bg=bg), rays_o, rays_d, chunk,
                              self.device)
+
+    def _render_image_chain(self, rays_o: Tensor, rays_d: Tensor, time: Tensor, n_samples: int, chunk: int, bg: Optional[Tensor]) -> Tensor:
+        raise NotImplementedError(f"render_image(chain=True): {type(self).__name__} has no evaluation launch chain (Part3InstantEngine "
+                                  "renders through nerf_p3_render_rays_fwd)")
 
 
 class GridEngine(DynamicEngine):

@@ -1105,6 +1105,36 @@ def instant_render_rays_fwd(packed: Tensor, table: Tensor, levels: HashLevelTabl
     return out, depth, acc
 
 
+def p3_render_workspace_bytes(chunk: int, n_samples: int) -> int:
+    return _lib.load().nerf_p3_render_workspace_bytes(chunk, n_samples)
+
+
+def p3_render_rays_fwd(packed_d: Tensor, packed_c: Tensor, table: Tensor, levels: HashLevelTable, hash_bound: float, binary_grid: Tensor,
+                       grid_bound: float, rays_o: Tensor, rays_d: Tensor, n_samples: int, near: float, far: float, time: Tensor,
+                       bg: Optional[Tensor] = None, chunk: int = 65536, workspace: Optional[Tensor] = None):
+    """(rgb [R,3], depth [R], acc [R]) of the Part 3 field with a hash-grid canonical field at ONE time against an occupancy grid,
+    for any number of rays: one launch chain over chunks of ``chunk`` rays in one reused workspace (nerf_p3_render_rays_fwd) --
+    compaction, the deformation chain at the scalar time, the fp16 gather of the canonical table at x_c, the canonical chain, indexed
+    compositing; the active count of a chunk and the time stay on the device, nothing is allocated or waited for between the
+    launches.  ``packed_d`` / ``packed_c``: part3.deform_pack's and part4.pack's images; ``table``: fp32 [entries, 2] or its fp16
+    copy; ``time``: a ONE-element fp32 device tensor, read by the kernels (overwrite it in place to replay a captured frame at
+    another time); ``workspace``: uint8, at least p3_render_workspace_bytes(chunk, n_samples) bytes (allocated here otherwise);
+    its first int32 holds the last chunk's active count afterwards."""
+    lib = _lib.load()
+    packed_d, grid, rays_o, rays_d, R, bg, bg_rows, chunk, workspace, out, depth, acc = _counted_render_args(
+        "p3_render_rays_fwd", lib.nerf_p3_render_workspace_bytes, packed_d, binary_grid, rays_o, rays_d, n_samples, bg, chunk, workspace)
+    packed_c = _dev(packed_c, "packed_c", torch.uint8)
+    if not isinstance(time, Tensor) or time.numel() != 1:
+        raise ValueError("p3_render_rays_fwd: time must be a one-element fp32 device tensor")
+    time = _dev(time, "time")
+    table, table_f32, table_f16 = _table_arg("p3_render_rays_fwd", table, levels)
+    _lib.check(lib.nerf_p3_render_rays_fwd(_p(packed_d), _p(packed_c), table_f32, table_f16, levels.n_levels, *levels.host_args(),
+                                           float(hash_bound), _p(grid), grid.shape[0], float(grid_bound), _p(rays_o), _p(rays_d), R,
+                                           n_samples, float(near), float(far), _p(time), _p(bg), bg_rows, chunk, _p(workspace), _p(out),
+                                           _p(depth), _p(acc), _stream()), "nerf_p3_render_rays_fwd")
+    return out, depth, acc
+
+
 def instant_grid_update_workspace_bytes(slab_cells: int) -> int:
     return _lib.load().nerf_instant_grid_update_workspace_bytes(slab_cells)
 

@@ -22,6 +22,7 @@ import torch
 from . import _lib, ops
 from . import part4 as p4
 from .dynamic_engine import GridEngine, clip_adamw_flat, composite_mse_reg_bwd, normsq_flat, sample_inputs
+from .flat_engine import render_counted_chain
 
 Tensor = torch.Tensor
 P = lambda t: None if t is None else t.data_ptr()
@@ -255,6 +256,22 @@ class Part3InstantEngine(GridEngine):
         dx, xc = deform_fwd(self.packed_d, pts, t)
         rgb, sigma = self._canonical(xc, t, dirs, self._p4_ws(n, "eval"), False)
         return rgb, sigma, dx
+
+    _chain_ws = None           # render_image(chain=True): one workspace per (chunk, n_samples)
+    _chain_time = None         # ... and the one time word its kernels read
+
+    def _render_image_chain(self, rays_o: Tensor, rays_d: Tensor, time: Tensor, n_samples: int, chunk: int, bg: Optional[Tensor]) -> Tensor:
+        """the frame as ONE launch chain (nerf_p3_render_rays_fwd): the chunks' active counts and the time stay on the device, no host
+        read, no time vector, no delta_x and no allocation per chunk; the same bits as the loop"""
+        if self._chain_ws is None:
+            self._chain_ws, self._chain_time = {}, torch.zeros(1, device=self.device)
+        self._chain_time.copy_(time.reshape(1))
+        bg = self.bg if bg is None else bg
+        return render_counted_chain(
+            lambda o, d, chunk, ws: ops.p3_render_rays_fwd(self.packed_d, self.packed_c, self.table_h.view(-1, 2), self.levels, self.bound,
+                                                           self.binary_grid, self.grid_bound, o, d, n_samples, self.near, self.far,
+                                                           self._chain_time, bg, chunk, workspace=ws),
+            ops.p3_render_workspace_bytes, self._chain_ws, rays_o, rays_d, n_samples, chunk, self.device)
 
     def compute_gradients(self, rays_o: Tensor, rays_d: Tensor, target: Tensor, times: Tensor, n_samples: int, prepared=None,
                           first_ray: int = 0, bg: Optional[Tensor] = None, sync_grads_async=None, probes=None) -> Tensor:
