@@ -20,6 +20,13 @@ inline int check_launch(const char* what) {
 
 inline hipStream_t as_stream(nerf_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// one piece of a workspace layout: its byte offset, *o moved past it to the next multiple of 256 bytes
+inline size_t piece(size_t* o, size_t bytes) {
+  const size_t at = *o;
+  *o += (bytes + 255) / 256 * 256;
+  return at;
+}
+
 // Development options (api.cpp): defaults come from the environment, read ONCE per process
 // (NERF_CHAIN_LEGACY, NERF_WGRAD_DEBUG, ...); nerf_set_option() changes them afterwards.
 struct Options {

@@ -2,6 +2,7 @@
 // lattice generation and the overwrite / running-max + threshold + active count pass.
 #include "common.h"
 #include "lattice.h"
+#include "slab_chain.h"
 
 namespace nerf {
 
@@ -59,13 +60,14 @@ extern "C" int nerf_grid_update(const float* sigma, float* grid, uint8_t* binary
 
 // ---- the Instant-NGP field's refresh as one launch chain (reference DensityGrid.update around the hash field,
 // src/renderer.py:35-132, the density query src/decoders.py:148-153) ----
-// clear the count -> per slab of `slab_cells` cells: hash gather (points from the cell index, or from `pts`) -> sigma-net chain
-// with nerf_grid_update's fold in its epilogue.  The slabs share ONE operand image; stream order serialises them.  No lattice
-// tensor, no rgb, no view directions, no allocation, no host read: 2 * ceil(n_cells / slab_cells) + 1 enqueues.
+// The slab chain of slab_chain.h with ONE pass per slab: hash gather (points from the cell index, or from `pts`) -> sigma-net chain
+// with nerf_grid_update's fold in its epilogue.  The workspace is one slab's bf16 operand image.  2 enqueues per slab.
+static const size_t kImageRowBytes = 32 * 2;             // 16 levels x 2 features, bf16 or fp16
+
 extern "C" size_t nerf_instant_grid_update_workspace_bytes(int64_t slab_cells) {
-  if (slab_cells <= 0) return 0;
-  const size_t rows = ((size_t)slab_cells + 127) / 128 * 128;
-  return (rows * 32 * 2 + 255) / 256 * 256;
+  size_t o = 0;
+  piece(&o, slab_rows(slab_cells) * kImageRowBytes);
+  return o;
 }
 
 extern "C" int nerf_instant_grid_update(const void* packed, const float* table_f32, const void* table_f16, int n_levels,
@@ -74,71 +76,52 @@ extern "C" int nerf_instant_grid_update(const void* packed, const float* table_f
                                         int64_t n_cells, int resolution, float grid_bound, float* grid, uint8_t* binary_grid, float decay,
                                         int dynamic, float threshold, unsigned long long* active_count, int64_t slab_cells,
                                         void* workspace, nerf_stream_t stream) {
-  NERF_REQUIRE(n_cells >= 0, "nerf_instant_grid_update: n_cells=%lld", (long long)n_cells);
+  static const char* const what = "nerf_instant_grid_update";
+  NERF_REQUIRE(n_cells >= 0, "%s: n_cells=%lld", what, (long long)n_cells);
   if (pts != nullptr) {
-    NERF_REQUIRE(resolution == 0, "nerf_instant_grid_update: resolution=%d with a point buffer (must be 0)", resolution);
+    NERF_REQUIRE(resolution == 0, "%s: resolution=%d with a point buffer (must be 0)", what, resolution);
     if (n_cells == 0) return NERF_OK;
   } else {
-    NERF_REQUIRE(resolution >= 2 && resolution <= 32768, "nerf_instant_grid_update: resolution=%d (2..32768)", resolution);
-    NERF_REQUIRE(n_cells == (int64_t)resolution * resolution * resolution, "nerf_instant_grid_update: n_cells=%lld is not resolution^3 (%d)",
-                 (long long)n_cells, resolution);
-    NERF_REQUIRE(grid_bound > 0.0f, "nerf_instant_grid_update: grid_bound must be positive");
+    const int ok = slab_lattice_check(what, resolution, n_cells, grid_bound);
+    if (ok != NERF_OK) return ok;
   }
-  NERF_REQUIRE(n_levels == 16, "nerf_instant_grid_update: n_levels=%d (the default-shape sigma-net reads 16 levels x 2 features)", n_levels);
-  NERF_REQUIRE((table_f32 == nullptr) != (table_f16 == nullptr), "nerf_instant_grid_update: exactly one of table_f32 / table_f16");
-  NERF_REQUIRE(slab_cells > 0 && slab_cells % 128 == 0, "nerf_instant_grid_update: slab_cells=%lld (a positive multiple of 128)",
-               (long long)slab_cells);
-  NERF_REQUIRE(slab_cells * 32 < ((int64_t)1 << 31), "nerf_instant_grid_update: slab too large (slab_cells * 32 must stay below 2^31)");
-  NERF_REQUIRE(hash_bound > 0.0f, "nerf_instant_grid_update: hash_bound must be positive");
-  NERF_REQUIRE(packed && scale_host && res_host && size_host && offset_host && dense_host && grid && binary_grid && active_count && workspace,
-               "nerf_instant_grid_update: NULL pointer");
-  NERF_REQUIRE(((uintptr_t)workspace & 255) == 0, "nerf_instant_grid_update: workspace must be 256-byte aligned");
-  if (hipMemsetAsync(active_count, 0, sizeof(unsigned long long), as_stream(stream)) != hipSuccess)
-    return fail(NERF_ELAUNCH, "nerf_instant_grid_update: memset failed");
-  for (int64_t c0 = 0; c0 < n_cells; c0 += slab_cells) {
-    const int64_t n = n_cells - c0 < slab_cells ? n_cells - c0 : slab_cells;
-    int rc;
-    if (pts != nullptr) {
-      rc = nerf_hash_encode_fwd_nat(pts + c0 * 3, n, table_f32, table_f16, n_levels, scale_host, res_host, size_host, offset_host, dense_host,
-                                    hash_bound, workspace, 0, stream);
-      if (rc != NERF_OK) return rc;
-    } else {
-      rc = hash_fwd_lattice(c0, n, resolution, grid_bound, table_f32, table_f16,
-                            LevelArgs{n_levels, scale_host, res_host, size_host, offset_host, dense_host, hash_bound}, workspace, 0, stream);
-      if (rc != NERF_OK) return rc;
-    }
-    rc = imlp_sigma_grid(packed, workspace, n, grid + c0, binary_grid + c0, decay, dynamic, threshold, active_count, stream);
-    if (rc != NERF_OK) return rc;
-  }
-  return NERF_OK;
+  NERF_REQUIRE(n_levels == 16, "%s: n_levels=%d (the default-shape sigma-net reads 16 levels x 2 features)", what, n_levels);
+  NERF_REQUIRE((table_f32 == nullptr) != (table_f16 == nullptr), "%s: exactly one of table_f32 / table_f16", what);
+  NERF_REQUIRE(hash_bound > 0.0f, "%s: hash_bound must be positive", what);
+  NERF_REQUIRE(packed && scale_host && res_host && size_host && offset_host && dense_host, "%s: NULL pointer", what);
+  const LevelArgs levels{n_levels, scale_host, res_host, size_host, offset_host, dense_host, hash_bound};
+  return slab_chain(what, n_cells, grid, binary_grid, decay, active_count, slab_cells, workspace, 1, stream,
+                    [=](int, int64_t c0, int64_t n, float* slab_grid, uint8_t* slab_binary, float slab_decay, unsigned long long* count) {
+                      const int rc = pts != nullptr
+                                         ? nerf_hash_encode_fwd_nat(pts + c0 * 3, n, table_f32, table_f16, n_levels, scale_host, res_host, size_host,
+                                                                    offset_host, dense_host, hash_bound, workspace, 0, stream)
+                                         : hash_fwd_lattice(c0, n, resolution, grid_bound, table_f32, table_f16, levels, workspace, 0, stream);
+                      if (rc != NERF_OK) return rc;
+                      return imlp_sigma_grid(packed, workspace, n, slab_grid, slab_binary, slab_decay, dynamic, threshold, count, stream);
+                    });
 }
 
 // ---- the Part 4 dual-hash field's refresh as one launch chain (reference DensityGrid.update in its dynamic form around
 // NeuralField('part4'), src/renderer.py:62-86, 118-132, src/core.py:282-352) ----
-// clear the count -> per slab of `slab_cells` cells, per time anchor k (t = 0, 0.5, 1): gather of deformation grid k ALONE at the
-// lattice nodes (the triangle weights of an anchor are a unit vector) -> density-only deformation chain (x_c) -> canonical gather at
-// x_c -> canonical sigma-net chain with the running maximum in its epilogue.  The first anchor of a slab folds against the decayed
-// history, max(grid * decay, s0); the other two run with decay 1, so the cell ends as max(max(max(g d, s0), s1), s2) -- the
-// reference's max(g d, max(s0, s1, s2)) (a maximum of non-NaN values does not depend on its grouping).  Only the last anchor's
-// pass is given the count pointer (instant_sigma skips a NULL one): binary_grid and the count are those of the finished cell.
-// The (slab, anchor) passes share ONE workspace; stream order serialises them.  12 * ceil(n_cells / slab_cells) + 1 enqueues.
-namespace nerf {
-struct P4GridWorkspace { size_t deform_nat, xc, canon_nat, total; };
-static P4GridWorkspace p4_grid_workspace(int64_t slab_cells) {
-  const size_t rows = ((size_t)slab_cells + 127) / 128 * 128;
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  P4GridWorkspace w{};
-  w.deform_nat = 0;
-  w.xc = w.deform_nat + up(rows * 32 * 2);
-  w.canon_nat = w.xc + up(rows * 3 * 4);
-  w.total = w.canon_nat + up(rows * 32 * 2);
-  return w;
-}
-}  // namespace nerf
+// The slab chain of slab_chain.h with one pass per time anchor k (t = 0, 0.5, 1): gather of deformation grid k ALONE at the lattice
+// nodes (the triangle weights of an anchor are a unit vector) -> density-only deformation chain (x_c) -> canonical gather at x_c ->
+// canonical sigma-net chain with the running maximum in its epilogue.  4 enqueues per (slab, anchor).
 
-extern "C" size_t nerf_p4_grid_update_workspace_bytes(int64_t slab_cells) {
-  return slab_cells > 0 ? p4_grid_workspace(slab_cells).total : 0;
+// byte offsets into the workspace of the two deforming fields: [fp16 operand image of a deformation grid (Part 4 alone) | x_c fp32 |
+// fp16 operand image of the canonical grid] of one slab
+struct DeformGridLayout { size_t deform_nat, xc, canon_nat, total; };
+static DeformGridLayout deform_grid_layout(int64_t slab_cells, bool deform_image) {
+  const size_t rows = slab_rows(slab_cells);
+  DeformGridLayout l{};
+  size_t o = 0;
+  l.deform_nat = piece(&o, deform_image ? rows * kImageRowBytes : 0);
+  l.xc = piece(&o, rows * 3 * 4);
+  l.canon_nat = piece(&o, rows * kImageRowBytes);
+  l.total = o;
+  return l;
 }
+
+extern "C" size_t nerf_p4_grid_update_workspace_bytes(int64_t slab_cells) { return deform_grid_layout(slab_cells, true).total; }
 
 extern "C" int nerf_p4_grid_update(const void* packed, const float* params_f32, const float* const* tables_f32, const void* const* tables_f16,
                                    int deform_levels, const float* d_scale_host, const unsigned* d_res_host, const unsigned* d_size_host,
@@ -147,75 +130,46 @@ extern "C" int nerf_p4_grid_update(const void* packed, const float* params_f32, 
                                    const unsigned* c_dense_host, float hash_bound, int64_t n_cells, int resolution, float grid_bound,
                                    float* grid, uint8_t* binary_grid, float decay, float threshold, unsigned long long* active_count,
                                    int64_t slab_cells, void* workspace, nerf_stream_t stream) {
+  static const char* const what = "nerf_p4_grid_update";
   NERF_REQUIRE((tables_f32 == nullptr) != (tables_f16 == nullptr),
-               "nerf_p4_grid_update: exactly one of tables_f32 / tables_f16 (the four tables are all fp32 or all fp16)");
+               "%s: exactly one of tables_f32 / tables_f16 (the four tables are all fp32 or all fp16)", what);
   for (int k = 0; k < 4; ++k)
-    NERF_REQUIRE((tables_f32 != nullptr ? (const void*)tables_f32[k] : tables_f16[k]) != nullptr, "nerf_p4_grid_update: table %d is NULL", k);
+    NERF_REQUIRE((tables_f32 != nullptr ? (const void*)tables_f32[k] : tables_f16[k]) != nullptr, "%s: table %d is NULL", what, k);
   NERF_REQUIRE(deform_levels == 12 && canon_levels == 16,
-               "nerf_p4_grid_update: deform_levels=%d, canon_levels=%d (the default-shape chains read 12 and 16 levels x 2 features)",
-               deform_levels, canon_levels);
-  NERF_REQUIRE(resolution >= 2 && resolution <= 32768, "nerf_p4_grid_update: resolution=%d (2..32768)", resolution);
-  NERF_REQUIRE(n_cells == (int64_t)resolution * resolution * resolution, "nerf_p4_grid_update: n_cells=%lld is not resolution^3 (%d)",
-               (long long)n_cells, resolution);
-  NERF_REQUIRE(slab_cells > 0 && slab_cells % 128 == 0, "nerf_p4_grid_update: slab_cells=%lld (a positive multiple of 128)", (long long)slab_cells);
-  NERF_REQUIRE(slab_cells * 32 < ((int64_t)1 << 31), "nerf_p4_grid_update: slab too large (slab_cells * 32 must stay below 2^31)");
-  NERF_REQUIRE(workspace != nullptr, "nerf_p4_grid_update: workspace is NULL");
-  NERF_REQUIRE(((uintptr_t)workspace & 255) == 0, "nerf_p4_grid_update: workspace must be 256-byte aligned");
-  NERF_REQUIRE(hash_bound > 0.0f && grid_bound > 0.0f, "nerf_p4_grid_update: hash_bound and grid_bound must be positive");
-  NERF_REQUIRE(packed && params_f32 && grid && binary_grid && active_count, "nerf_p4_grid_update: NULL pointer");
+               "%s: deform_levels=%d, canon_levels=%d (the default-shape chains read 12 and 16 levels x 2 features)", what, deform_levels,
+               canon_levels);
+  NERF_REQUIRE(hash_bound > 0.0f, "%s: hash_bound must be positive", what);
+  NERF_REQUIRE(packed && params_f32, "%s: NULL pointer", what);
   NERF_REQUIRE(d_scale_host && d_res_host && d_size_host && d_offset_host && d_dense_host && c_scale_host && c_res_host && c_size_host &&
-               c_offset_host && c_dense_host, "nerf_p4_grid_update: NULL level table");
+               c_offset_host && c_dense_host, "%s: NULL level table", what);
+  const int ok = slab_lattice_check(what, resolution, n_cells, grid_bound);
+  if (ok != NERF_OK) return ok;
   const LevelArgs lv_d{deform_levels, d_scale_host, d_res_host, d_size_host, d_offset_host, d_dense_host, hash_bound};
-  const P4GridWorkspace w = p4_grid_workspace(slab_cells);
+  const DeformGridLayout l = deform_grid_layout(slab_cells, true);
   char* ws = static_cast<char*>(workspace);
-  float* xc = reinterpret_cast<float*>(ws + w.xc);
-  if (hipMemsetAsync(active_count, 0, sizeof(unsigned long long), as_stream(stream)) != hipSuccess)
-    return fail(NERF_ELAUNCH, "nerf_p4_grid_update: memset failed");
-  const float anchors[3] = {0.0f, 0.5f, 1.0f};
-  for (int64_t c0 = 0; c0 < n_cells; c0 += slab_cells) {
-    const int64_t n = n_cells - c0 < slab_cells ? n_cells - c0 : slab_cells;
-    for (int k = 0; k < 3; ++k) {
-      int rc = hash_fwd_lattice(c0, n, resolution, grid_bound, tables_f32 ? tables_f32[k] : nullptr, tables_f16 ? tables_f16[k] : nullptr, lv_d,
-                                ws + w.deform_nat, 1, stream);
-      if (rc != NERF_OK) return rc;
-      rc = p4_deform_lattice(packed, params_f32, ws + w.deform_nat, anchors[k], c0, n, resolution, grid_bound, xc, stream);
-      if (rc != NERF_OK) return rc;
-      rc = nerf_hash_encode_fwd_nat(xc, n, tables_f32 ? tables_f32[3] : nullptr, tables_f16 ? tables_f16[3] : nullptr, canon_levels, c_scale_host,
-                                    c_res_host, c_size_host, c_offset_host, c_dense_host, hash_bound, ws + w.canon_nat, 1, stream);
-      if (rc != NERF_OK) return rc;
-      rc = p4_canon_sigma_grid(packed, ws + w.canon_nat, anchors[k], n, grid + c0, binary_grid + c0, k == 0 ? decay : 1.0f, threshold,
-                               k == 2 ? active_count : nullptr, stream);
-      if (rc != NERF_OK) return rc;
-    }
-  }
-  return NERF_OK;
+  return slab_chain(
+      what, n_cells, grid, binary_grid, decay, active_count, slab_cells, workspace, 3, stream,
+      [=](int k, int64_t c0, int64_t n, float* slab_grid, uint8_t* slab_binary, float slab_decay, unsigned long long* count) {
+        const float anchors[3] = {0.0f, 0.5f, 1.0f}, anchor = anchors[k];
+        float* xc = reinterpret_cast<float*>(ws + l.xc);
+        int rc = hash_fwd_lattice(c0, n, resolution, grid_bound, tables_f32 ? tables_f32[k] : nullptr, tables_f16 ? tables_f16[k] : nullptr, lv_d,
+                                  ws + l.deform_nat, 1, stream);
+        if (rc != NERF_OK) return rc;
+        rc = p4_deform_lattice(packed, params_f32, ws + l.deform_nat, anchor, c0, n, resolution, grid_bound, xc, stream);
+        if (rc != NERF_OK) return rc;
+        rc = nerf_hash_encode_fwd_nat(xc, n, tables_f32 ? tables_f32[3] : nullptr, tables_f16 ? tables_f16[3] : nullptr, canon_levels, c_scale_host,
+                                      c_res_host, c_size_host, c_offset_host, c_dense_host, hash_bound, ws + l.canon_nat, 1, stream);
+        if (rc != NERF_OK) return rc;
+        return p4_canon_sigma_grid(packed, ws + l.canon_nat, anchor, n, slab_grid, slab_binary, slab_decay, threshold, count, stream);
+      });
 }
 
 // ---- the Part 3 field's refresh (MLP deformation, hash-grid canonical field) as one launch chain (reference run.py:1191-1222: the
 // union over 8-16 times through DensityGrid.update(..., decay=1.0), src/renderer.py:87-101, 118-132, around NeuralField('part3'),
 // src/core.py:233-281, with the deformation MLP of src/decoders.py:165-195) ----
-// clear the count -> per slab of `slab_cells` cells, per time j: deformation chain on the lattice nodes at the scalar time (x_c
-// alone) -> canonical gather at x_c -> canonical sigma-net chain with the running maximum in its epilogue.  The first time of a slab
-// folds against the decayed history, max(grid * decay, s_0); the others run with decay 1, so the cell ends as
-// max(... max(max(g d, s_0), s_1) ..., s_{T-1}) -- with decay 1 the reference's sequence of updates.  Only the last time's pass is
-// given the count pointer (instant_sigma skips a NULL one): binary_grid and the count are those of the finished cell.
-// The (slab, time) passes share ONE workspace; stream order serialises them.  3 * n_times * ceil(n_cells / slab_cells) + 1 enqueues.
-namespace nerf {
-struct P3GridWorkspace { size_t xc, canon_nat, total; };
-static P3GridWorkspace p3_grid_workspace(int64_t slab_cells) {
-  const size_t rows = ((size_t)slab_cells + 127) / 128 * 128;
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  P3GridWorkspace w{};
-  w.xc = 0;
-  w.canon_nat = w.xc + up(rows * 3 * 4);
-  w.total = w.canon_nat + up(rows * 32 * 2);
-  return w;
-}
-}  // namespace nerf
-
-extern "C" size_t nerf_p3_grid_update_workspace_bytes(int64_t slab_cells) {
-  return slab_cells > 0 ? p3_grid_workspace(slab_cells).total : 0;
-}
+// The slab chain of slab_chain.h with one pass per time j: deformation chain on the lattice nodes at the scalar time (x_c alone) ->
+// canonical gather at x_c -> canonical sigma-net chain with the running maximum in its epilogue.  3 enqueues per (slab, time).
+extern "C" size_t nerf_p3_grid_update_workspace_bytes(int64_t slab_cells) { return deform_grid_layout(slab_cells, false).total; }
 
 extern "C" int nerf_p3_grid_update(const void* packed_deform, const void* packed_canon, const float* table_f32, const void* table_f16,
                                    int canon_levels, const float* c_scale_host, const unsigned* c_res_host, const unsigned* c_size_host,
@@ -223,39 +177,28 @@ extern "C" int nerf_p3_grid_update(const void* packed_deform, const void* packed
                                    int n_times, int64_t n_cells, int resolution, float grid_bound, float* grid, uint8_t* binary_grid,
                                    float decay, float threshold, unsigned long long* active_count, int64_t slab_cells, void* workspace,
                                    nerf_stream_t stream) {
-  NERF_REQUIRE((table_f32 == nullptr) != (table_f16 == nullptr), "nerf_p3_grid_update: exactly one of table_f32 / table_f16");
-  NERF_REQUIRE(canon_levels == 16, "nerf_p3_grid_update: canon_levels=%d (the default-shape sigma-net reads 16 levels x 2 features)", canon_levels);
-  NERF_REQUIRE(n_times >= 1 && n_times <= 256, "nerf_p3_grid_update: n_times=%d (1..256)", n_times);
-  NERF_REQUIRE(times_host != nullptr, "nerf_p3_grid_update: times_host is NULL");
-  for (int j = 0; j < n_times; ++j)
-    NERF_REQUIRE(__builtin_isfinite(times_host[j]), "nerf_p3_grid_update: times_host[%d] is not finite", j);
-  NERF_REQUIRE(resolution >= 2 && resolution <= 32768, "nerf_p3_grid_update: resolution=%d (2..32768)", resolution);
-  NERF_REQUIRE(n_cells == (int64_t)resolution * resolution * resolution, "nerf_p3_grid_update: n_cells=%lld is not resolution^3 (%d)",
-               (long long)n_cells, resolution);
-  NERF_REQUIRE(slab_cells > 0 && slab_cells % 128 == 0, "nerf_p3_grid_update: slab_cells=%lld (a positive multiple of 128)", (long long)slab_cells);
-  NERF_REQUIRE(slab_cells * 32 < ((int64_t)1 << 31), "nerf_p3_grid_update: slab too large (slab_cells * 32 must stay below 2^31)");
-  NERF_REQUIRE(workspace != nullptr, "nerf_p3_grid_update: workspace is NULL");
-  NERF_REQUIRE(((uintptr_t)workspace & 255) == 0, "nerf_p3_grid_update: workspace must be 256-byte aligned");
-  NERF_REQUIRE(hash_bound > 0.0f && grid_bound > 0.0f, "nerf_p3_grid_update: hash_bound and grid_bound must be positive");
-  NERF_REQUIRE(packed_deform && packed_canon && grid && binary_grid && active_count, "nerf_p3_grid_update: NULL pointer");
-  NERF_REQUIRE(c_scale_host && c_res_host && c_size_host && c_offset_host && c_dense_host, "nerf_p3_grid_update: NULL level table");
-  const P3GridWorkspace w = p3_grid_workspace(slab_cells);
+  static const char* const what = "nerf_p3_grid_update";
+  NERF_REQUIRE((table_f32 == nullptr) != (table_f16 == nullptr), "%s: exactly one of table_f32 / table_f16", what);
+  NERF_REQUIRE(canon_levels == 16, "%s: canon_levels=%d (the default-shape sigma-net reads 16 levels x 2 features)", what, canon_levels);
+  NERF_REQUIRE(n_times >= 1 && n_times <= 256, "%s: n_times=%d (1..256)", what, n_times);
+  NERF_REQUIRE(times_host != nullptr, "%s: times_host is NULL", what);
+  for (int j = 0; j < n_times; ++j) NERF_REQUIRE(__builtin_isfinite(times_host[j]), "%s: times_host[%d] is not finite", what, j);
+  NERF_REQUIRE(hash_bound > 0.0f, "%s: hash_bound must be positive", what);
+  NERF_REQUIRE(packed_deform && packed_canon, "%s: NULL pointer", what);
+  NERF_REQUIRE(c_scale_host && c_res_host && c_size_host && c_offset_host && c_dense_host, "%s: NULL level table", what);
+  const int ok = slab_lattice_check(what, resolution, n_cells, grid_bound);
+  if (ok != NERF_OK) return ok;
+  const DeformGridLayout l = deform_grid_layout(slab_cells, false);
   char* ws = static_cast<char*>(workspace);
-  float* xc = reinterpret_cast<float*>(ws + w.xc);
-  if (hipMemsetAsync(active_count, 0, sizeof(unsigned long long), as_stream(stream)) != hipSuccess)
-    return fail(NERF_ELAUNCH, "nerf_p3_grid_update: memset failed");
-  for (int64_t c0 = 0; c0 < n_cells; c0 += slab_cells) {
-    const int64_t n = n_cells - c0 < slab_cells ? n_cells - c0 : slab_cells;
-    for (int j = 0; j < n_times; ++j) {
-      int rc = p3_deform_lattice(packed_deform, times_host[j], c0, n, resolution, grid_bound, xc, stream);
-      if (rc != NERF_OK) return rc;
-      rc = nerf_hash_encode_fwd_nat(xc, n, table_f32, table_f16, canon_levels, c_scale_host, c_res_host, c_size_host, c_offset_host,
-                                    c_dense_host, hash_bound, ws + w.canon_nat, 1, stream);
-      if (rc != NERF_OK) return rc;
-      rc = p4_canon_sigma_grid(packed_canon, ws + w.canon_nat, times_host[j], n, grid + c0, binary_grid + c0, j == 0 ? decay : 1.0f, threshold,
-                               j == n_times - 1 ? active_count : nullptr, stream);
-      if (rc != NERF_OK) return rc;
-    }
-  }
-  return NERF_OK;
+  return slab_chain(
+      what, n_cells, grid, binary_grid, decay, active_count, slab_cells, workspace, n_times, stream,
+      [=](int j, int64_t c0, int64_t n, float* slab_grid, uint8_t* slab_binary, float slab_decay, unsigned long long* count) {
+        float* xc = reinterpret_cast<float*>(ws + l.xc);
+        int rc = p3_deform_lattice(packed_deform, times_host[j], c0, n, resolution, grid_bound, xc, stream);
+        if (rc != NERF_OK) return rc;
+        rc = nerf_hash_encode_fwd_nat(xc, n, table_f32, table_f16, canon_levels, c_scale_host, c_res_host, c_size_host, c_offset_host,
+                                      c_dense_host, hash_bound, ws + l.canon_nat, 1, stream);
+        if (rc != NERF_OK) return rc;
+        return p4_canon_sigma_grid(packed_canon, ws + l.canon_nat, times_host[j], n, slab_grid, slab_binary, slab_decay, threshold, count, stream);
+      });
 }

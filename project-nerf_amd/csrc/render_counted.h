@@ -17,12 +17,6 @@ namespace nerf {
 // byte offsets into the workspace; the count word sits at offset 0
 struct CountedRenderLayout { size_t z, slots, pts, dirs, image, rgb, sigma, total; };
 
-inline size_t piece(size_t* o, size_t bytes) {
-  const size_t at = *o;
-  *o += (bytes + 255) / 256 * 256;
-  return at;
-}
-
 // image_row_bytes: bytes per sample of the operand image between the compaction and the decoder, its rows padded to a multiple
 // of 128 samples (0: the entry has none, and the piece takes no room)
 inline CountedRenderLayout counted_render_layout(int64_t chunk_rays, int n_samples, size_t image_row_bytes) {

@@ -19,7 +19,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import flat_params, ops
-from .flat_engine import LapSlots, ViewSlots, cosine_lr, render_chunks, render_counted_chain
+from .flat_engine import LapSlots, ViewSlots, cosine_lr, grid_update_chain, render_chunks, render_counted_chain
 
 Tensor = torch.Tensor
 
@@ -695,15 +695,12 @@ class InstantNgpEngine:
     _GRID_SLAB = 2 ** 18       # cells per slab of the chain refresh: the loop form's batch
 
     def _update_grid_chain(self) -> float:
-        res = self.grid.shape[0]
-        if self._grid_ws is None:
-            self._grid_ws = torch.empty(ops.instant_grid_update_workspace_bytes(self._GRID_SLAB), dtype=torch.uint8, device=self.device)
         # NEW grid tensors, allocated while the old ones are alive: the speculative hash backward recognises a new grid by
         # (data_ptr, _version) of binary_grid, and a raw kernel store into the old tensor would change neither
-        grid, binary, count = ops.instant_grid_update(self.packed, self._gather_table(), self.levels, self.bound, res, self.bound,
-                                                      self.grid_threshold, slab_cells=self._GRID_SLAB, workspace=self._grid_ws)
-        self.grid, self.binary_grid = grid, binary
-        return float(count.item()) / binary.numel()      # the one host sync the loop form also has
+        return grid_update_chain(                        # its one host sync the loop form also has
+            self, lambda slab, ws: ops.instant_grid_update(self.packed, self._gather_table(), self.levels, self.bound, self.grid.shape[0],
+                                                           self.bound, self.grid_threshold, slab_cells=slab, workspace=ws),
+            ops.instant_grid_update_workspace_bytes)
 
     @torch.no_grad()
     def render_rays(self, rays_o: Tensor, rays_d: Tensor, n_samples: int):

@@ -1135,6 +1135,36 @@ def p3_render_rays_fwd(packed_d: Tensor, packed_c: Tensor, table: Tensor, levels
     return out, depth, acc
 
 
+def _grid_update_args(name: str, workspace_bytes, device, resolution, prev, slab_cells, workspace, n_points: Optional[int] = None,
+                      fresh: bool = False):
+    """the checked arguments and the allocated outputs of the three occupancy-grid refresh chains (``name``: the entry, for the
+    messages; ``workspace_bytes``: its size query; the cells are the res^3 lattice nodes, or ``n_points`` points where that is
+    given; ``fresh``: without ``prev`` a new grid is allocated): (res -- 0 for points --, grid -- ``prev``, which the chain
+    updates in place --, binary bool, count int64 [1] that the call clears, slab_cells, workspace)"""
+    if n_points is None:
+        res = int(resolution)
+        if res < 2:
+            raise ValueError(f"{name}: resolution {res} (at least 2)")
+        shape = (res, res, res)
+    else:
+        res, shape = 0, (n_points,)
+    if prev is not None or not fresh:
+        grid = _dev(prev, "prev")
+        if grid is not prev or grid.numel() != _math.prod(shape):
+            raise ValueError(f"{name}: prev must be a contiguous tensor of one value per cell (it is updated in place)")
+    else:
+        grid = torch.empty(shape, device=device, dtype=torch.float32)
+    slab_cells = int(slab_cells)
+    need = workspace_bytes(slab_cells)
+    if workspace is None:
+        workspace = torch.empty(need, device=device, dtype=torch.uint8)
+    elif _dev(workspace, "workspace", torch.uint8).numel() < need:
+        raise ValueError(f"{name}: workspace of {workspace.numel()} bytes, {need} needed for slabs of {slab_cells} cells")
+    binary = torch.empty(shape, device=device, dtype=torch.bool)
+    count = torch.empty(1, device=device, dtype=torch.int64)
+    return res, grid, binary, count, slab_cells, workspace
+
+
 def instant_grid_update_workspace_bytes(slab_cells: int) -> int:
     return _lib.load().nerf_instant_grid_update_workspace_bytes(slab_cells)
 
@@ -1152,39 +1182,18 @@ def instant_grid_update(packed: Tensor, table: Tensor, levels: HashLevelTable, h
     lib = _lib.load()
     packed = _dev(packed, "packed", torch.uint8)
     table, table_f32, table_f16 = _table_arg("instant_grid_update", table, levels)
-    if isinstance(source, Tensor):
-        pts = _dev(source, "pts")
-        if pts.dim() != 2 or pts.shape[1] != 3:
-            raise ValueError(f"instant_grid_update: pts of shape {tuple(pts.shape)}, expected [n, 3]")
-        res, shape = 0, (pts.shape[0],)
-    else:
-        pts, res = None, int(source)
-        if res < 2:
-            raise ValueError(f"instant_grid_update: resolution {res} (at least 2)")
-        shape = (res, res, res)
-    n = 1
-    for s in shape:
-        n *= s
-    slab_cells = int(slab_cells)
-    need = lib.nerf_instant_grid_update_workspace_bytes(slab_cells)
-    if prev is not None:
-        grid = _dev(prev, "prev")
-        if grid is not prev or grid.numel() != n:
-            raise ValueError("instant_grid_update: prev must be a contiguous tensor of one value per cell (it is updated in place)")
-    else:
-        grid = torch.empty(shape, device=packed.device, dtype=torch.float32)
-    if workspace is None:
-        workspace = torch.empty(need, device=packed.device, dtype=torch.uint8)
-    elif _dev(workspace, "workspace", torch.uint8).numel() < need:
-        raise ValueError(f"instant_grid_update: workspace of {workspace.numel()} bytes, {need} needed for slabs of {slab_cells} cells")
-    binary = torch.empty(shape, device=packed.device, dtype=torch.bool)
-    if n == 0:               # an empty point buffer (its data pointer is NULL: the entry would take it for the lattice source)
-        return grid, binary, torch.zeros(1, device=packed.device, dtype=torch.int64)
-    count = torch.empty(1, device=packed.device, dtype=torch.int64)      # cleared by the call
+    pts = _dev(source, "pts") if isinstance(source, Tensor) else None
+    if pts is not None and (pts.dim() != 2 or pts.shape[1] != 3):
+        raise ValueError(f"instant_grid_update: pts of shape {tuple(pts.shape)}, expected [n, 3]")
+    res, grid, binary, count, slab_cells, workspace = _grid_update_args(
+        "instant_grid_update", lib.nerf_instant_grid_update_workspace_bytes, packed.device, source, prev, slab_cells, workspace,
+        n_points=None if pts is None else pts.shape[0], fresh=True)
+    if grid.numel() == 0:    # an empty point buffer (its data pointer is NULL: the entry would take it for the lattice source)
+        return grid, binary, count.zero_()
     _lib.check(lib.nerf_instant_grid_update(_p(packed), table_f32, table_f16, levels.n_levels,
-                                            *levels.host_args(), float(hash_bound), _p(pts), n, res, float(grid_bound), _p(grid), _p(binary),
-                                            float(decay), 0 if prev is None else 1, float(threshold), _p(count), slab_cells, _p(workspace),
-                                            _stream()), "nerf_instant_grid_update")
+                                            *levels.host_args(), float(hash_bound), _p(pts), grid.numel(), res, float(grid_bound), _p(grid),
+                                            _p(binary), float(decay), 0 if prev is None else 1, float(threshold), _p(count), slab_cells,
+                                            _p(workspace), _stream()), "nerf_instant_grid_update")
     return grid, binary, count
 
 
@@ -1210,20 +1219,8 @@ def p4_grid_update(packed: Tensor, params: Tensor, tables, levels_d: HashLevelTa
     held = [_table_arg("p4_grid_update", t, levels_c if k == 3 else levels_d)[0] for k, t in enumerate(tables)]   # kept until the launches are queued
     ptrs = (_ct.c_void_p * 4)(*[t.data_ptr() for t in held])
     half = held[0].dtype == torch.float16
-    res = int(resolution)
-    if res < 2:
-        raise ValueError(f"p4_grid_update: resolution {res} (at least 2)")
-    grid = _dev(prev, "prev")
-    if grid is not prev or grid.numel() != res ** 3:
-        raise ValueError("p4_grid_update: prev must be a contiguous tensor of one value per cell (it is updated in place)")
-    slab_cells = int(slab_cells)
-    need = lib.nerf_p4_grid_update_workspace_bytes(slab_cells)
-    if workspace is None:
-        workspace = torch.empty(max(need, 256), device=packed.device, dtype=torch.uint8)
-    elif _dev(workspace, "workspace", torch.uint8).numel() < need:
-        raise ValueError(f"p4_grid_update: workspace of {workspace.numel()} bytes, {need} needed for slabs of {slab_cells} cells")
-    binary = torch.empty((res, res, res), device=packed.device, dtype=torch.bool)
-    count = torch.empty(1, device=packed.device, dtype=torch.int64)      # cleared by the call
+    res, grid, binary, count, slab_cells, workspace = _grid_update_args(
+        "p4_grid_update", lib.nerf_p4_grid_update_workspace_bytes, packed.device, resolution, prev, slab_cells, workspace)
     _lib.check(lib.nerf_p4_grid_update(_p(packed), _p(params), None if half else ptrs, ptrs if half else None, levels_d.n_levels,
                                        *levels_d.host_args(), levels_c.n_levels, *levels_c.host_args(), float(hash_bound), res ** 3, res,
                                        float(grid_bound), _p(grid), _p(binary), float(decay), float(threshold), _p(count), slab_cells,
@@ -1254,20 +1251,8 @@ def p3_grid_update(packed_d: Tensor, packed_c: Tensor, table: Tensor, levels: Ha
     if not 1 <= len(times) <= 256:
         raise ValueError(f"p3_grid_update: {len(times)} times (1..256)")
     times_host = (_ct.c_float * len(times))(*times)
-    res = int(resolution)
-    if res < 2:
-        raise ValueError(f"p3_grid_update: resolution {res} (at least 2)")
-    grid = _dev(prev, "prev")
-    if grid is not prev or grid.numel() != res ** 3:
-        raise ValueError("p3_grid_update: prev must be a contiguous tensor of one value per cell (it is updated in place)")
-    slab_cells = int(slab_cells)
-    need = lib.nerf_p3_grid_update_workspace_bytes(slab_cells)
-    if workspace is None:
-        workspace = torch.empty(max(need, 256), device=packed_d.device, dtype=torch.uint8)
-    elif _dev(workspace, "workspace", torch.uint8).numel() < need:
-        raise ValueError(f"p3_grid_update: workspace of {workspace.numel()} bytes, {need} needed for slabs of {slab_cells} cells")
-    binary = torch.empty((res, res, res), device=packed_d.device, dtype=torch.bool)
-    count = torch.empty(1, device=packed_d.device, dtype=torch.int64)      # cleared by the call
+    res, grid, binary, count, slab_cells, workspace = _grid_update_args(
+        "p3_grid_update", lib.nerf_p3_grid_update_workspace_bytes, packed_d.device, resolution, prev, slab_cells, workspace)
     _lib.check(lib.nerf_p3_grid_update(_p(packed_d), _p(packed_c), table_f32, table_f16, levels.n_levels, *levels.host_args(),
                                        float(hash_bound), times_host, len(times), res ** 3, res, float(grid_bound), _p(grid), _p(binary),
                                        float(decay), float(threshold), _p(count), slab_cells, _p(workspace), _stream()),

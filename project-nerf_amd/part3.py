@@ -22,7 +22,7 @@ import torch
 from . import _lib, ops
 from . import part4 as p4
 from .dynamic_engine import GridEngine, clip_adamw_flat, composite_mse_reg_bwd, normsq_flat, sample_inputs
-from .flat_engine import render_counted_chain
+from .flat_engine import grid_update_chain, render_counted_chain
 
 Tensor = torch.Tensor
 P = lambda t: None if t is None else t.data_ptr()
@@ -359,10 +359,8 @@ class Part3InstantEngine(GridEngine):
         """update_grid(times) as ONE density-only launch chain (nerf_p3_grid_update): no lattice tensor, no time vectors, no
         delta_x, no colour-net, one sync instead of one per time, one workspace kept on the engine; the same bits as the loop.
         ``self.grid`` is updated in place and ``binary_grid`` is a new tensor, as the loop leaves them."""
-        if self._grid_ws is None:
-            self._grid_ws = torch.empty(ops.p3_grid_update_workspace_bytes(self._GRID_SLAB), dtype=torch.uint8, device=self.device)
-        _, binary, count = ops.p3_grid_update(self.packed_d, self.packed_c, self.table_h.view(-1, 2), self.levels, self.bound, times,
-                                              self.grid.shape[0], self.grid_bound, self.grid_threshold, self.grid, decay=1.0,
-                                              slab_cells=self._GRID_SLAB, workspace=self._grid_ws)
-        self.binary_grid = binary
-        return float(count.item()) / binary.numel()      # the one host sync
+        return grid_update_chain(                        # its one host sync; the grid it installs is ``self.grid`` itself
+            self, lambda slab, ws: ops.p3_grid_update(self.packed_d, self.packed_c, self.table_h.view(-1, 2), self.levels, self.bound, times,
+                                                      self.grid.shape[0], self.grid_bound, self.grid_threshold, self.grid, decay=1.0,
+                                                      slab_cells=slab, workspace=ws),
+            ops.p3_grid_update_workspace_bytes)

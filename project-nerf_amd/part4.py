@@ -19,7 +19,7 @@ import torch
 
 from . import _lib, ops
 from .dynamic_engine import GridEngine, clip_adamw_flat, composite_mse_reg_bwd, normsq_flat, sample_inputs, wait_all
-from .flat_engine import ViewSlots
+from .flat_engine import ViewSlots, grid_update_chain
 
 Tensor = torch.Tensor
 P = lambda t: None if t is None else t.data_ptr()
@@ -558,13 +558,10 @@ class DualHashEngine(GridEngine):
     _GRID_SLAB = 2 ** 18       # cells per slab of the chain refresh: the loop form's batch
 
     def _update_grid_chain(self, decay: float) -> float:
-        res = self.grid.shape[0]
-        if self._grid_ws is None:
-            self._grid_ws = torch.empty(ops.p4_grid_update_workspace_bytes(self._GRID_SLAB), dtype=torch.uint8, device=self.device)
         # NEW grid tensors, allocated while the old ones are alive: the speculative hash backward recognises a refresh by
         # (data_ptr, _version) of binary_grid, and a raw kernel store into the old tensor would change neither
-        grid, binary, count = ops.p4_grid_update(self.packed, self.net, self._tables_for_forward(), self.levels_d, self.levels_c, self.bound,
-                                                 res, self.grid_bound, self.grid_threshold, self.grid.clone(), decay,
-                                                 slab_cells=self._GRID_SLAB, workspace=self._grid_ws)
-        self.grid, self.binary_grid = grid, binary
-        return float(count.item()) / binary.numel()      # the one host sync the loop form also has
+        return grid_update_chain(                        # its one host sync the loop form also has
+            self, lambda slab, ws: ops.p4_grid_update(self.packed, self.net, self._tables_for_forward(), self.levels_d, self.levels_c,
+                                                      self.bound, self.grid.shape[0], self.grid_bound, self.grid_threshold,
+                                                      self.grid.clone(), decay, slab_cells=slab, workspace=ws),
+            ops.p4_grid_update_workspace_bytes)

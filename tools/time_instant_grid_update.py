@@ -8,31 +8,11 @@ five interleaved windows of 20 refreshes, a host clock around a final device syn
 Prints one JSON line and writes it to profiles/instant_grid_update_timing.json.  The measuring runs in a child process under
 `timeout`; this process never opens the GPU.
     python tools/time_instant_grid_update.py [--refreshes N] [--windows W] [--res R] [--limit SECONDS] [--legs loop,chain,graph]"""
-import argparse, json, os, statistics, subprocess, sys, time
+import os, sys
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-ap = argparse.ArgumentParser()
-ap.add_argument("--refreshes", type=int, default=20)
-ap.add_argument("--windows", type=int, default=5)
-ap.add_argument("--res", type=int, default=128)
-ap.add_argument("--limit", type=int, default=240, help="seconds the measuring child may take")
-ap.add_argument("--legs", default="loop,chain,graph", help="legs to time (a profiler run of the child takes one: --child --legs chain)")
-ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
-args = ap.parse_args()
+from grid_update_timing import ROOT, report, start
 
-if not args.child:
-    cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child", "--refreshes", str(args.refreshes),
-           "--windows", str(args.windows), "--res", str(args.res), "--legs", args.legs]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    sys.stderr.write(r.stderr)
-    if r.returncode != 0:
-        sys.exit(f"the measuring process ended with status {r.returncode}")
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
-    json.loads(line)
-    with open(os.path.join(ROOT, "profiles", "instant_grid_update_timing.json"), "w") as f:
-        f.write(line + "\n")
-    print(line, flush=True)
-    sys.exit(0)
+args = start(__file__, "instant_grid_update", 240)
 
 import torch
 import yaml
@@ -70,32 +50,9 @@ graph.replay()
 torch.cuda.synchronize()
 same_graph = bool(torch.equal(ref[0], captured[0]) and torch.equal(ref[1], captured[1]) and int(captured[2]) == int(ref[1].sum()))
 
-
-def timed(fn, n):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / n
-
-
-legs = [(name, fn) for name, fn in (("loop", loop), ("chain", chain), ("graph", graph.replay)) if name in args.legs.split(",")]
-ms = {name: [] for name, _ in legs}
-for name, fn in legs:
-    timed(fn, 5)                                         # warm-up: allocations, code objects, clocks
-for _ in range(args.windows):
-    for name, fn in legs:
-        ms[name].append(timed(fn, args.refreshes))
 cells = args.res ** 3
 out = {"tool": "time_instant_grid_update", "grid": f"{args.res}^3", "cells": cells, "slab_cells": eng._GRID_SLAB,
        "slabs": (cells + eng._GRID_SLAB - 1) // eng._GRID_SLAB, "active_ratio": round(ratio, 4), "table": str(table.dtype).replace("torch.", ""),
        "refreshes_per_window": args.refreshes, "windows": args.windows, "chain_equals_loop": same, "graph_equals_loop": same_graph,
        "workspace_bytes": eng._grid_ws.numel(), "loop_workspace_bytes_per_batch": ops._lib.load().nerf_imlp_workspace_bytes(min(cells, 2 ** 18))}
-for name in ms:
-    out[name] = {"median_ms": round(statistics.median(ms[name]), 4), "min_ms": round(min(ms[name]), 4), "max_ms": round(max(ms[name]), 4)}
-if "loop" in ms and "chain" in ms:
-    out["chain_median_below_loop_min"] = bool(out["chain"]["median_ms"] < out["loop"]["min_ms"])
-if "chain" in ms and "graph" in ms:
-    out["graph_not_above_chain_max"] = bool(out["graph"]["median_ms"] <= out["chain"]["max_ms"])
-print(json.dumps(out), flush=True)
+report(args, out, loop, chain, graph.replay)
