@@ -591,9 +591,14 @@ int nerf_hash_encode_bwd_ws_store_precounted(const float* pts, int64_t n, int n_
  * occupancy grid, point count within ~10 % of the last call's) and reads the status block afterwards: 8 x u32, published by the
  * call's last launch at nerf_hash_encode_bwd_spec_status(workspace) (device) and, when status_host is given, in that host-mapped
  * pinned block as well (no copy launch; word [7] is written LAST, as 1, after a system-scope fence: a caller that cleared it before
- * the call may poll it instead of recording an event) -- [3] records that
- * overflowed, [4] != 0: records were LOST (overflow list full or estimates larger than the workspace): the gradient of that call is
- * incomplete, fall back to the counted form.  Levels of at most 256 slices (tables up to 2^20 entries per level); not with option "deterministic". */
+ * the call may poll it instead of recording an event) -- [0] work items, [1] and [5] record capacity planned, [2] fp32 bits of the
+ * largest |gradient|, [3] records that did not fit their bins (exactly the sum over the bins of max(true count - capacity, 0); they
+ * took the overflow list), [4] != 0: records were LOST (the overflow list of 2^20 records was full): the gradient of that call is
+ * incomplete, fall back to the counted form, [6] 1: the estimates (+ 1/8 + 64 per bin) exceeded the record area of this call's n --
+ * a batch that shrank -- and the capacities were scaled down to it in proportion; the area always holds the batch's own 8 L n
+ * records, so the call is complete all the same ([4] tells), [7] 1: published.  Whatever the estimates are, nothing is written outside
+ * workspace_bytes(n), the counts left for the next call are this batch's true ones, and a flagged call leaves every entry a partial
+ * sum of its own terms.  Levels of at most 256 slices (tables up to 2^20 entries per level); not with option "deterministic". */
 int nerf_hash_encode_bwd_spec_begin(void* workspace, nerf_stream_t stream);
 int nerf_hash_encode_bwd_ws_store_spec(const float* pts, int64_t n, int n_levels, const float* scale_host,
                                        const unsigned* res_host, const unsigned* size_host, const unsigned* offset_host,

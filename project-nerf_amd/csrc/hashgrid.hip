@@ -319,8 +319,9 @@ struct BinPlan {
 
 struct BinHeader {                             // start of the workspace
   unsigned n_items, n_records, amax_bits, n_overflow;  // amax_bits: largest |d_feat| of the call as fp32 bits
-  unsigned lost, spec_total, ticket, pad1;     // speculative form: records dropped (overflow list full / plan did not fit); total capacity;
-};                                             // ticket: workgroups of the call's last launch that are done
+  unsigned lost, spec_total, ticket, scaled;   // speculative form: records dropped (overflow list full); total capacity planned;
+};                                             // ticket: workgroups of the call's last launch that are done; scaled: the plan pass scaled the
+                                               // estimates down to the record area (status word [6])
 constexpr int kAmaxSlotWord = 32;              // words [32, 32 + kAmaxSlots) of the header area: a producer's running maxima of |d_feat| (common.h),
                                                // folded into amax_bits (and cleared) by the plan pass of the forms that do not count
 constexpr int kSpecStatusWord = 16;            // the speculative form's last launch publishes the header here (workspace + 64 bytes) ...
@@ -534,7 +535,11 @@ hash_bin_plan_kernel(HashLevels L, BinPlan plan, unsigned* __restrict__ count, u
   // det_int (option "deterministic" with a staging array): only the bins of DENSE levels are cut (chunk), the others never
   // est != null, spec_capacity == 0 (counted forms): the bins' true counts are also left in est for a later speculative call.
   // spec_capacity > 0 (speculative form): NO counts exist -- a bin's capacity is est + est / 8 + 64 (written to count[], which the
-  // later passes read as the bin's size), its records start at start[bin]; the reduce pass reads the true fill from cursor[]
+  // later passes read as the bin's size), its records start at start[bin]; the reduce pass reads the true fill from cursor[].
+  // The estimates are those of ANOTHER batch: where sum(est + est / 8 + 64) exceeds the record area (a batch that shrank -- the area
+  // is 1.25 x 8 L n + 64 per bin of THIS call's n), the capacities are scaled down to it: est * room / sum(est + est / 8) + 64 with
+  // room = spec_capacity - 64 bins.  Their total is then at most spec_capacity, the area still holds every record of the batch
+  // (8 L n <= room) and whatever misses its bin takes the overflow list as ever; header->scaled says so (status word [6]).
   // chunk: records per work item -- kChunk, or 0xffffffff (option "deterministic"): a bin is never cut, so no slice is
   // flushed with float atomics; the coarse dense levels' bins then serialise on one workgroup each
   __shared__ unsigned scan_r[1024], scan_i[1024], wave_r[16], wave_i[16];
@@ -558,12 +563,29 @@ hash_bin_plan_kernel(HashLevels L, BinPlan plan, unsigned* __restrict__ count, u
   unsigned pre[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) { const unsigned b = r * 1024 + threadIdx.x; pre[r] = b < n_bins ? src[b] : 0u; }
+  unsigned long long scale_num = 0, scale_den = 0;           // scale_den != 0: the capacities are scaled
+  if (spec_capacity) {                         // uniform.  One total over the bins, out of the preloaded rounds: one more barrier
+    __shared__ unsigned long long wave_want[16];
+    unsigned long long want = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) want += (unsigned long long)pre[r] + (pre[r] >> 3);
+    for (unsigned b = 4096 + threadIdx.x; b < n_bins; b += 1024) { const unsigned e = src[b]; want += (unsigned long long)e + (e >> 3); }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) want += __shfl_xor(want, off);
+    if ((threadIdx.x & 63) == 0) wave_want[threadIdx.x >> 6] = want;
+    __syncthreads();
+    want = 0;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) want += wave_want[w];
+    const unsigned long long margins = 64ull * n_bins;       // <= 64 kMaxBins, which bin_record_capacity holds on top of the records
+    if (want + margins > spec_capacity) { scale_num = spec_capacity - margins; scale_den = want; }
+  }
   for (unsigned base = 0; base < n_bins; base += 1024) {
     const unsigned b = base + threadIdx.x, round = base >> 10;
     unsigned c = round == 0 ? pre[0] : round == 1 ? pre[1] : round == 2 ? pre[2] : round == 3 ? pre[3] : (b < n_bins ? src[b] : 0u);
     if (b < n_bins) {
       if (spec_capacity) {
-        c = c + (c >> 3) + 64u;
+        c = scale_den ? (unsigned)((unsigned long long)c * scale_num / scale_den) + 64u : c + (c >> 3) + 64u;
         count[b] = c;
       } else if (est != nullptr) est[b] = c;
     }
@@ -641,10 +663,7 @@ hash_bin_plan_kernel(HashLevels L, BinPlan plan, unsigned* __restrict__ count, u
       header->spec_total = carry_r;
       header->n_overflow = 0;
       header->lost = 0;
-      if (carry_r > spec_capacity) {           // the estimates do not fit the workspace: nothing may be written
-        header->n_items = 0;
-        header->lost = 2;
-      }
+      header->scaled = scale_den ? 1u : 0u;    // (carry_r <= spec_capacity either way)
     }
   }
 }
@@ -941,7 +960,8 @@ hash_bin_overflow_kernel(BinHeader* __restrict__ header, const BinRecord* __rest
   __syncthreads();
   if (last == 0u || threadIdx.x >= 8) return;
   unsigned* h = reinterpret_cast<unsigned*>(header);
-  const unsigned word = threadIdx.x >= 6 ? 0u : atomicOr(&h[threadIdx.x], 0u);     // the coherent copy (other launches' atomics)
+  // the coherent copy (other launches' atomics) of header words 0..5; status word [6]: the header's `scaled`
+  const unsigned word = threadIdx.x == 7 ? 0u : atomicOr(&h[threadIdx.x == 6 ? 7 : threadIdx.x], 0u);
   if (threadIdx.x < 7) {
     h[kSpecStatusWord + threadIdx.x] = word;
     if (status_host != nullptr) status_host[threadIdx.x] = word;
@@ -1426,9 +1446,10 @@ extern "C" int nerf_hash_encode_bwd_ws_slots(void* workspace, int64_t n, int n_l
 }
 
 // device address of the 8-word status block the LAST speculative call published: [0] items, [1] record capacity planned, [2] largest
-// |gradient| bits, [3] records that went to the overflow list, [4] != 0: records were LOST (the gradient of that call is incomplete: 1
-// the overflow list was full, 2 the estimates did not fit the workspace), [5] capacity planned.  The same eight words go to the
-// status_host block given to the call (host-mapped pinned memory: readable once an event recorded behind the call has completed).
+// |gradient| bits, [3] records that did not fit their bins (sum over the bins of max(true count - capacity, 0)), [4] != 0: records were
+// LOST (the overflow list was full: the gradient of that call is incomplete), [5] capacity planned, [6] 1: the estimates exceeded the
+// record area and the capacities were scaled down to it (that by itself loses nothing: [4] tells), [7] 1: published.  The same eight words go
+// to the status_host block given to the call (host-mapped pinned memory: readable once an event recorded behind the call has completed).
 extern "C" const void* nerf_hash_encode_bwd_spec_status(const void* workspace) {
   return workspace == nullptr ? nullptr : static_cast<const char*>(workspace) + sizeof(unsigned) * kSpecStatusWord;
 }

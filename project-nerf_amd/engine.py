@@ -386,9 +386,9 @@ class InstantNgpEngine:
         # latency-bound forward cost more than the 0.05 ms count pass they replace): off by default
         self.precount = bool(cfg.get("precount", False))
         # speculative hash backward (default on, single rank): NO count pass -- the bins' capacities come from the true counts of the
-        # previous step's call; records that do not fit are added with atomics by a last small launch, a lost record (never seen in
-        # training; the status block is read back one step late) switches the form off.  Used when the occupancy grid is the one
-        # the estimates were taken on and the active-sample count is within 10 % of that call's
+        # previous step's call; records that do not fit are added with atomics by a last small launch, a lost record (the overflow
+        # list was full; the status block is read back one step late) switches the form off.  Used when the occupancy grid is the one
+        # the estimates were taken on and the active-sample count is within -50 % .. +10 % of that call's (specbwd.py)
         from .specbwd import SpeculativeScatter
         self.spec = SpeculativeScatter(bool(cfg.get("speculative_hash_backward", True)) and not os.environ.get("NERF_NO_SPECULATIVE_BWD"))  # env: A/B aid
         self._table_h_buf = torch.zeros(n_pad, device=self.device, dtype=torch.float16) if self.half_table else None

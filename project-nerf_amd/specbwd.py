@@ -5,9 +5,11 @@ run.py:619 / 1941).
 The speculative form skips the count pass: the bins' capacities come from the TRUE record counts the previous call on the same
 workspace left behind.  That is sound while consecutive batches fill the bins alike -- same occupancy grid, about the same number of
 active points -- which this class decides; a record that does not fit is added through an overflow list by the call's last launch,
-and that launch publishes eight status words into a host-mapped block ([3] overflowed records, [4] != 0: records were LOST, [7] = 1
-written last).  The block is read a step or two later without any event or copy launch; a lost record switches the engine back to
-the counted form for good (and warns: one step's table gradient was incomplete)."""
+and that launch publishes eight status words into a host-mapped block ([3] overflowed records, [4] != 0: records were LOST -- the
+overflow list was full --, [6] = 1: the estimates exceeded the record area of the call's point count and the capacities were scaled
+down to it, which loses nothing, [7] = 1 written last).  The block is read a step or two later without any event or copy launch; a
+lost record switches the engine back to the counted form for good (and warns: one step's table gradient was incomplete).
+``lost_calls``, ``scaled_calls`` and ``overflow_max`` (largest word [3]) count what the blocks read so far said."""
 from __future__ import annotations
 
 import warnings
@@ -28,6 +30,9 @@ class SpeculativeScatter:
         self._checks = {}                 # turn -> status block not yet read
         self.last_status: Optional[torch.Tensor] = None
         self.calls = 0
+        self.lost_calls = 0               # blocks read with [4] != 0
+        self.scaled_calls = 0             # blocks read with [6] != 0
+        self.overflow_max = 0             # largest [3] of the blocks read
 
     # -- decision ------------------------------------------------------------------------------------------------------
     def ok(self, ws_ptr: int, grid_id, n: int) -> bool:
@@ -46,7 +51,10 @@ class SpeculativeScatter:
         status = self._checks.pop(turn)
         if int(status[7]) == 0:                               # not published yet: wait for the stream (rare: the block is two calls old)
             torch.cuda.current_stream().synchronize()
+        self.overflow_max = max(self.overflow_max, int(status[3]) & 0xFFFFFFFF)
+        self.scaled_calls += int(status[6]) != 0
         if int(status[4]) != 0:
+            self.lost_calls += 1
             warnings.warn(f"speculative hash backward: records were lost (status {status.tolist()}): one step's table gradient was "
                           "incomplete; the counted form is used from here on")
             self.enabled = False

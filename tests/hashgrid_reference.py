@@ -341,6 +341,55 @@ def scatter_fixed_bound(count, abs_sum, amax, n_points, initial=None):
     return bound
 
 
+SLICE_LOG2 = 12        # a bin of the binned scatter: 4096 consecutive entries of one level (kSlice)
+
+
+def level_slices(levels):
+    """bins per level: ceil(size / 4096)"""
+    return [(int(lv.size) + (1 << SLICE_LOG2) - 1) >> SLICE_LOG2 for lv in levels]
+
+
+def bin_counts(ref, d_feat):
+    """int64 [bins]: records per bin of the binned scatter for the batch of ``ref`` (a HashReference).
+
+    A record is one corner of one (point, level) whose gradient pair is not (0, 0); its bin within the level is
+    (entry - offset) >> 12.  ``d_feat`` [n, 2L]: one table, the levels' bins one after the other.  ``d_feat`` [k, n, 2L]:
+    k tables of the same level structure scattered to from the same points -- the bins of virtual level table * L + level,
+    in that order (plan_bins of csrc/hashgrid.hip)."""
+    d = np.asarray(d_feat)
+    d = d[None] if d.ndim == 2 else d
+    slices = level_slices(ref.levels)
+    out = []
+    for k in range(d.shape[0]):
+        live = (d[k].reshape(ref.n, ref.n_levels, 2) != 0).any(axis=-1)          # [n, L]
+        for li, lv in enumerate(ref.levels):
+            local = (ref.idx[live[:, li], li, :] - int(lv.offset)) >> SLICE_LOG2
+            out.append(np.bincount(local.reshape(-1), minlength=slices[li]).astype(np.int64))
+    return np.concatenate(out)
+
+
+def planned_capacities(est):
+    """records the speculative form plans per bin from the counts ``est`` the previous call left: est + est / 8 + 64
+    (integer arithmetic, as the plan pass)"""
+    est = np.asarray(est, dtype=np.int64)
+    return est + (est >> 3) + 64
+
+
+def spec_overflow_bound(count, abs_sum, amax, n_points):
+    """Speculative binned scatter whose call was complete (status word [4] == 0):
+    |kernel - reference| <= scatter_fixed_bound + 2 * count * U * abs_sum.
+
+    A record that fits its bin is summed as in the counted form (scatter_fixed_bound, quantisation included).  A record
+    that does not fit keeps its 26-bit fixed-point term (the same quantisation, already charged per record) and reaches
+    d_table on its own: the integer, up to 25 magnitude bits, is converted to fp32 (one rounding, at most U times the
+    term, and the terms of an entry sum to at most abs_sum), then added with one float atomic onto a partial sum of the
+    entry's own terms (one rounding, at most U * abs_sum to first order).  At most ``count`` records of an entry
+    overflow: 2 * count * U * abs_sum on top of the counted form's bound, whatever the order of the atomics."""
+    count_col = np.asarray(count, dtype=np.float64)[:, None]
+    abs_sum = np.asarray(abs_sum, dtype=np.float64)
+    return scatter_fixed_bound(count, abs_sum, amax, n_points) + 2.0 * count_col * U * abs_sum
+
+
 C_INPUT_TERM = 16
 
 

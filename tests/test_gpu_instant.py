@@ -814,3 +814,58 @@ def test_instant_engine_speculative_backward_equals_counted_backward():
         assert abs(l1 - l0) < 1e-6 * max(l0, 1.0) and bool(torch.isfinite(t1).all())
         assert float((n1 - n0).abs().max()) <= 1e-5 * float(n0.abs().max())
         assert float((t1 - t0).abs().max()) <= 2e-6 * float(t0.abs().max())
+
+
+@pytest.mark.gpu
+def test_instant_engine_short_last_batch_takes_the_scaled_speculative_form():
+    """The shorter last batch of an epoch: two full steps of R = 6,144 rays (about 195 k active points on this grid), then the first
+    60 % of the rays (about 117 k) on the same grid -- inside the engine's window of 0.5 .. 1.1 of the last point count, but the
+    estimates of the full batch (+ 1/8 + 64 per bin: 28.2 M records) exceed the record area of the short one (23.0 M).  The step takes
+    the speculative form, the plan pass scales the capacities down to the area (status word [6]) and the gradient is complete: loss,
+    network gradient and table gradient against an engine that counts every step, at the bounds of the test above."""
+    import yaml
+    from conftest import ROOT
+    from project_nerf_amd.engine import InstantNgpEngine
+    ops_mod = __import__("project_nerf_amd").ops
+    cfg = yaml.safe_load(open(os.path.join(ROOT, "configs", "part2_instant.yaml.example")))
+    R, S = 6144, 64
+    short = R * 3 // 5
+    gen = torch.Generator().manual_seed(4)
+    o = torch.randn(R, 3, generator=gen)
+    o = (o / o.norm(dim=-1, keepdim=True) * 4.0311).cuda()
+    d = ((torch.rand(R, 3, generator=gen) - 0.5) * 1.6).cuda() - o
+    d = (d / d.norm(dim=-1, keepdim=True)).contiguous()
+    target = torch.rand(R, 3, generator=gen).cuda()
+    ax = torch.linspace(-1.5, 1.5, 128)
+    gx, gy, gz = torch.meshgrid(ax, ax, ax, indexing="ij")
+    grid = ((gx ** 2 + gy ** 2 + gz ** 2) < 1.2 ** 2).cuda()
+    runs = []
+    for spec in (True, False):
+        eng = InstantNgpEngine(dict(cfg, speculative_hash_backward=spec), seed=0)
+        eng.table.copy_((torch.rand(eng.table.numel(), generator=torch.Generator().manual_seed(5)) - 0.5).cuda())
+        eng.net[2048:2048 + 64] *= 20.0
+        ops_mod.imlp_pack(eng.net, eng.packed)
+        eng.binary_grid = grid
+        rec = []
+        for step, rays in enumerate((R, R, short)):
+            u = torch.rand(R, S, generator=torch.Generator().manual_seed(100 + step)).cuda()
+            eng.g_table.fill_(float("nan"))
+            before = eng.spec.calls
+            loss = float(eng.compute_gradients(o[:rays].contiguous(), d[:rays].contiguous(), target[:rays].contiguous(), S,
+                                               u=u[:rays].contiguous()))
+            rec.append((loss, eng.g_net.clone(), eng.g_table.clone()))
+        runs.append(rec)
+        if spec:
+            assert eng.spec.calls == before + 1 and eng.spec.calls >= 2, (before, eng.spec.calls)      # the short step was speculative
+            torch.cuda.synchronize()
+            status = eng.spec.last_status.tolist()
+            eng.spec.ok(0, None, 0)                                # reads every published block (and trusts nothing: no such workspace)
+            print(f"[instant, short last batch] status {status}; overflow_max {eng.spec.overflow_max}, scaled_calls {eng.spec.scaled_calls}")
+            assert status[7] == 1 and status[6] == 1 and status[4] == 0, status
+            assert eng.spec.lost_calls == 0 and eng.spec.scaled_calls == 1 and eng.spec.enabled
+        else:
+            assert eng.spec.calls == 0
+    for (l1, n1, t1), (l0, n0, t0) in zip(*runs):
+        assert abs(l1 - l0) < 1e-6 * max(l0, 1.0) and bool(torch.isfinite(t1).all())
+        assert float((n1 - n0).abs().max()) <= 1e-5 * float(n0.abs().max())
+        assert float((t1 - t0).abs().max()) <= 2e-6 * float(t0.abs().max())

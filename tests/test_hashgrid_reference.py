@@ -148,6 +148,63 @@ def test_bounds_follow_their_derivations():
     assert np.array_equal(H.input_gradient_bound(np.asarray([1.0]), 16), [32 * H.U])
     assert np.array_equal(H.input_gradient_bound(np.asarray([1.0]), 16, np.asarray([3.0]), initial_adds=16), [(32 + 16 * 4) * H.U])
     assert H.worst_fraction([1.0, 5.0], [2.0, 0.0]) == 0.5
+    # the speculative form's overflow records: two more roundings per record on top of the counted form's bound
+    spec = H.spec_overflow_bound(count, abs_sum, 1.0, 5000)
+    assert np.all(spec >= fixed) and np.array_equal(spec[0], [0.0, 0.0])
+    assert np.array_equal(spec[1], fixed[1] + 2.0 * 3 * H.U * abs_sum[1])
+    assert np.array_equal(H.planned_capacities([0, 7, 8, 1000]), [64, 71, 73, 1189])
+
+
+@pytest.mark.parametrize("name", TABLES)
+def test_bin_counts_cover_every_live_record(cases, name):
+    """sum of the bins = 8 records per live (row, level); three tables: the bins of virtual level table * L + level"""
+    c = cases[name]
+    ref, d_feat = c["ref"], c["d_feat"]
+    n_levels = ref.n_levels
+    live = (d_feat.reshape(ref.n, n_levels, 2) != 0).any(axis=-1)
+    assert live[::7].sum() == 0 and live.sum() == (ref.n - len(range(0, ref.n, 7))) * n_levels
+    bins = H.bin_counts(ref, d_feat)
+    slices = H.level_slices(c["levels"])
+    assert bins.shape == (sum(slices),) and bins.dtype == np.int64
+    assert int(bins.sum()) == 8 * int(live.sum())
+    if name == "instant_l16_t19":
+        assert sum(slices) == 1592
+    # per level: exactly that level's records
+    first = np.concatenate([[0], np.cumsum(slices)])
+    for li in range(n_levels):
+        assert int(bins[first[li]:first[li + 1]].sum()) == 8 * int(live[:, li].sum())
+    # a level whose gradient columns are zero everywhere has no record
+    d2 = d_feat.copy()
+    d2[:, 0:2] = 0.0
+    assert int(H.bin_counts(ref, d2)[:slices[0]].sum()) == 0
+    # a pair with ONE non-zero component is live
+    d3 = np.zeros_like(d_feat)
+    d3[3, 1] = 1e-30
+    assert int(H.bin_counts(ref, d3).sum()) == 8
+    three = np.stack([d_feat, d2, np.zeros_like(d_feat)])
+    stacked = H.bin_counts(ref, three)
+    assert np.array_equal(stacked, np.concatenate([bins, H.bin_counts(ref, d2), np.zeros_like(bins)]))
+
+
+def test_bin_counts_equal_a_brute_force_loop():
+    n_levels, log2_t, base, pls, bound = 5, 14, 16, 1.5, 1.5         # 4920-entry dense level 0 (two slices), hashed levels of four
+    levels = O.hash_grid_levels(n_levels, log2_t, base, pls)
+    pts = H.random_batch(bound, 40, 3)
+    rng = np.random.default_rng(4)
+    d_feat = rng.standard_normal((40, 2 * n_levels))
+    d_feat[::3] = 0.0
+    d_feat[5, 2:4] = 0.0
+    ref = H.HashReference(pts, levels, bound)
+    slices = H.level_slices(levels)
+    assert max(slices) > 1
+    want = [np.zeros(s, dtype=np.int64) for s in slices]
+    for p in range(40):
+        for li in range(n_levels):
+            if d_feat[p, 2 * li] == 0.0 and d_feat[p, 2 * li + 1] == 0.0:
+                continue
+            for k in range(8):
+                want[li][(int(ref.idx[p, li, k]) - int(levels[li].offset)) // 4096] += 1
+    assert np.array_equal(H.bin_counts(ref, d_feat), np.concatenate(want))
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
