@@ -52,7 +52,8 @@ extern "C" {
 /* 13: the Part 4 occupancy-grid refresh as one density-only launch chain, nerf_p4_grid_update*, is new. */
 /* 14: the Part 3 (MLP deformation) occupancy-grid refresh as one density-only launch chain, nerf_p3_grid_update*, is new. */
 /* 15: the Part 3 (hash-grid canonical field) evaluation launch chain, nerf_p3_render_*, is new. */
-#define NERF_ABI_VERSION 15
+/* 16: the Part 3 (8x256 canonical field, standard and direct time conditioning) evaluation launch chain, nerf_p3_nerf_render_*, is new. */
+#define NERF_ABI_VERSION 16
 
 typedef void* nerf_stream_t;
 
@@ -781,6 +782,36 @@ int nerf_p3_render_rays_fwd(const void* packed_deform, const void* packed_canon,
                             int64_t n_rays, int n_samples, float near_plane, float far_plane, const float* time_dev,
                             const float* bg, int64_t bg_rows, int64_t chunk_rays, void* workspace, float* out_rgb,
                             float* out_depth, float* out_acc, nerf_stream_t stream);
+
+/* ---- a1 + a2 + a5 + a6 + a10 + f2: evaluation of Part 3 with the 8x256 canonical field as one launch chain ----
+ * replaces render_image's chunk loop (src/renderer.py:387-418) around render_rays(perturb=False) for mode part3 with
+ * canonical_type nerf, the field query being the Part 3 forward of NeuralField (src/core.py:108-146: deformation MLP
+ * src/decoders.py:165-195, NeRFDecoder on [code(x_c) | code(t)]; under direct_time_conditioning the decoder on
+ * [code(x) | code(t)] alone).  This field has no occupancy grid: a frame is dense.  A frame is rendered at ONE time;
+ * per chunk of `chunk_rays` rays, on the caller's stream: nerf_sample_rays (plain depths, points and directions) ->
+ * deformation chain at the scalar time -> x_c -> canonical chain at (x_c, the scalar time, directions) ->
+ * nerf_composite_fwd.  Four launches per chunk, three under direct time conditioning; the two field launches read the
+ * time from DEVICE memory: no allocation, no host read, no event, no synchronisation; the whole frame can be captured
+ * in a hipGraph (one linear chain) and replayed at another time after the time word (like the rays and the packed
+ * images) was overwritten in place.  Results are bit-identical to the same steps called one by one with a time vector
+ * that repeats the time (nerf_sample_rays, nerf_p3_deform_fwd, nerf_p3_canon_fwd with train 0, nerf_composite_fwd).
+ *   packed_deform: nerf_p3_deform_pack's image, or NULL: direct time conditioning -- no deformation launch, the
+ *   canonical chain reads the sampled points themselves.  packed_canon: nerf_p3_canon_pack's image (256-byte aligned;
+ *   its time_dim was fixed when it was packed).  rays_o / rays_d [n_rays,3]; 2 <= n_samples <= 1024; time_dev: ONE fp32
+ *   on the device; bg / bg_rows as nerf_composite_fwd (bg NULL, or bg_rows in {1, n_rays}); chunk_rays > 0,
+ *   chunk_rays * n_samples < 2^31.
+ *   workspace: nerf_p3_nerf_render_workspace_bytes(chunk_rays, n_samples) bytes, 256-byte aligned, contents
+ *   irrelevant.  With n = chunk_rays * n_samples, every piece rounded up to 256 bytes: z n*4, pts n*12, dirs n*12,
+ *   x_c n*12 (laid out under direct time conditioning too: one formula), sigma n*4, rgb n*12 -- 56 bytes per sample.
+ *   The query returns 0 for non-positive arguments.
+ * A bad argument returns NERF_EINVAL before anything is launched; n_rays == 0 is a successful no-op. */
+size_t nerf_p3_nerf_render_workspace_bytes(int64_t chunk_rays, int n_samples);
+int nerf_p3_nerf_render_rays_fwd(const void* packed_deform /* NULL: direct time conditioning */,
+                                 const void* packed_canon, const float* rays_o, const float* rays_d,
+                                 int64_t n_rays, int n_samples, float near_plane, float far_plane,
+                                 const float* time_dev, const float* bg, int64_t bg_rows, int64_t chunk_rays,
+                                 void* workspace, float* out_rgb, float* out_depth, float* out_acc,
+                                 nerf_stream_t stream);
 
 /* ---- a9 + a14: compositing fused with the MSE loss and its backward --------------------------
  * replaces, for one training step, volume_render (src/renderer.py:204-237), nn.MSELoss

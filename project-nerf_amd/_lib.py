@@ -71,6 +71,9 @@ PROTOTYPES = {
     "nerf_p3_render_workspace_bytes": (size_t, [i64, i32]),
     "nerf_p3_render_rays_fwd": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, f32, c_ptr, i32, f32, c_ptr, c_ptr, i64, i32,
                                       f32, f32, c_ptr, c_ptr, i64, i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "nerf_p3_nerf_render_workspace_bytes": (size_t, [i64, i32]),
+    "nerf_p3_nerf_render_rays_fwd": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, i64, i32, f32, f32, c_ptr, c_ptr, i64, i64, c_ptr, c_ptr, c_ptr, c_ptr,
+                                           c_ptr]),
     "nerf_render_rays_grid_workspace_bytes": (size_t, [i64, i32]),
     "nerf_render_rays_grid_fwd": (i32, [c_ptr, c_ptr, i32, f32, c_ptr, c_ptr, i64, i32, f32, f32, c_ptr, i64, i64, c_ptr, c_ptr, c_ptr, c_ptr,
                                         c_ptr]),
@@ -186,7 +189,7 @@ PROTOTYPES = {
     "nerf_adamw_clip_step_shadow": (i32, [c_ptr, c_ptr, c_ptr, c_ptr, i64, i32, f32, f32, f32, f32, f32, c_ptr, f32, f32, c_ptr, c_ptr]),
 }
 
-ABI_VERSION = 15    # the NERF_ABI_VERSION of include/nerf_hip.h this table was written against
+ABI_VERSION = 16    # the NERF_ABI_VERSION of include/nerf_hip.h this table was written against
 
 _lib = None
 

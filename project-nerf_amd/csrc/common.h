@@ -119,6 +119,13 @@ int hash_fwd_counted_f16(const float* pts, const unsigned* count, int64_t capaci
                          const LevelArgs& levels, void* out_nat, nerf_stream_t stream);
 int p4_canon_fwd_counted(const void* packed, const void* hash_nat, const float* dirs, const unsigned* count, int64_t capacity,
                          const float* time_dev, float* rgb, float* sigma, nerf_stream_t stream);
+// The two field launches of nerf_p3_nerf_render_rays_fwd (render_p3_nerf.hip) per chunk, on rows [0, n) of nerf_sample_rays's pts / dirs
+// (n on the host: the 8x256 canonical field has no occupancy grid) at the time *time_dev, a DEVICE word.  p3deform.hip: the deformation
+// MLP at the scalar time, x_c [n,3] fp32 and nothing else; p3canon.hip: the canonical inference chain at (code(x), code of the scalar,
+// code(dirs)).
+int p3_deform_rows(const void* packed, const float* pts, int64_t n, const float* time_dev, float* x_canonical, nerf_stream_t stream);
+int p3_canon_fwd_scalar_time(const void* packed, const float* x, const float* dirs, int64_t n, const float* time_dev, float* rgb, float* sigma,
+                             nerf_stream_t stream);
 // mlp_fwd.hip: the 8x256 inference chain in point mode (64 samples per wave) on the first *count rows of pts / dirs, for
 // render_grid.hip's launch chain
 int mlp_fwd_counted(const void* packed, const float* pts, const float* dirs, const unsigned* count, int64_t capacity, float* rgb,

@@ -6,6 +6,8 @@
 //                  plan: six natural code k-steps at pts_layers.0 and at the skip; the codes are formed in registers from
 //                  x [n,3] and t [n] (and formed again at the skip instead of being held live through layers 0..3).  TRAIN:
 //                  blocked bf16 images of every layer input and the ReLU masks, as the vanilla forward writes them.
+//   fwd_scalar_time_kernel   the inference forward at ONE time read from a device word (CanonCodeScalar), for the evaluation launch
+//                  chain nerf_p3_nerf_render_rays_fwd (render_p3_nerf.hip); the same bits as fwd_kernel<false> at that time.
 //   dgrad_kernel   mlp_chain_body.h::chain_dgrad, the body of mlp_bwd.hip::mlp_bwd_kernel, on this layout's dgrad stream:
 //                  pre-activation gradient images.
 //   dcode_kernel   d code(x) = W0[:, :63]^T dz0 + W4[:, 256:319]^T dz4 from the bf16 images of dz0 / dz4, then the Fourier
@@ -152,6 +154,52 @@ __global__ void __launch_bounds__(kChainThreads, 2) fwd_kernel(const FwdArgs a) 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int col = lane & 31, half = lane >> 5;
   chain_forward<CanonFwd, TRAIN>(a, smem, tid, lane, wave, col, half);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last pass's look-ahead DMA must not outlive the wave
+}
+
+// The canonical chain of the Part 3 (8x256 canonical field) evaluation launch chain (nerf_p3_nerf_render_rays_fwd): fwd_kernel<false>
+// at ONE time, read from DEVICE memory.  CanonCodeScalar is CanonCode with t = *a.time_dev instead of a.t[nc]: code_operand, the
+// direction code and again() are the same calls on the same values, so rgb and sigma keep fwd_kernel<false>'s bits when a.t holds that
+// time in every row.  The training-image pointers exist because chain_forward names them; TRAIN is false and they stay NULL.
+struct FwdScalarArgs {
+  const char* packed;
+  const float* x;        // [n,3] x_c, or x under direct time conditioning
+  const float* time_dev; // ONE fp32
+  const float* dirs;     // [n,3]
+  int64_t n, n_pad;
+  float* rgb;
+  float* sigma;
+  __bf16* st_xenc;
+  __bf16* st_h;
+  __bf16* st_feat;
+  __bf16* st_hv;
+  __bf16* st_denc;
+  uint4* st_mask;
+};
+struct CanonCodeScalar {
+  static constexpr int kKs = cplan::kCodeKs;
+  float x0, x1, x2, t;
+  __device__ __forceinline__ void form(const FwdScalarArgs& a, int64_t nc, int half, bf16x8 (&code)[kKs], bf16x8 (&denc)[2]) {
+    x0 = a.x[nc * 3 + 0]; x1 = a.x[nc * 3 + 1]; x2 = a.x[nc * 3 + 2]; t = *a.time_dev;
+    code_operand(x0, x1, x2, t, half, code);
+    fourier_operand<2, plan::kDirDim>(a.dirs[nc * 3 + 0], a.dirs[nc * 3 + 1], a.dirs[nc * 3 + 2], half, denc);
+  }
+  __device__ __forceinline__ void again(int half, const bf16x8 (&)[kKs], bf16x8 (&out)[kKs]) const {
+    code_operand(x0, x1, x2, t, half, out);
+  }
+};
+struct CanonFwdScalar {
+  using Chain = nerf::Chain<cplan::kFwdChunks, cplan::step_of, false, false>;
+  using Code = CanonCodeScalar;
+  static constexpr size_t kStreamOff = cplan::kPackFwdOff, kBiasOff = cplan::kPackBiasOff;
+};
+
+__global__ void __launch_bounds__(kChainThreads, 2) fwd_scalar_time_kernel(const FwdScalarArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int col = lane & 31, half = lane >> 5;
+  chain_forward<CanonFwdScalar, false>(a, smem, tid, lane, wave, col, half);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last pass's look-ahead DMA must not outlive the wave
 }
 
@@ -474,6 +522,22 @@ extern "C" int nerf_p3_canon_fwd(const void* packed, void* workspace, const floa
   if (train) hipLaunchKernelGGL(p3c::fwd_kernel<true>, dim3(grid), dim3(kChainThreads), kChainLds, as_stream(stream), a);
   else hipLaunchKernelGGL(p3c::fwd_kernel<false>, dim3(grid), dim3(kChainThreads), kChainLds, as_stream(stream), a);
   return check_launch("nerf_p3_canon_fwd");
+}
+
+// The canonical launch of nerf_p3_nerf_render_rays_fwd per chunk (common.h; render_p3_nerf.hip has checked the entry's arguments): rows
+// [0, n) of x / dirs at the time *time_dev, nerf_p3_canon_fwd's inference launch shape.
+int nerf::p3_canon_fwd_scalar_time(const void* packed, const float* x, const float* dirs, int64_t n, const float* time_dev, float* rgb,
+                                   float* sigma, nerf_stream_t stream) {
+  NERF_REQUIRE(n > 0 && n < ((int64_t)1 << 31) && packed && x && dirs && time_dev && rgb && sigma && ((uintptr_t)packed & 255) == 0,
+               "nerf_p3_nerf_render_rays_fwd (canonical chain): bad arguments");
+  p3c::FwdScalarArgs a{};
+  a.packed = static_cast<const char*>(packed);
+  a.x = x; a.time_dev = time_dev; a.dirs = dirs; a.n = n; a.n_pad = (n + 255) / 256 * 256; a.rgb = rgb; a.sigma = sigma;
+  const int grid = grid_for(a.n_pad / kTileSamples, 1);
+  if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_p3_nerf_render_rays_fwd: cannot query device");
+  if (int rc = ensure_dynamic_lds((const void*)p3c::fwd_scalar_time_kernel, kChainLds, "nerf_p3_nerf_render_rays_fwd"); rc != NERF_OK) return rc;
+  hipLaunchKernelGGL(p3c::fwd_scalar_time_kernel, dim3(grid), dim3(kChainThreads), kChainLds, as_stream(stream), a);
+  return check_launch("nerf_p3_nerf_render_rays_fwd (canonical chain)");
 }
 
 extern "C" int nerf_p3_canon_bwd(const void* packed, void* workspace, const float* x, const float* rgb, const float* sigma,

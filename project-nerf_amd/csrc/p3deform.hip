@@ -263,6 +263,20 @@ __global__ void __launch_bounds__(kThreads) deform_counted_kernel(const char* pa
   });
 }
 
+// The deformation chain of the Part 3 (8x256 canonical field) evaluation launch chain (nerf_p3_nerf_render_rays_fwd): the same body on
+// rows [0, n) of nerf_sample_rays's pts -- that field has no occupancy grid, every sample of the chunk is a row, so n (> 0) is known on
+// the host -- at the time *time_dev, read from DEVICE memory once at entry.  The padded row count is formed here, as above.
+__global__ void __launch_bounds__(kThreads) deform_rows_kernel(const char* packed, const float* __restrict__ pts, int64_t n,
+                                                               const float* __restrict__ time_dev, float* __restrict__ xc) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const float t = *time_dev;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
+  deform_scalar_time(smem, packed, t, n, (n + kTile - 1) / kTile * kTile, xc, tid, lane, wave, col, half, [&](int64_t row, float (&x)[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) x[c] = pts[row * 3 + c];
+  });
+}
+
 __global__ void __launch_bounds__(kThreads) dgrad_kernel(const Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
@@ -507,4 +521,16 @@ int nerf::p3_deform_counted(const void* packed, const float* pts, const unsigned
   hipLaunchKernelGGL(p3::deform_counted_kernel, dim3(grid), dim3(p3::kThreads), p3::kFwdLds, as_stream(stream),
                      static_cast<const char*>(packed), pts, count, capacity, time_dev, x_canonical);
   return check_launch("nerf_p3_render_rays_fwd (deformation chain)");
+}
+
+// The deformation launch of nerf_p3_nerf_render_rays_fwd per chunk (common.h; render_p3_nerf.hip has checked the entry's arguments): rows
+// [0, n) of the chunk's pts, n on the host.
+int nerf::p3_deform_rows(const void* packed, const float* pts, int64_t n, const float* time_dev, float* x_canonical, nerf_stream_t stream) {
+  NERF_REQUIRE(n > 0 && packed && pts && time_dev && x_canonical, "nerf_p3_nerf_render_rays_fwd (deformation chain): bad arguments");
+  const int grid = grid_for((n + p3::kTile - 1) / p3::kTile, 1);   // one workgroup per CU (LDS)
+  if (grid <= 0) return fail(NERF_ELAUNCH, "nerf_p3_nerf_render_rays_fwd: cannot query device");
+  if (int rc = ensure_dynamic_lds((const void*)p3::deform_rows_kernel, p3::kFwdLds, "nerf_p3_nerf_render_rays_fwd"); rc != NERF_OK) return rc;
+  hipLaunchKernelGGL(p3::deform_rows_kernel, dim3(grid), dim3(p3::kThreads), p3::kFwdLds, as_stream(stream),
+                     static_cast<const char*>(packed), pts, n, time_dev, x_canonical);
+  return check_launch("nerf_p3_nerf_render_rays_fwd (deformation chain)");
 }

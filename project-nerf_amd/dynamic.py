@@ -201,6 +201,8 @@ def run_dynamic(cfg, args):
         o, d = o.reshape(-1, 3), d.reshape(-1, 3)
         if o.shape[0] == 0:
             return o.new_zeros(0, width, 3)
+        if eng is not None and part3 and render_chain and use_engine3n:     # Part3NerfEngine's chain is a method of its own
+            return eng.render_image_chain(o.contiguous(), d.contiguous(), t.reshape(1, 1), render_n, chunk=chunk, bg=eval_bg).view(rows, width, 3)
         if eng is not None and part3:               # a Part 3 engine renders validation and test views itself
             return eng.render_image(o.contiguous(), d.contiguous(), t.reshape(1, 1), render_n, chunk=chunk, bg=eval_bg,
                                     chain=render_chain).view(rows, width, 3)
@@ -279,16 +281,18 @@ def run_dynamic(cfg, args):
                          "part4, or mode part3 with canonical_type instant): the refresh chain is the flat-parameter engine's -- the "
                          "module path and Part3NerfEngine, which has no occupancy grid, have none")
     # render_chain: true (mode part3) -- validation and test views as one launch chain per row band:
-    # Part3InstantEngine.render_image(chain=True), nerf_p3_render_rays_fwd
+    # Part3InstantEngine.render_image(chain=True), nerf_p3_render_rays_fwd; Part3NerfEngine.render_image_chain, nerf_p3_nerf_render_rays_fwd
     render_chain = part3 and bool(cfg.get("render_chain", False))
     if render_chain and args.eval_only:
         say(">>> render_chain: true has no effect with --eval_only (no engine is built); the views render through the module path")
         render_chain = False
-    elif render_chain and not use_engine3:
-        raise ValueError("render_chain: true needs Part3InstantEngine (engine: true, canonical_type instant, use_density_grid and the "
-                         "compiled shapes): the evaluation chain is that engine's -- the module path and Part3NerfEngine have none")
+    elif render_chain and not (use_engine3 or use_engine3n):
+        raise ValueError("render_chain: true needs a Part 3 engine (engine: true and the compiled shapes; Part3InstantEngine for "
+                         "canonical_type instant with use_density_grid, Part3NerfEngine for canonical_type nerf): the evaluation chain "
+                         "is the engine's -- the module path has none")
     elif render_chain:
-        say(">>> render_chain: validation and test views as one launch chain per row band (nerf_p3_render_rays_fwd)")
+        say(">>> render_chain: validation and test views as one launch chain per row band "
+            f"({'nerf_p3_nerf_render_rays_fwd' if use_engine3n else 'nerf_p3_render_rays_fwd'})")
     if world > 1 and not args.eval_only:
         say(f">>> data parallel: {world} ranks x {local} rays (global batch {local * world}); clip after the all-reduce")
     sync_async = parallel.allreduce_sum_async if world > 1 else None

@@ -1135,6 +1135,43 @@ def p3_render_rays_fwd(packed_d: Tensor, packed_c: Tensor, table: Tensor, levels
     return out, depth, acc
 
 
+def p3_nerf_render_workspace_bytes(chunk: int, n_samples: int) -> int:
+    return _lib.load().nerf_p3_nerf_render_workspace_bytes(chunk, n_samples)
+
+
+def p3_nerf_render_rays_fwd(packed_d: Optional[Tensor], packed_c: Tensor, rays_o: Tensor, rays_d: Tensor, n_samples: int, near: float,
+                            far: float, time: Tensor, bg: Optional[Tensor] = None, chunk: int = 16384, workspace: Optional[Tensor] = None):
+    """(rgb [R,3], depth [R], acc [R]) of the Part 3 field with the 8x256 canonical field at ONE time, every sample of every ray (this
+    field has no occupancy grid), for any number of rays: one launch chain over chunks of ``chunk`` rays in one reused workspace
+    (nerf_p3_nerf_render_rays_fwd) -- plain depths and points, the deformation chain at the scalar time, the canonical chain at x_c,
+    compositing; the time stays on the device, nothing is allocated or waited for between the launches.  ``packed_d``:
+    part3.deform_pack's image, or None: direct time conditioning (no deformation launch, the canonical chain at the points
+    themselves); ``packed_c``: part3_nerf.canon_pack's image; ``time``: a ONE-element fp32 device tensor, read by the kernels
+    (overwrite it in place to replay a captured frame at another time); ``workspace``: uint8, at least
+    p3_nerf_render_workspace_bytes(chunk, n_samples) bytes (allocated here otherwise)."""
+    lib = _lib.load()
+    rays_o, rays_d = _dev(rays_o, "rays_o"), _dev(rays_d, "rays_d")
+    packed_d = None if packed_d is None else _dev(packed_d, "packed_d", torch.uint8)
+    packed_c = _dev(packed_c, "packed_c", torch.uint8)
+    if not isinstance(time, Tensor) or time.numel() != 1:
+        raise ValueError("p3_nerf_render_rays_fwd: time must be a one-element fp32 device tensor")
+    time = _dev(time, "time")
+    R = rays_o.shape[0]
+    chunk = max(1, min(int(chunk), max(R, 1)))
+    need = lib.nerf_p3_nerf_render_workspace_bytes(chunk, n_samples)
+    if workspace is None:
+        workspace = torch.empty(need, device=rays_o.device, dtype=torch.uint8)
+    elif _dev(workspace, "workspace", torch.uint8).numel() < need:
+        raise ValueError(f"p3_nerf_render_rays_fwd: workspace of {workspace.numel()} bytes, {need} needed for chunk {chunk} x {n_samples}")
+    bg = None if bg is None else _dev(bg, "bg")
+    out = torch.empty(R, 3, device=rays_o.device)
+    depth, acc = torch.empty(R, device=rays_o.device), torch.empty(R, device=rays_o.device)
+    _lib.check(lib.nerf_p3_nerf_render_rays_fwd(_p(packed_d), _p(packed_c), _p(rays_o), _p(rays_d), R, n_samples, float(near), float(far),
+                                                _p(time), _p(bg), _bg_rows(bg), chunk, _p(workspace), _p(out), _p(depth), _p(acc), _stream()),
+               "nerf_p3_nerf_render_rays_fwd")
+    return out, depth, acc
+
+
 def _grid_update_args(name: str, workspace_bytes, device, resolution, prev, slab_cells, workspace, n_points: Optional[int] = None,
                       fresh: bool = False):
     """the checked arguments and the allocated outputs of the three occupancy-grid refresh chains (``name``: the entry, for the

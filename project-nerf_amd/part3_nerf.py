@@ -23,6 +23,7 @@ import torch
 from . import _lib, flat_params, ops
 from . import part3 as p3
 from .dynamic_engine import DynamicEngine, clip_adamw_flat, composite_mse_reg_bwd, normsq_flat, sample_inputs
+from .flat_engine import render_counted_chain
 
 Tensor = torch.Tensor
 P = lambda t: None if t is None else t.data_ptr()
@@ -277,3 +278,22 @@ class Part3NerfEngine(DynamicEngine):
         rgb, sigma, _ = self.field(pts, dirs, t)
         out_rgb, depth, acc, _ = ops.composite(rgb.view(R, n_samples, 3), sigma.view(R, n_samples), z, rays_d.contiguous(), bg)
         return out_rgb, depth, acc
+
+    _chain_ws = None           # render_image_chain: one workspace per (chunk, n_samples)
+    _chain_time = None         # ... and the one time word its kernels read
+
+    @torch.no_grad()
+    def render_image_chain(self, rays_o: Tensor, rays_d: Tensor, time: Tensor, n_samples: int, chunk: Optional[int] = None,
+                           bg: Optional[Tensor] = None) -> Tensor:
+        """one view at one time as ONE launch chain (nerf_p3_nerf_render_rays_fwd): the time stays on the device, no time vector, no
+        delta_x and no allocation per chunk, the deformation on its scalar-time kernel; the same bits as render_image.  A method of
+        its own: render_image(chain=True) keeps raising on this engine, as update_grid(chain=True) / update_grid_chain split on
+        Part3InstantEngine."""
+        if self._chain_ws is None:
+            self._chain_ws, self._chain_time = {}, torch.zeros(1, device=self.device)
+        self._chain_time.copy_(time.reshape(1))
+        bg = self.bg if bg is None else bg
+        return render_counted_chain(
+            lambda o, d, chunk, ws: ops.p3_nerf_render_rays_fwd(self.packed_d, self.packed_c, o, d, n_samples, self.near, self.far,
+                                                                self._chain_time, bg, chunk, workspace=ws),
+            ops.p3_nerf_render_workspace_bytes, self._chain_ws, rays_o, rays_d, n_samples, chunk or self.RENDER_CHUNK, self.device)
